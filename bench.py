@@ -14,6 +14,12 @@ torch.distributed.run on 127.0.0.1) or, explicitly,
          --master-port P bench.py --gpus N --steps K --warmup W
 One process per GPU; the path shards over independent pairs, so there is no data-path collective
 (weak scaling: per-GPU batch fixed).  Rank 0 prints ONE JSON line.
+
+A plain run measures the headline only: set-up, --warmup steps, --steps timed steps, the result line (`value`,
+`ms_per_step`, the arithmetic and guard statistics of those steps).  `--full` adds everything else this file measures:
+the per-kernel HIP-event timers and the roofline (armed during the timed steps), the bf16x6 and discarded-stages legs,
+the other BASELINE configs, the training steps and the CPU baseline.  `--dump-outputs DIR` writes what the last timed
+step returned (see dump_outputs); the inputs and weights are seeded, so equal arguments give equal inputs.
 """
 import argparse
 import json
@@ -72,6 +78,11 @@ def parse():
     ap.add_argument("--dry-collective", action="store_true", help="multi-GPU readiness check only: bring the process group up, run the collective "
                     "self-test (world size the backend reports, checked rank-id collectives, one timed all-reduce) and print the gradient bucket "
                     "plan of both training steps; nothing is benchmarked")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: the per-kernel timers and roofline, "
+                    "the bf16x6 and discarded-stages legs, the other BASELINE configs, the training steps and the CPU baseline (the --no-* "
+                    "options above trim this set); without it a run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned "
+                    "(fused image and labels: a fixed seeded sample, plus exact per-pair summaries) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -334,6 +345,42 @@ def config_leg(backbone, B, H, W, steps, graph=False):
     return rec
 
 
+DUMP_SEED = 1234
+DUMP_SAMPLE = {"fused": 8 * 2 ** 20, "labels": 4 * 2 ** 20}  # float32 elements drawn per output: 48 MiB in all
+
+
+def _dump_sample(t, k, seed):
+    """Values of t at up to k flat positions drawn from a generator seeded by seed + t's size: the same positions in every
+    run with the same arguments.  The whole tensor when it holds no more than k elements."""
+    flat = t.reshape(-1)
+    n = flat.numel()
+    if n <= k:
+        return flat
+    g = torch.Generator().manual_seed(seed + n)
+    idx = torch.unique(torch.randint(0, n, (k,), generator=g))  # sorted, duplicates dropped
+    return flat.index_select(0, idx.to(flat.device))
+
+
+def dump_outputs(dirname, fused, labels, num_classes):
+    """--dump-outputs: what a caller of the timed path received from its last step - fused RGB (B,3,H,W) fp32 and argmax
+    labels (B,H,W) - as float32 samples at fixed seeded positions (DUMP_SAMPLE), and beside them two exact summaries of the
+    whole outputs in float64: the sum of each pair's fused channels and each pair's label histogram."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    B = labels.shape[0]
+    pair = torch.arange(B, device=labels.device).view(B, 1, 1)
+    arrays = {
+        "fused_sample": _dump_sample(fused, DUMP_SAMPLE["fused"], DUMP_SEED).float(),
+        "labels_sample": _dump_sample(labels, DUMP_SAMPLE["labels"], DUMP_SEED).float(),
+        "fused_sum_per_pair_channel": fused.double().sum(dim=(2, 3)),
+        "labels_count_per_pair_class": torch.bincount((labels.long() + num_classes * pair).reshape(-1),
+                                                      minlength=B * num_classes).view(B, num_classes).double(),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a.cpu().numpy())
+    print(f"[bench] wrote {', '.join(n + '.npy' for n in arrays)} to {dirname}", file=sys.stderr, flush=True)
+
+
 def dry_collective(args, rank, world):
     """--dry-collective: what the first real multi-GPU run should print before anything is timed."""
     from segmif_amd import dist
@@ -401,26 +448,30 @@ def main():
         pipe.capture(ir, vis, mask)  # (f16x3: the graph carries its own range guard, read back after every replay)
 
     def step():
-        return pipe(ir, vis, mask)[1]
+        return pipe(ir, vis, mask)  # (fused, labels)
 
     fence = dist.fence
 
     with torch.no_grad():
         for _ in range(args.warmup):
-            labels = step()
+            outs = step()
         timer, side = None, {}
-        if not args.no_kernel_timer:
+        if args.full and not args.no_kernel_timer:
             timer = ops.LaunchTimer("drdb_dcov")
             side = {t: ops.LaunchTimer(t) for t in ("dwconv", "cp_gram", "cp_tail", "bilinear", "mixffn")}
             ops.set_launch_timer(timer, side)
         fence()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            labels = step()
+            outs = step()
         fence()
         elapsed = time.perf_counter() - t0
         ops.set_launch_timer(None)
+    labels = outs[1]
     assert labels.shape == (B, H, W)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs[0], labels, 9)
+    del outs
 
     rank_ms = dist.gather_over_ranks(1000.0 * elapsed / args.steps)  # per-rank spread: a slow GPU / link shows here
     elapsed = dist.max_over_ranks(elapsed)
@@ -432,7 +483,7 @@ def main():
 
     # for continuity with rounds 1-2: the same step on bf16 triples throughout (6 products per MAC, no range guard)
     elapsed_bf16 = None
-    if ops.conv3x3_mode() == "planes16" and not args.graph and not args.no_extras:
+    if args.full and ops.conv3x3_mode() == "planes16" and not args.graph and not args.no_extras:
         prev_mode, prev_lin = ops.set_conv3x3_mode("planes"), ops.set_linear_mode("bf16x6" if ops.linear_mode() == "f16x3" else ops.linear_mode())
         with torch.no_grad():
             step()
@@ -449,7 +500,7 @@ def main():
     # (the reference computes and drops them, core/mix_transformer.py:358-375) not computed - identical results
     enc = seg.denoise_net.encoder
     elapsed_dse = None
-    if not args.graph and not args.no_extras:
+    if args.full and not args.graph and not args.no_extras:
         enc.skip_unused_fusion_stages = True
         with torch.no_grad():
             step()
@@ -463,7 +514,7 @@ def main():
 
     # the other single-GPU forward configs of BASELINE.json, short legs in the same arithmetic (never part of `value`)
     configs = None
-    if world == 1 and not args.no_configs and not args.graph and (args.backbone, H, W) == ("mit_b3", 480, 640):
+    if args.full and world == 1 and not args.no_configs and not args.graph and (args.backbone, H, W) == ("mit_b3", 480, 640):
         configs = {}
         for key, cfg in (("config1_mit_b1_b4_480x640", ("mit_b1", 4, 480, 640)), ("config4_mit_b5_b2_1024x1024", ("mit_b5", 2, 1024, 1024)),
                          ("mit_b1_b64_480x640", ("mit_b1", 64, 480, 640))):
@@ -473,7 +524,7 @@ def main():
                 configs[key] = {"error": f"{type(exc).__name__}: {exc}"}
 
     train = None
-    if not args.no_train and not args.graph:
+    if args.full and not args.no_train and not args.graph:
         del pipe, labels
         torch.cuda.empty_cache()
         try:
@@ -604,7 +655,7 @@ def main():
             out["configs"] = configs
         if train is not None:
             out["train"] = train
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.backbone, H, W)
             out["speedup_vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
         print(json.dumps(out), flush=True)

@@ -172,6 +172,34 @@ def test_bench_main_self_launches_when_no_launcher_set_world_size(monkeypatch):
     assert called == {"gpus": 8}
 
 
+def test_bench_dump_outputs_fixed_sample_within_budget(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: float32 / float64 .npy files, the same seeded positions in every run, 64 MB at most
+    in all, and whole-output summaries that are exact."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", {"fused": 1000, "labels": 500})
+    B, H, W = 3, 20, 30
+    g = torch.Generator().manual_seed(0)
+    fused = torch.rand(B, 3, H, W, generator=g)
+    labels = torch.randint(0, 9, (B, H, W), generator=g, dtype=torch.int32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), fused, labels, 9)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["fused_sample.npy", "fused_sum_per_pair_channel.npy", "labels_count_per_pair_class.npy", "labels_sample.npy"]
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+    fs = np.load(tmp_path / "a" / "fused_sample.npy")
+    assert 900 < fs.size <= 1000 and np.isin(fs, fused.numpy().reshape(-1)).all()
+    assert np.array_equal(np.load(tmp_path / "a" / "fused_sum_per_pair_channel.npy"), fused.double().sum(dim=(2, 3)).numpy())
+    counts = np.load(tmp_path / "a" / "labels_count_per_pair_class.npy")
+    assert counts.shape == (B, 9) and (counts.sum(1) == H * W).all()
+    assert counts[1, 4] == int((labels[1] == 4).sum())
+    monkeypatch.undo()
+    assert 4 * sum(bench.DUMP_SAMPLE.values()) + 8 * 64 * 12 <= 64 * 2 ** 20  # the bench's own sample sizes, batch 64
+
+
 def test_bench_dry_collective_world_2_on_gloo():
     """`bench.py --gpus 2 --dry-collective` under torch.distributed.run with the collectives on gloo:
     rank 0 prints the world size the backend reports, the checked rank-id collectives, one timed all-reduce and the gradient

@@ -6,7 +6,7 @@ mkdir -p $out
 for r in $(seq 1 $R); do
   for v in A B; do
     if [ $v = A ]; then e="$A"; else e="$B"; fi
-    env $e timeout 200 python bench.py --steps 6 --warmup 2 --no-train --no-extras --no-cpu-baseline --no-configs > $out/bench_${v}_$r.json 2> $out/bench_${v}_$r.err
+    env $e timeout 200 python bench.py --full --steps 6 --warmup 2 --no-train --no-extras --no-cpu-baseline --no-configs > $out/bench_${v}_$r.json 2> $out/bench_${v}_$r.err
   done
 done
 python - "$out" "$A" "$B" "$R" <<'PY'

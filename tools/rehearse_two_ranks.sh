@@ -4,4 +4,4 @@
 # steps.  Not a measurement.   usage (through gpurun): bash tools/rehearse_two_ranks.sh
 cd ${GRAFT_REPO_ROOT:-.}
 SEGMIF_DIST_BACKEND=gloo timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 \
-  bench.py --gpus 2 --steps 2 --warmup 1 --batch 8 --train-batch 2 --train-steps 2 2>&1 | grep -v "amdgpu.ids\|^W0\|^\*\*\*" | tail -3
+  bench.py --full --gpus 2 --steps 2 --warmup 1 --batch 8 --train-batch 2 --train-steps 2 2>&1 | grep -v "amdgpu.ids\|^W0\|^\*\*\*" | tail -3
