@@ -18,9 +18,9 @@
 #include <stdint.h>
 
 #include "segmif_hip.h"
+#include "split_ops.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace segmif;
 
 namespace {
 

@@ -20,8 +20,8 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "igemm_common.h"
 #include "segmif_hip.h"
+#include "split_ops.h"
 
 namespace segmif {
 namespace {
@@ -32,13 +32,6 @@ constexpr int AB_TILE = ABT * ABP;  // floats per staged 32 x 64 tile
 
 __device__ __forceinline__ f32x16 mfma_f32(float a, float b, const f32x16& c) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int v = 0; v < 16; ++v) z[v] = 0.f;
-  return z;
 }
 
 // accumulator register v of lane (r, hh) holds row (v & 3) + 8 (v >> 2) + 4 hh of the 32 x 32 tile, column r

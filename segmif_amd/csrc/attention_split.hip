@@ -19,7 +19,7 @@
 // 16 s + 4 h + (j & 3) + 8 (j >> 2) again - so P feeds the second product without leaving its registers and the V
 // image is stored transposed in that key order.
 //
-// F16 = true ("f16x3", segmif_sr_attention_split16_f32; the format: csrc/conv3x3_planes.hip / planes16.h): THREE
+// F16 = true ("f16x3", segmif_sr_attention_split16_f32; the format: csrc/conv3x3_planes.hip / split_ops.h): THREE
 // v_mfma_f32_32x32x16_f16 per product instead of six.  K and V^T play the weights' role (three half planes W0 | W - W0 |
 // 2^-11 W0 of the values scaled by a power of two), Q and P the activations' (half pairs x = hi + 2^-11 lo, split in
 // registers).  The scale is per (key tile, head, image), found by the pack workgroup that writes the tile's image: the largest
@@ -32,23 +32,14 @@
 #include "device_once.h"
 #include <stdint.h>
 
-#include "planes16.h"
+#include "split_ops.h"
 #include "segmif_hip.h"
 
-namespace p16 = segmif::p16;
+using namespace segmif;
 
 #ifndef ATTN_ABL
 #define ATTN_ABL 0  // tuning aid (tools/attn_ablate.sh): 1 = no tile DMA after the first, 2 = no softmax arithmetic, 4 = no Q K^T MFMAs, 8 = no P V MFMAs, 16 = no per-tile barrier (with 1), 32 = no output stores
 #endif
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
@@ -70,82 +61,6 @@ struct Img {
   static_assert(O_TILE_SCALES + 8 <= BYTES, "tile scales must fit the image");
 };
 constexpr int IMG_MAX = Img<false>::BYTES;  // what segmif_sr_attention_split_workspace sizes a tile for (either format)
-constexpr int PX6[6] = {2, 1, 0, 1, 0, 0};  // six products, least significant first: plane of the first operand ...
-constexpr int PY6[6] = {0, 1, 2, 0, 1, 0};  // ... and of the second
-
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
-  f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
-
-__device__ __forceinline__ void split3(float x0, float x1, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
-  p0 = pk_bf16(x0, x1);
-  float r0 = x0 - __uint_as_float(p0 << 16), r1 = x1 - __uint_as_float(p0 & 0xffff0000u);
-  p1 = pk_bf16(r0, r1);
-  r0 -= __uint_as_float(p1 << 16);
-  r1 -= __uint_as_float(p1 & 0xffff0000u);
-  p2 = pk_bf16(r0, r1);
-}
-
-struct Op3 {
-  u32x4 p[3];
-};
-__device__ __forceinline__ Op3 split8(const f32x4 lo, const f32x4 hi) {
-  Op3 o;
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    uint32_t a, b, c;
-    split3(lo[2 * e], lo[2 * e + 1], a, b, c);
-    o.p[0][e] = a; o.p[1][e] = b; o.p[2][e] = c;
-    split3(hi[2 * e], hi[2 * e + 1], a, b, c);
-    o.p[0][2 + e] = a; o.p[1][2 + e] = b; o.p[2][2 + e] = c;
-  }
-  return o;
-}
-__device__ __forceinline__ bf16x8 op(const u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
-__device__ __forceinline__ f32x16 mma6(const u32x4* a, const u32x4* b, f32x16 acc) {
-#pragma unroll
-  for (int t = 0; t < 6; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(a[PX6[t]]), op(b[PY6[t]]), acc, 0, 0, 0);
-  return acc;
-}
-// f16x3: an activation operand is a half pair (hi, lo = 2^11 residual); products least significant first: lo W0s, hi Wl, hi W0
-struct Op2 {
-  u32x4 hi, lo;
-};
-__device__ __forceinline__ Op2 split8h(const f32x4 a, const f32x4 b) {
-  const float y[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  Op2 o;
-  p16::split8(y, o.hi, o.lo);
-  return o;
-}
-__device__ __forceinline__ f16x8 oph(const u32x4 v) { return __builtin_bit_cast(f16x8, v); }
-__device__ __forceinline__ u32x4 times_2m11(const u32x4 v) {  // 8 halves x 2^-11 (v_pk_mul_f16; exact up to the half's own rounding)
-  const f16x8 s = {(_Float16)0x1p-11f, (_Float16)0x1p-11f, (_Float16)0x1p-11f, (_Float16)0x1p-11f,
-                   (_Float16)0x1p-11f, (_Float16)0x1p-11f, (_Float16)0x1p-11f, (_Float16)0x1p-11f};
-  return __builtin_bit_cast(u32x4, oph(v) * s);
-}
-__device__ __forceinline__ f32x16 mma3(const u32x4* w, const Op2& x, f32x16 acc) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(oph(w[2]), oph(x.lo), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(oph(w[1]), oph(x.hi), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(oph(w[0]), oph(x.hi), acc, 0, 0, 0);
-  return acc;
-}
-// three half planes W0 | W - W0 | 2^-11 W0 of two adjacent scaled values -> one dword per plane
-__device__ __forceinline__ void split3h(float x0, float x1, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
-  typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-  const h2 w0 = {(_Float16)x0, (_Float16)x1};
-  const h2 wl = {(_Float16)(x0 - (float)w0[0]), (_Float16)(x1 - (float)w0[1])};
-  const h2 ws = {(_Float16)((float)w0[0] * (1.f / p16::LSCALE)), (_Float16)((float)w0[1] * (1.f / p16::LSCALE))};
-  p0 = __builtin_bit_cast(uint32_t, w0);
-  p1 = __builtin_bit_cast(uint32_t, wl);
-  p2 = __builtin_bit_cast(uint32_t, ws);
-}
-// power of two that brings mx into [2^14, 2^15) (1 for zero / non-finite input)
-__device__ __forceinline__ float pow2_scale(float mx) {
-  int e = 0;
-  if (mx >= 1e-30f && mx <= 3e38f) e = 14 - (int)((__float_as_uint(mx) >> 23) - 127);
-  return ldexpf(1.f, e);
-}
 
 __device__ __forceinline__ int slot_to_index(int pos) {  // position 16 s + 8 h + j -> 16 s + 4 h + (j & 3) + 8 (j >> 2)
   const int s = pos >> 4, hh = (pos >> 3) & 1, j = pos & 7;
@@ -155,16 +70,6 @@ __device__ __forceinline__ const unsigned char* uniform_ptr(const unsigned char*
   const uint64_t v = (uint64_t)(uintptr_t)p;
   const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
   return reinterpret_cast<const unsigned char*>((uintptr_t)(((uint64_t)hi << 32) | lo));
-}
-// (r6) the SADDR form of the same instruction: wave-uniform base in SGPRs + a 32-bit lane offset (csrc/conv3x3_planes.hip, dma16s: no
-// per-instruction address arithmetic, one VGPR read per lane instead of two, no write-after-read interlock on a shared address pair)
-__device__ __forceinline__ void dma16s(const unsigned char* sbase, uint32_t voff, unsigned char* lds_wave_base) {
-  const uint32_t m = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)lds_wave_base);
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(m) : "memory", "m0");
-}
-__device__ __forceinline__ void dma16(const unsigned char* src, unsigned char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
 // One workgroup per (key tile, head, batch): the tile's K rows and V^T rows, split, in LDS-image order.
@@ -208,8 +113,8 @@ __global__ __launch_bounds__(256) void sr_attention_pack_kernel(const float* __r
       red[1][tid >> 6] = mv;
     }
     __syncthreads();
-    sk = pow2_scale(fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3])));
-    sv = pow2_scale(fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3])));
+    sk = p16::pow2_scale(fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3])));
+    sv = p16::pow2_scale(fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3])));
     if (tid == 0) {
       reinterpret_cast<float*>(dst + I::O_TILE_SCALES)[0] = 1.f / sk;  // exact: powers of two
       reinterpret_cast<float*>(dst + I::O_TILE_SCALES)[1] = 1.f / sv;
@@ -220,8 +125,8 @@ __global__ __launch_bounds__(256) void sr_attention_pack_kernel(const float* __r
     const int u = tid + 256 * i;
     const int row = u >> 5, pp = 2 * (u & 31);
     uint32_t a, bb, c;
-    if constexpr (F16) split3h(kv2[i][0] * sk, kv2[i][1] * sk, a, bb, c);
-    else split3(kv2[i][0], kv2[i][1], a, bb, c);
+    if constexpr (F16) p16::split3h(kv2[i][0] * sk, kv2[i][1] * sk, a, bb, c);
+    else bf3::split3(kv2[i][0], kv2[i][1], a, bb, c);
     unsigned char* o = dst + row * I::KPITCH + pp * 2;
     *reinterpret_cast<uint32_t*>(o) = a;
     *reinterpret_cast<uint32_t*>(o + 128) = bb;
@@ -232,8 +137,8 @@ __global__ __launch_bounds__(256) void sr_attention_pack_kernel(const float* __r
     const int u = tid + 256 * i;
     const int d = u & 63, pp = 2 * (u >> 6);
     uint32_t a, bb, c;
-    if constexpr (F16) split3h(vv2[i][0] * sv, vv2[i][1] * sv, a, bb, c);
-    else split3(vv2[i][0], vv2[i][1], a, bb, c);
+    if constexpr (F16) p16::split3h(vv2[i][0] * sv, vv2[i][1] * sv, a, bb, c);
+    else bf3::split3(vv2[i][0], vv2[i][1], a, bb, c);
     unsigned char* o = dst + I::K_BYTES + d * I::VPITCH + pp * 2;
     *reinterpret_cast<uint32_t*>(o) = a;
     *reinterpret_cast<uint32_t*>(o + 64) = bb;
@@ -257,17 +162,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
   const bool q_ok = qi < N;
   const unsigned char* src = img + ((long long)b * heads + head) * ntiles * IMG;
 
-  // 26 (f16x3: 18) wave-sized (1 KB) DMA instructions per tile, dealt round-robin to the four waves
+  // 26 (f16x3: 18) wave-sized (1 KB) DMA instructions per tile, dealt round-robin to the four waves, in SADDR form (split_ops.h,
+  // dma16s).  M0 goes through readfirstlane with the cast written out: through lds_addr the compiler drops the readfirstlane and
+  // the kernel's code changes.
   auto stage = [&](int kt, int buf) {
     const unsigned char* s = src + (long long)kt * IMG;
     unsigned char* d = smem + buf * IMG;
-    for (int i = wave; i < IMG / 1024; i += 4) dma16s(uniform_ptr(s + i * 1024), (uint32_t)(lane * 16), d + i * 1024);
+    for (int i = wave; i < IMG / 1024; i += 4)
+      dma16s(uniform_ptr(s + i * 1024), (uint32_t)(lane * 16),
+             __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(d + i * 1024)));
   };
   stage(0, 0);
 
   // the query row, split: K-step s = head dimensions 16 s + {4h .. 4h+3, 8 + 4h .. 8 + 4h+3}
-  Op3 qp[F16 ? 1 : 4];
-  Op2 qh[F16 ? 4 : 1];
+  bf3::Op3 qp[F16 ? 1 : 4];
+  p16::Op2 qh[F16 ? 4 : 1];
   uint32_t amx = 0u;
   {
     const float* qrow = q + ((long long)b * N + (q_ok ? qi : 0)) * ldq + head * 64 + 4 * h;
@@ -281,10 +190,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
       // softmax_e(scale q.k) = softmax_2((scale log2(e) q).k): one multiply per query element here, a bare v_exp_f32 per
       // score in the key loop
       if constexpr (F16) {
-        qh[s] = split8h(lo * (scale * 1.44269504088896340736f), hi * (scale * 1.44269504088896340736f));
+        qh[s] = p16::split8h(lo * (scale * 1.44269504088896340736f), hi * (scale * 1.44269504088896340736f));
         amx = p16::absmax_pk4(amx, qh[s].hi, qh[s].lo);
       } else {
-        qp[s] = split8(lo * (scale * 1.44269504088896340736f), hi * (scale * 1.44269504088896340736f));
+        qp[s] = bf3::split8(lo * (scale * 1.44269504088896340736f), hi * (scale * 1.44269504088896340736f));
       }
     }
   }
@@ -319,10 +228,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
       u32x4 kf[3];
 #pragma unroll
       for (int k = 0; k < NPL; ++k) kf[k] = *reinterpret_cast<const u32x4*>(Kt + r * I::KPITCH + k * 128 + (16 * st + 8 * h) * 2);
-      if constexpr (F16) kf[2] = times_2m11(kf[0]);
+      if constexpr (F16) kf[2] = p16::times_2m11(kf[0]);
       if (ATTN_ABL & 4) asm volatile("" ::"v"(kf[0]), "v"(kf[1]), "v"(kf[2]));
-      else if constexpr (F16) s = mma3(kf, qh[st], s);
-      else s = mma6(kf, qp[st].p, s);
+      else if constexpr (F16) s = p16::mma3(kf, qh[st], s);
+      else s = bf3::mma6(kf, qp[st].p, s);
     }
     // ---- per-lane online softmax over this lane's 16 keys (+ partner half) -----------------
     if ((kt + 1) * KT > Nk) {  // last, partial tile: keys past the end get no weight
@@ -364,20 +273,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     for (int sp = 0; sp < 2; ++sp) {
       const f32x4 pa = {s[8 * sp], s[8 * sp + 1], s[8 * sp + 2], s[8 * sp + 3]};
       const f32x4 pb = {s[8 * sp + 4], s[8 * sp + 5], s[8 * sp + 6], s[8 * sp + 7]};
-      Op3 pk;
-      Op2 ph;
-      if constexpr (F16) ph = split8h(pa, pb);
-      else pk = split8(pa, pb);
+      bf3::Op3 pk;
+      p16::Op2 ph;
+      if constexpr (F16) ph = p16::split8h(pa, pb);
+      else pk = bf3::split8(pa, pb);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
         u32x4 vf[3];
 #pragma unroll
         for (int k = 0; k < NPL; ++k)
           vf[k] = *reinterpret_cast<const u32x4*>(Vt + (dt * 32 + r) * I::VPITCH + k * 64 + (16 * sp + 8 * h) * 2);
-        if constexpr (F16) vf[2] = times_2m11(vf[0]);
+        if constexpr (F16) vf[2] = p16::times_2m11(vf[0]);
         if (ATTN_ABL & 8) asm volatile("" ::"v"(vf[0]), "v"(vf[1]), "v"(vf[2]), "v"(ph.hi), "v"(ph.lo));
-        else if constexpr (F16) o[dt] = mma3(vf, ph, o[dt]);
-        else o[dt] = mma6(vf, pk.p, o[dt]);
+        else if constexpr (F16) o[dt] = p16::mma3(vf, ph, o[dt]);
+        else o[dt] = bf3::mma6(vf, pk.p, o[dt]);
       }
     }
     if (!(ATTN_ABL & 16)) {

@@ -19,6 +19,7 @@
 
 #include "igemm_common.h"
 #include "segmif_hip.h"
+#include "split_ops.h"
 
 namespace segmif {
 namespace {

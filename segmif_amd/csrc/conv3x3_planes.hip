@@ -46,7 +46,7 @@
 #include <stdlib.h>
 
 #include "igemm_common.h"
-#include "planes16.h"
+#include "split_ops.h"
 #include "segmif_hip.h"
 
 #ifndef PLANES_DBG
@@ -82,13 +82,6 @@ __device__ unsigned long long planes_epi_timeline[256][2][PLANES_TL_ITEMS][8];
 namespace segmif {
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
 constexpr int PB = 2;            // zero border of a planes image (pixels) = the largest dilation served
 constexpr int TH = 8, TW = 32;   // output patch of a workgroup
 constexpr int PXB = 96;          // bytes per pixel per chunk: 3 planes x 16 bf16 (also a weight row in both formats)
@@ -99,32 +92,6 @@ constexpr int W1_BYTES = 64 * PXB;       // one chunk of the fused 1x1 weights, 
 
 inline int planes_hp(int H) { return (H + TH - 1) / TH * TH + 2 * PB; }
 inline int planes_wp(int W) { return (W + TW - 1) / TW * TW + 2 * PB; }
-
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {  // v_cvt_pk_bf16_f32: a -> low half
-  f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
-
-__device__ __forceinline__ void split3(float x0, float x1, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
-  p0 = pk_bf16(x0, x1);
-  float r0 = x0 - __uint_as_float(p0 << 16), r1 = x1 - __uint_as_float(p0 & 0xffff0000u);
-  p1 = pk_bf16(r0, r1);
-  r0 -= __uint_as_float(p1 << 16);
-  r1 -= __uint_as_float(p1 & 0xffff0000u);
-  p2 = pk_bf16(r0, r1);
-}
-
-// 8 fp32 values (positions 8h .. 8h+7 of a chunk) -> one 16-byte piece per plane
-__device__ __forceinline__ void split8(const float* y, u32x4& p0, u32x4& p1, u32x4& p2) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    uint32_t a, b, c;
-    split3(y[2 * e], y[2 * e + 1], a, b, c);
-    p0[e] = a;
-    p1[e] = b;
-    p2[e] = c;
-  }
-}
 
 template <bool F16>
 __device__ __forceinline__ f32x16 mfma_split(const u32x4& a, const u32x4& b, const f32x16& c) {
@@ -169,22 +136,9 @@ struct PlanesConvK {
   int amax_images;            // 1: every image reports to amax[0]
 };
 
-__device__ __forceinline__ void dma16(const unsigned char* src, unsigned char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 #ifndef PLANES_SADDR
-#define PLANES_SADDR 1  // (r6) LDS-DMA with a scalar base + a 32-bit lane offset (no address arithmetic per instruction)
+#define PLANES_SADDR 1  // (r6) LDS-DMA with a scalar base + a 32-bit lane offset (no address arithmetic per instruction; split_ops.h, dma16s)
 #endif
-// (r6) The same instruction in its SADDR form: a wave-uniform 64-bit base in SGPRs + a 32-bit per-lane offset.  From the builtin
-// hipcc makes, per DMA instruction, a v_lshl_add_u64 into ONE shared 64-bit address register pair and the load from it - the next
-// instruction's address write has to wait until the load in front has read that pair (a write-after-read interlock on a
-// vector-memory operand: tens to hundreds of cycles beside the other team's MFMA stream), and every address costs two VGPR reads.
-// Here the offsets sit in their own registers for the kernel's life and a DMA instruction is an s_mov of M0 and the load.
-__device__ __forceinline__ void dma16s(const unsigned char* sbase, uint32_t voff, unsigned char* lds_wave_base) {
-  const uint32_t m = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)lds_wave_base;
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(m) : "memory", "m0");
-}
 
 // One persistent workgroup per CU, 8 waves = two TEAMS of four (one wave per SIMD each).  A team owns one 8 x 32
 // patch at a time and alternates between two roles, the teams in anti-phase, one workgroup barrier per phase:
@@ -285,7 +239,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       for (int j = 0; j < AJ; ++j) {
         const int i = j * 4 + wave;
         if (j < AJ - 1 || i * 64 + lane < A_UNITS) {
-          if constexpr (PLANES_SADDR && F16) dma16s(ab, a_rel[j], As + i * 1024);
+          if constexpr (PLANES_SADDR && F16) dma16s(ab, a_rel[j], lds_addr(As + i * 1024));
           else dma16(ab + a_rel[j], As + i * 1024);
         }
       }
@@ -302,7 +256,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int j = 0; j < (W_SPLIT + 3) / 4; ++j) {
       const int i = lo + j * 4 + wave;
       if (i < hi) {
-        if constexpr (PLANES_SADDR && F16) dma16s(p.wt + (long long)c * W3_BYTES + i * 1024, (uint32_t)(lane * 16), wd + i * 1024);
+        if constexpr (PLANES_SADDR && F16) dma16s(p.wt + (long long)c * W3_BYTES + i * 1024, (uint32_t)(lane * 16), lds_addr(wd + i * 1024));
         else dma16(wb + i * 1024, wd + i * 1024);
       }
     }
@@ -313,7 +267,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       for (int j = 0; j < 2; ++j) {
         const int i = j * 4 + wave;
         if (i < W1_INSTR) {
-          if constexpr (PLANES_SADDR && F16) dma16s(p.w1 + (long long)c * W1_BYTES + i * 1024, (uint32_t)(lane * 16), w1d + i * 1024);
+          if constexpr (PLANES_SADDR && F16) dma16s(p.w1 + (long long)c * W1_BYTES + i * 1024, (uint32_t)(lane * 16), lds_addr(w1d + i * 1024));
           else dma16(w1b + i * 1024, w1d + i * 1024);
         }
       }
@@ -617,7 +571,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           const uint32_t mx = p16::absmax_pk4(amx, pl[0], pl[1]);
           amx = ok ? mx : amx;
         } else {
-          split8(y + 8 * q, pl[0], pl[1], pl[2]);
+          bf3::split8(y + 8 * q, pl[0], pl[1], pl[2]);
         }
         if (PLANES_DBG & 64) asm volatile("" ::"v"(pl[0]), "v"(pl[1]), "v"(pl[2]));
         if (!(LEAN && FUSE) && p.pout && ok && !(PLANES_DBG & 64)) {
@@ -922,7 +876,7 @@ __global__ void planes_from_f32_kernel(const float* __restrict__ x, int ldx, uns
     }
   } else {
     u32x4 p0, p1, p2;
-    split8(y, p0, p1, p2);
+    bf3::split8(y, p0, p1, p2);
     *reinterpret_cast<u32x4*>(dst) = p0;
     *reinterpret_cast<u32x4*>(dst + 32) = p1;
     *reinterpret_cast<u32x4*>(dst + 64) = p2;
@@ -1029,7 +983,7 @@ __global__ void planes_pack_weight_kernel(const float* __restrict__ w, int N, in
   const int chunk = (int)(t / taps);
   const float x = w[(long long)n * ldw + tap * Cin + chunk * 16 + sigma16(j)];
   uint32_t p0, p1, p2;
-  split3(x, 0.f, p0, p1, p2);
+  bf3::split3(x, 0.f, p0, p1, p2);
   const int f = (n >> 4) & 1;
   const long long row = ((long long)chunk * taps + tap) * N + n;
   uint16_t* dst = out + row * 48 + (((j >> 3) ^ f) * 8) + (j & 7);

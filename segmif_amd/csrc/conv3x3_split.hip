@@ -40,7 +40,7 @@
 // instead of 64-byte halo reads.  Next (round 2): a persistent, LDS-double-buffered schedule.
 //
 // f16x3 form (round 4, the training path's default; F16 = true below).  Same kernel, half pairs instead of bf16 triples:
-// x = hi + 2^-11 lo (planes16.h), weights as W0 | Wl | 2^-11 W0 of the row scaled by a power of two (conv3x3_planes.hip's
+// x = hi + 2^-11 lo (split_ops.h), weights as W0 | Wl | 2^-11 W0 of the row scaled by a power of two (conv3x3_planes.hip's
 // format), THREE products (lo W0s, hi Wl, hi W0) instead of six - the matrix pipe was 56 % of a call.  A half has 5 exponent
 // bits, and this kernel also multiplies GRADIENTS (1e-7 and below), so the range is not guarded but MADE: the caller passes
 // the device slots holding max |x| of the input's channel blocks (their producers' epilogues, or segmif_amax_f32), the kernel
@@ -54,7 +54,7 @@
 #include <stdint.h>
 
 #include "igemm_common.h"
-#include "planes16.h"
+#include "split_ops.h"
 #include "segmif_hip.h"
 
 #ifndef SPLIT_INTERLEAVE
@@ -80,31 +80,9 @@ __device__ unsigned long long split_timeline[SPLIT_TL_BLOCKS][SPLIT_TL_CHUNKS + 
 namespace segmif {
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int STW = 32;
 constexpr int ROWB = 112;    // LDS bytes per weight row (3 planes) and per bf16x3 pixel
 constexpr int ROWB_H = 80;   // per f16x3 pixel: 2 planes x 32 B + 16 B pad (conflict-free ds_read_b128 over 16 pixels: 20-dword stride)
-
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {  // v_cvt_pk_bf16_f32: a -> low half
-  f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
-
-__device__ __forceinline__ void split3(float x0, float x1, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
-  p0 = pk_bf16(x0, x1);
-  float r0 = x0 - __uint_as_float(p0 << 16), r1 = x1 - __uint_as_float(p0 & 0xffff0000u);
-  p1 = pk_bf16(r0, r1);
-  r0 -= __uint_as_float(p1 << 16);
-  r1 -= __uint_as_float(p1 & 0xffff0000u);
-  p2 = pk_bf16(r0, r1);
-}
 
 inline int split_nout(int N) { return N <= 32 ? 32 : 64; }
 
@@ -190,8 +168,8 @@ __global__ __launch_bounds__(STH * 32) __attribute__((amdgpu_waves_per_eu(2, 2))
       pa[j][1] = u32x2{la, lb};
     } else {
       uint32_t p0a, p1a, p2a, p0b, p1b, p2b;
-      split3(x[0], x[1], p0a, p1a, p2a);
-      split3(x[2], x[3], p0b, p1b, p2b);
+      bf3::split3(x[0], x[1], p0a, p1a, p2a);
+      bf3::split3(x[2], x[3], p0b, p1b, p2b);
       pa[j][0] = u32x2{p0a, p0b};
       pa[j][1] = u32x2{p1a, p1b};
       pa[j][NPA - 1] = u32x2{p2a, p2b};
@@ -441,7 +419,7 @@ __global__ void split_pack_kernel(const float* __restrict__ w, int N, int Cin, i
   const int gn = nt * NOUT + n;
   const float x = gn < N ? w[(long long)gn * ldw + tap * Cin + chunk * 16 + c16] : 0.f;
   uint32_t p0, p1, p2;
-  split3(x, 0.f, p0, p1, p2);
+  bf3::split3(x, 0.f, p0, p1, p2);
   const long long row = (((long long)nt * nchunks + chunk) * 9 + tap) * NOUT + n;
   out[row * 48 + c16] = (uint16_t)(p0 & 0xffffu);
   out[row * 48 + 16 + c16] = (uint16_t)(p1 & 0xffffu);

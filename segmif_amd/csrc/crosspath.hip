@@ -29,17 +29,10 @@
 #include "device_once.h"
 #include <stdint.h>
 
-#include "planes16.h"
+#include "split_ops.h"
 #include "segmif_hip.h"
 
-namespace p16 = segmif::p16;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+using namespace segmif;
 
 namespace {
 
@@ -53,58 +46,6 @@ constexpr int WPB2 = 3 * 256 + 16;   // 128 columns
 constexpr int CP_WAVES = 8;
 constexpr int GRAM_WGS = 64;  // workgroups per image at least (x 8 waves x 32-pixel tiles): independent of the batch, so results do not depend on it; 8 left a single image on 8 CUs
 constexpr int GRAM_RUN_TILES = 32;  // a wave accumulates at most this many tiles (1024 pixels) in fp32 before the fp64 combine
-constexpr int PX6[6] = {2, 1, 0, 1, 0, 0};  // six products, least significant first: plane of the first operand ...
-constexpr int PY6[6] = {0, 1, 2, 0, 1, 0};  // ... and of the second
-
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int v = 0; v < 16; ++v) z[v] = 0.f;
-  return z;
-}
-
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
-  f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
-
-__device__ __forceinline__ void split3(float x0, float x1, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
-  p0 = pk_bf16(x0, x1);
-  float r0 = x0 - __uint_as_float(p0 << 16), r1 = x1 - __uint_as_float(p0 & 0xffff0000u);
-  p1 = pk_bf16(r0, r1);
-  r0 -= __uint_as_float(p1 << 16);
-  r1 -= __uint_as_float(p1 & 0xffff0000u);
-  p2 = pk_bf16(r0, r1);
-}
-
-// 8 consecutive K-slots of a lane -> one MFMA operand per plane
-struct Op3 {
-  u32x4 p[3];
-};
-__device__ __forceinline__ Op3 split8(const f32x4 lo, const f32x4 hi) {
-  Op3 o;
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    uint32_t a, b, c;
-    split3(lo[2 * e], lo[2 * e + 1], a, b, c);
-    o.p[0][e] = a; o.p[1][e] = b; o.p[2][e] = c;
-    split3(hi[2 * e], hi[2 * e + 1], a, b, c);
-    o.p[0][2 + e] = a; o.p[1][2 + e] = b; o.p[2][2 + e] = c;
-  }
-  return o;
-}
-__device__ __forceinline__ Op3 split8(const f32x16 t, int s) {  // accumulator registers 8s .. 8s+7
-  return split8(f32x4{t[8 * s], t[8 * s + 1], t[8 * s + 2], t[8 * s + 3]},
-                f32x4{t[8 * s + 4], t[8 * s + 5], t[8 * s + 6], t[8 * s + 7]});
-}
-__device__ __forceinline__ bf16x8 op(const u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
-
-// six-product fp32-class accumulate: acc += A B with A's planes `a` (first MFMA operand: rows) and B's planes `b`
-__device__ __forceinline__ f32x16 mma6(const u32x4* a, const u32x4* b, f32x16 acc) {
-#pragma unroll
-  for (int t = 0; t < 6; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(a[PX6[t]]), op(b[PY6[t]]), acc, 0, 0, 0);
-  return acc;
-}
 
 // 64 rows x 64 columns [col0, col0 + 64) of a row-major fp32 matrix -> split LDS image at positions [pos0, pos0 + 64)
 __device__ __forceinline__ void stage_split64(const float* __restrict__ w, int ldw, int col0, unsigned char* dst, int pitch,
@@ -115,7 +56,7 @@ __device__ __forceinline__ void stage_split64(const float* __restrict__ w, int l
     const int col = 16 * s + 4 * hh + (j & 3) + 8 * (j >> 2);
     const f32x2 v = *reinterpret_cast<const f32x2*>(w + (long long)row * ldw + col0 + col);
     uint32_t a, b, c;
-    split3(v[0], v[1], a, b, c);
+    bf3::split3(v[0], v[1], a, b, c);
     unsigned char* d = dst + row * pitch + (pos0 + pp) * 2;
     *reinterpret_cast<uint32_t*>(d) = a;
     *reinterpret_cast<uint32_t*>(d + plane_bytes) = b;
@@ -130,44 +71,9 @@ __device__ __forceinline__ void wfrag(const unsigned char* base, int row, int pi
   for (int k = 0; k < 3; ++k) out[k] = *reinterpret_cast<const u32x4*>(a + k * plane_bytes);
 }
 
-// ---- (r6) f16x3 arithmetic for the tail (planes16.h): weights as three half planes W0 | W - W0 | 2^-11 W0 of the row scaled by a
-// power of two, activations as half pairs split in registers; three products per MAC, least significant first: lo W0s, hi Wl, hi W0
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-struct Op2 {
-  u32x4 hi, lo;
-};
-__device__ __forceinline__ Op2 split8h(const f32x4 a, const f32x4 b) {
-  const float y[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  Op2 o;
-  p16::split8(y, o.hi, o.lo);
-  return o;
-}
-__device__ __forceinline__ Op2 split8h(const f32x16 t, int s) {  // accumulator registers 8s .. 8s+7
-  return split8h(f32x4{t[8 * s], t[8 * s + 1], t[8 * s + 2], t[8 * s + 3]},
-                 f32x4{t[8 * s + 4], t[8 * s + 5], t[8 * s + 6], t[8 * s + 7]});
-}
-__device__ __forceinline__ f16x8 oph(const u32x4 v) { return __builtin_bit_cast(f16x8, v); }
-// acc += W X with the weight planes `w` as the MFMA's first operand (rows) and the half pair `x` as its second
-__device__ __forceinline__ f32x16 mma3(const u32x4* w, const Op2& x, f32x16 acc) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(oph(w[2]), oph(x.lo), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(oph(w[1]), oph(x.hi), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(oph(w[0]), oph(x.hi), acc, 0, 0, 0);
-  return acc;
-}
-__device__ __forceinline__ void split3h(float x0, float x1, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
-  typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-  const h2 w0 = {(_Float16)x0, (_Float16)x1};
-  const h2 wl = {(_Float16)(x0 - (float)w0[0]), (_Float16)(x1 - (float)w0[1])};
-  const h2 ws = {(_Float16)((float)w0[0] * (1.f / p16::LSCALE)), (_Float16)((float)w0[1] * (1.f / p16::LSCALE))};
-  p0 = __builtin_bit_cast(uint32_t, w0);
-  p1 = __builtin_bit_cast(uint32_t, wl);
-  p2 = __builtin_bit_cast(uint32_t, ws);
-}
-__device__ __forceinline__ float pow2_scale(float mx) {  // brings mx into [2^14, 2^15); 1 for zero / non-finite
-  int e = 0;
-  if (mx >= 1e-30f && mx <= 3e38f) e = 14 - (int)((__float_as_uint(mx) >> 23) - 127);
-  return ldexpf(1.f, e);
-}
+// ---- (r6) f16x3 arithmetic for the tail (split_ops.h, p16): weights as three half planes W0 | W - W0 | 2^-11 W0 of the row scaled
+// by a power of two, activations as half pairs split in registers; three products per MAC, least significant first: lo W0s, hi Wl,
+// hi W0.
 // f16x3 LDS image of 64 rows x NCOL columns (64 | 128) of a row-major fp32 matrix, same positions as stage_split64; the row
 // scale 2^-e(n) goes to inv[n].  One row per LPR lanes (a half-wave for 64 columns, a wave for 128): its maximum is a
 // shuffle reduction.  Must be called by all `nthreads` threads (a multiple of 64).
@@ -183,9 +89,9 @@ __device__ __forceinline__ void stage_split_h(const float* __restrict__ w, int l
     float mx = fmaxf(fabsf(v[0]), fabsf(v[1]));
 #pragma unroll
     for (int o = LPR / 2; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    const float sc = pow2_scale(mx);
+    const float sc = p16::pow2_scale(mx);
     uint32_t a, b, c;
-    split3h(v[0] * sc, v[1] * sc, a, b, c);
+    p16::split3h(v[0] * sc, v[1] * sc, a, b, c);
     unsigned char* d = dst + row * pitch + pp * 2;
     *reinterpret_cast<uint32_t*>(d) = a;
     *reinterpret_cast<uint32_t*>(d + NCOL * 2) = b;
@@ -262,12 +168,12 @@ __global__ __launch_bounds__(512) void crosspath_gram_kernel(const float* __rest
     f32x16 y[2] = {zero16(), zero16()};
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      const Op3 xs = split8(cur[2 * s], cur[2 * s + 1]);
+      const bf3::Op3 xs = bf3::split8(cur[2 * s], cur[2 * s + 1]);
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt) {
         u32x4 wf[3];
         wfrag(Ws + zo, nt * 32 + r, WPB, 128, s, h, wf);
-        y[nt] = mma6(xs.p, wf, y[nt]);
+        y[nt] = bf3::mma6(xs.p, wf, y[nt]);
       }
     }
 #pragma unroll
@@ -286,10 +192,10 @@ __global__ __launch_bounds__(512) void crosspath_gram_kernel(const float* __rest
     // stage 2: G[i][j] += sum_px Y[px][i] Y[px][j]: registers 8s .. 8s+7 of stage 1 are the 8 K-slots (pixels) of step s
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      const Op3 y0 = split8(y[0], s), y1 = split8(y[1], s);
-      g[0] = mma6(y0.p, y0.p, g[0]);
-      g[1] = mma6(y0.p, y1.p, g[1]);
-      g[2] = mma6(y1.p, y1.p, g[2]);
+      const bf3::Op3 y0 = bf3::split8(y[0], s), y1 = bf3::split8(y[1], s);
+      g[0] = bf3::mma6(y0.p, y0.p, g[0]);
+      g[1] = bf3::mma6(y0.p, y1.p, g[1]);
+      g[2] = bf3::mma6(y1.p, y1.p, g[2]);
     }
   };
   f32x4 xa[8], xb2[8], xc[8];
@@ -388,10 +294,10 @@ __global__ __launch_bounds__(512, 4) void crosspath_gram_lazy_kernel(const float
         y[nt][gq][j & 3] = pv ? v : 0.f;
       }
     }
-    const Op3 y0 = split8(y[0][0], y[0][1]), y1 = split8(y[1][0], y[1][1]);
-    g[0] = mma6(y0.p, y0.p, g[0]);
-    g[1] = mma6(y0.p, y1.p, g[1]);
-    g[2] = mma6(y1.p, y1.p, g[2]);
+    const bf3::Op3 y0 = bf3::split8(y[0][0], y[0][1]), y1 = bf3::split8(y[1][0], y[1][1]);
+    g[0] = bf3::mma6(y0.p, y0.p, g[0]);
+    g[1] = bf3::mma6(y0.p, y1.p, g[1]);
+    g[2] = bf3::mma6(y1.p, y1.p, g[2]);
   };
   float bufA[24], bufB[24];
   long long t = (long long)blockIdx.x * CP_WAVES + wave;
@@ -557,7 +463,7 @@ struct TailK {
   const float* bend; const float* gamma; const float* beta;
   float* out;
   unsigned char* planes;              // optional split-bf16 copy of out (conv3x3_planes.hip format) or null
-  int pl_f16;                         // the copy is an f16x3 one (half pairs, 64 bytes per pixel; planes16.h)
+  int pl_f16;                         // the copy is an f16x3 one (half pairs, 64 bytes per pixel; split_ops.h)
   uint32_t* pl_amax;                  // f16x3: range slot(s) for max |out| or null
   int pl_amax_images;                 // > 1: slot index = image (blockIdx.y)
   long long N;
@@ -727,7 +633,7 @@ __global__ __launch_bounds__(512) void crosspath_tail_kernel(const TailK p) {
       const long long cstride = (long long)p.Hp * p.Wp * 96;
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        const Op3 pl = split8(f32x4{o[8 * c], o[8 * c + 1], o[8 * c + 2], o[8 * c + 3]},
+        const bf3::Op3 pl = bf3::split8(f32x4{o[8 * c], o[8 * c + 1], o[8 * c + 2], o[8 * c + 3]},
                               f32x4{o[8 * c + 4], o[8 * c + 5], o[8 * c + 6], o[8 * c + 7]});
         *reinterpret_cast<u32x4*>(dst + c * cstride) = pl.p[0];
         *reinterpret_cast<u32x4*>(dst + c * cstride + 32) = pl.p[1];
@@ -760,12 +666,12 @@ __global__ __launch_bounds__(512) void crosspath_tail_kernel(const TailK p) {
       tt[1] = rows16(Cst + zo + src * 64 + 32);
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        const Op3 xs = split8(xc[2 * s], xc[2 * s + 1]);
+        const bf3::Op3 xs = bf3::split8(xc[2 * s], xc[2 * s + 1]);
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
           u32x4 wf[3];
           wfrag(Wsrc, nt * 32 + r, WPB, 128, s, h, wf);
-          tt[nt] = mma6(wf, xs.p, tt[nt]);
+          tt[nt] = bf3::mma6(wf, xs.p, tt[nt]);
         }
       }
       if (src == 0) load(t + stride, x3b, p.ld3, c3);  // (its rows have been split: the registers take the next tile's)
@@ -779,13 +685,13 @@ __global__ __launch_bounds__(512) void crosspath_tail_kernel(const TailK p) {
       for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
         for (int sp = 0; sp < 2; ++sp) {
-          const Op3 tk = split8(tt[nt], sp);
+          const bf3::Op3 tk = bf3::split8(tt[nt], sp);
           const int ks = src * 4 + nt * 2 + sp;
 #pragma unroll
           for (int mt = 0; mt < 2; ++mt) {
             u32x4 wf[3];
             wfrag(Wes + zo, mt * 32 + r, WPB2, 256, ks, h, wf);
-            z[mt] = mma6(wf, tk.p, z[mt]);
+            z[mt] = bf3::mma6(wf, tk.p, z[mt]);
           }
         }
     }
@@ -844,20 +750,20 @@ __global__ __launch_bounds__(512) void crosspath_tail_kernel(const TailK p) {
         pc[j][e + 1] = fmaxf(v[1], 0.f);
       }
     if constexpr (A16) {
-      const Op2 th = split8h(pc[0], pc[1]);
+      const p16::Op2 th = p16::split8h(pc[0], pc[1]);
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt) {
         u32x4 wf[3];
         wfrag(Wes + zo, mt * 32 + r, WPB2, 256, ks, h, wf);
-        z[mt] = mma3(wf, th, z[mt]);
+        z[mt] = p16::mma3(wf, th, z[mt]);
       }
     } else {
-      const Op3 tk = split8(pc[0], pc[1]);
+      const bf3::Op3 tk = bf3::split8(pc[0], pc[1]);
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt) {
         u32x4 wf[3];
         wfrag(Wes + zo, mt * 32 + r, WPB2, 256, ks, h, wf);
-        z[mt] = mma6(wf, tk.p, z[mt]);
+        z[mt] = bf3::mma6(wf, tk.p, z[mt]);
       }
     }
   };
@@ -898,12 +804,12 @@ __global__ __launch_bounds__(512) void crosspath_tail_kernel(const TailK p) {
       tt[1] = rows16(Cst + zo + 96);
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        const Op2 xh = split8h(ci[2 * s], ci[2 * s + 1]);
+        const p16::Op2 xh = p16::split8h(ci[2 * s], ci[2 * s + 1]);
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
           u32x4 wf[3];
           wfrag(Wis + zo, nt * 32 + r, WPB, 128, s, h, wf);
-          tt[nt] = mma3(wf, xh, tt[nt]);
+          tt[nt] = p16::mma3(wf, xh, tt[nt]);
         }
       }
 #pragma unroll
@@ -919,12 +825,12 @@ __global__ __launch_bounds__(512) void crosspath_tail_kernel(const TailK p) {
       tt[1] = rows16(Cst + zo + 96);
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        const Op3 xs = split8(ci[2 * s], ci[2 * s + 1]);
+        const bf3::Op3 xs = bf3::split8(ci[2 * s], ci[2 * s + 1]);
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
           u32x4 wf[3];
           wfrag(Wis + zo, nt * 32 + r, WPB, 128, s, h, wf);
-          tt[nt] = mma6(wf, xs.p, tt[nt]);
+          tt[nt] = bf3::mma6(wf, xs.p, tt[nt]);
         }
       }
 #pragma unroll
@@ -943,20 +849,20 @@ __global__ __launch_bounds__(512) void crosspath_tail_kernel(const TailK p) {
       for (int sp = 0; sp < 2; ++sp) {
         const int ks = 4 + nt * 2 + sp;
         if constexpr (A16) {
-          const Op2 th = split8h(tt[nt], sp);
+          const p16::Op2 th = p16::split8h(tt[nt], sp);
 #pragma unroll
           for (int mt = 0; mt < 2; ++mt) {
             u32x4 wf[3];
             wfrag(Wes + zo, mt * 32 + r, WPB2, 256, ks, h, wf);
-            z[mt] = mma3(wf, th, z[mt]);
+            z[mt] = p16::mma3(wf, th, z[mt]);
           }
         } else {
-          const Op3 tk = split8(tt[nt], sp);
+          const bf3::Op3 tk = bf3::split8(tt[nt], sp);
 #pragma unroll
           for (int mt = 0; mt < 2; ++mt) {
             u32x4 wf[3];
             wfrag(Wes + zo, mt * 32 + r, WPB2, 256, ks, h, wf);
-            z[mt] = mma6(wf, tk.p, z[mt]);
+            z[mt] = bf3::mma6(wf, tk.p, z[mt]);
           }
         }
       }

@@ -9,7 +9,7 @@
 // writes half pairs once - same byte count as fp32 - and the GEMM does no vector arithmetic on its operands at all:
 //
 //   PAIRS format: a row of K values = K / 16 groups of 64 bytes, [16 hi halves | 16 lo halves], x = hi + 2^-11 lo
-//                 (planes16.h; range-guarded by the producer like every f16x3 tensor).
+//                 (split_ops.h; range-guarded by the producer like every f16x3 tensor).
 //
 //   * tile 256 x 128 (8 waves of 64 x 64; WM = 2: 128 x 128, 4 waves, for problems too short to fill the chip), K step 16,
 //     a ring of S = 3 stages of 24 KB (A 16 KB + W 8 KB): 72 KB per workgroup, TWO workgroups per CU - one's epilogue and
@@ -36,15 +36,11 @@
 
 #include "device_once.h"
 #include "igemm_common.h"
-#include "planes16.h"
+#include "split_ops.h"
 #include "segmif_hip.h"
 
 namespace segmif {
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 #ifndef PAIRS_DBG
 #define PAIRS_DBG 0  // tuning aid: 1 = s_memtime timeline probe (tools/pairs_timeline.py)
@@ -80,26 +76,9 @@ struct GemmPairsK {
   // patch mode (patch_k > 0): A row (b, oy, ox) is the k x k patch at (st oy - pad, st ox - pad) of a dense NHWC pairs image
   // (B, H, W, C), C % 16 == 0, pixel pitch 4 C bytes; K = k k C in (ky, kx, c) order; a K step lies inside one tap
   int patch_k, patch_st, patch_pad, patch_H, patch_W, patch_OH, patch_OW, patch_C;
-  int saddr;                  // (r6) plain rows whose byte offsets from `a` fit 32 bits: LDS-DMA in SADDR form (below)
+  int saddr;                  // (r6) plain rows whose byte offsets from `a` fit 32 bits: LDS-DMA in SADDR form (split_ops.h, dma16s;
+                              // the lane offsets are constants of the kernel and the base moves by SALU)
 };
-
-// (r6) global_load_lds_dwordx4 in its SADDR form - a wave-uniform 64-bit base in SGPRs + a 32-bit per-lane offset (see
-// csrc/conv3x3_planes.hip, dma16s: per-lane 64-bit address pairs cost two VGPR reads per instruction and, advanced by vector adds, a
-// write-after-read interlock on a vector-memory operand; here the lane offsets are constants of the kernel and the base moves by SALU)
-__device__ __forceinline__ void dma16s(const unsigned char* sbase, uint32_t voff, unsigned char* lds_wave_base) {
-  const uint32_t m = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)lds_wave_base;
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(m) : "memory", "m0");
-}
-
-__device__ __forceinline__ u32x4 times_2m11(const u32x4 v) {  // 8 halves x 2^-11 (v_pk_mul_f16; exact up to the half's own rounding)
-  const f16x8 s = {(_Float16)0x1p-11f, (_Float16)0x1p-11f, (_Float16)0x1p-11f, (_Float16)0x1p-11f,
-                   (_Float16)0x1p-11f, (_Float16)0x1p-11f, (_Float16)0x1p-11f, (_Float16)0x1p-11f};
-  return __builtin_bit_cast(u32x4, __builtin_bit_cast(f16x8, v) * s);
-}
-
-__device__ __forceinline__ f32x16 mfma16(const u32x4& a, const u32x4& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
 
 // The step barrier.  __syncthreads() is a workgroup-scope fence + s_barrier, and hipcc lowers the fence to s_waitcnt vmcnt(0)
 // lgkmcnt(0): every LDS-DMA in flight - the stages issued AHEAD - would have to land before each barrier, which is the round trip
@@ -176,8 +155,7 @@ __global__ __launch_bounds__(WM * 128) __attribute__((amdgpu_waves_per_eu(WM == 
       for (int q = 0; q < APW; ++q) {
         const bool ok = (unsigned)(a_iy[q] + t_ky) < (unsigned)p.patch_H && (unsigned)(a_ix[q] + t_kx) < (unsigned)p.patch_W;
         const unsigned char* src = ok ? a_src[q] + off : zsrc;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                         (__attribute__((address_space(3))) void*)(base + (wave * APW + q) * 1024), 16, 0, 0);
+        dma16(src, base + (wave * APW + q) * 1024);
       }
       t_c0 += PBK;
       if (t_c0 == p.patch_C) {
@@ -189,22 +167,20 @@ __global__ __launch_bounds__(WM * 128) __attribute__((amdgpu_waves_per_eu(WM == 
       }
     } else if (sa) {
 #pragma unroll
-      for (int q = 0; q < APW; ++q) dma16s(p.a + (long long)ks * PROW, a_off[q], base + (wave * APW + q) * 1024);
+      for (int q = 0; q < APW; ++q) dma16s(p.a + (long long)ks * PROW, a_off[q], lds_addr(base + (wave * APW + q) * 1024));
     } else {
 #pragma unroll
       for (int q = 0; q < APW; ++q)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a_src[q] + (long long)ks * PROW),
-                                         (__attribute__((address_space(3))) void*)(base + (wave * APW + q) * 1024), 16, 0, 0);
+        dma16(a_src[q] + (long long)ks * PROW, base + (wave * APW + q) * 1024);
     }
     if (sa) {
       const unsigned char* wb = p.w + (long long)nt * nks * PWSTEP + (wave * WPW) * 1024 + (long long)ks * PWSTEP;  // (uniform)
 #pragma unroll
-      for (int q = 0; q < WPW; ++q) dma16s(wb + q * 1024, (uint32_t)(lane * 16), base + MT * PROW + (wave * WPW + q) * 1024);
+      for (int q = 0; q < WPW; ++q) dma16s(wb + q * 1024, (uint32_t)(lane * 16), lds_addr(base + MT * PROW + (wave * WPW + q) * 1024));
     } else {
 #pragma unroll
       for (int q = 0; q < WPW; ++q)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(w_src + (long long)ks * PWSTEP + q * 1024),
-                                         (__attribute__((address_space(3))) void*)(base + MT * PROW + (wave * WPW + q) * 1024), 16, 0, 0);
+        dma16(w_src + (long long)ks * PWSTEP + q * 1024, base + MT * PROW + (wave * WPW + q) * 1024);
     }
   };
 
@@ -249,7 +225,7 @@ __global__ __launch_bounds__(WM * 128) __attribute__((amdgpu_waves_per_eu(WM == 
         wl[i] = *reinterpret_cast<const u32x4*>(sb + w_lane + i * 32 * PROW + off_lo);
       }
 #pragma unroll
-      for (int j = 0; j < 2; ++j) ws[j] = times_2m11(w0[j]);
+      for (int j = 0; j < 2; ++j) ws[j] = p16::times_2m11(w0[j]);
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -422,8 +398,8 @@ __global__ __launch_bounds__(256) void pairs_to_f32_kernel(const unsigned char* 
   if (row >= rows) return;
   const unsigned char* src = x + row * ldx + (c >> 4) * 64 + (c & 15) * 2;
   const uint32_t* s32 = reinterpret_cast<const uint32_t*>(src);
-  const p16::h2 a0 = __builtin_bit_cast(p16::h2, s32[0]), a1 = __builtin_bit_cast(p16::h2, s32[1]);
-  const p16::h2 b0 = __builtin_bit_cast(p16::h2, s32[8]), b1 = __builtin_bit_cast(p16::h2, s32[9]);
+  const f16x2 a0 = __builtin_bit_cast(f16x2, s32[0]), a1 = __builtin_bit_cast(f16x2, s32[1]);
+  const f16x2 b0 = __builtin_bit_cast(f16x2, s32[8]), b1 = __builtin_bit_cast(f16x2, s32[9]);
   constexpr float inv = 1.f / p16::LSCALE;
   // (written out: the two-iteration loop over hi[e] / lo[e] this replaces was compiled to ONE dword load per plane and left
   // values 2, 3 of every quad undefined - found by the round trip of tools/pairs_debug.py)

@@ -13,7 +13,7 @@
 // each other's staging phases.
 //
 // F16 = true ("f16x3", segmif_gemm_split16_*; the format and its range guard are described in conv3x3_planes.hip /
-// planes16.h): A is split into half pairs (144-byte LDS rows: 2 K halves x 2 planes x 32 B + 16), the weight image keeps
+// split_ops.h): A is split into half pairs (144-byte LDS rows: 2 K halves x 2 planes x 32 B + 16), the weight image keeps
 // its 208-byte rows with the planes W0 | W - W0 | 2^-11 W0 of the row scaled by 2^e(n), three products per MAC, the
 // epilogue multiplies by 2^-e(n); max |A| of what a workgroup staged is folded into the guard slot.
 #include <hip/hip_runtime.h>
@@ -24,18 +24,11 @@
 #include <string.h>
 
 #include "igemm_common.h"
-#include "planes16.h"
+#include "split_ops.h"
 #include "segmif_hip.h"
 
 namespace segmif {
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 #ifndef GEMM_DBG
 #define GEMM_DBG 0  // tuning aid: 1 = s_memtime timeline probe (tools/gemm_timeline.py)
@@ -54,20 +47,6 @@ constexpr int GBM = 128, GBN = 128, GBK = 32;
 constexpr int GPITCH = 208;                   // bytes per LDS row
 constexpr int GTILE = GBM * GPITCH;           // 26 624 bytes = 26 DMA instructions of 1 KB
 constexpr int GPITCH_H = 144;                 // f16x3: bytes per LDS row of A (9 sixteen-byte slots: odd, conflict-free)
-
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
-  f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
-
-__device__ __forceinline__ void split3(float x0, float x1, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
-  p0 = pk_bf16(x0, x1);
-  float r0 = x0 - __uint_as_float(p0 << 16), r1 = x1 - __uint_as_float(p0 & 0xffff0000u);
-  p1 = pk_bf16(r0, r1);
-  r0 -= __uint_as_float(p1 << 16);
-  r1 -= __uint_as_float(p1 & 0xffff0000u);
-  p2 = pk_bf16(r0, r1);
-}
 
 struct GemmSplitK {
   const float* a;
@@ -179,8 +158,8 @@ __global__ __launch_bounds__(256) void gemm_split_kernel(const GemmSplitK p) {
         amx = p16::absmax_pk(p16::absmax_pk(amx, ha, la), hb, lb);
       } else {
         uint32_t p0a, p1a, p2a, p0b, p1b, p2b;
-        split3(x[0], x[1], p0a, p1a, p2a);
-        split3(x[2], x[3], p0b, p1b, p2b);
+        bf3::split3(x[0], x[1], p0a, p1a, p2a);
+        bf3::split3(x[2], x[3], p0b, p1b, p2b);
         *reinterpret_cast<u32x2*>(As + a_dst[j]) = u32x2{p0a, p0b};
         *reinterpret_cast<u32x2*>(As + a_dst[j] + 32) = u32x2{p1a, p1b};
         *reinterpret_cast<u32x2*>(As + a_dst[j] + 64) = u32x2{p2a, p2b};
@@ -194,8 +173,7 @@ __global__ __launch_bounds__(256) void gemm_split_kernel(const GemmSplitK p) {
     for (int j = 0; j < 7; ++j) {
       const int i = j * 4 + wave;
       if (i < GTILE / 1024)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + i * 1024),
-                                         (__attribute__((address_space(3))) void*)(Bs + i * 1024), 16, 0, 0);
+        dma16(src + i * 1024, Bs + i * 1024);
     }
   };
 
@@ -353,7 +331,7 @@ __global__ void gemm_split_pack_kernel(const float* __restrict__ w, int N, int K
   const int n = nt * GBN + row, k = ks * GBK + kk;
   const float x = (n < N && k < K) ? w[(long long)n * ldw + k] : 0.f;
   uint32_t p0, p1, p2;
-  split3(x, 0.f, p0, p1, p2);
+  bf3::split3(x, 0.f, p0, p1, p2);
   uint16_t* dst = out + (((long long)nt * nks + ks) * GBM + row) * (GPITCH / 2) + (kk >> 4) * 48 + (kk & 15);
   dst[0] = (uint16_t)(p0 & 0xffffu);
   dst[16] = (uint16_t)(p1 & 0xffffu);

@@ -27,30 +27,11 @@
 
 #include "segmif_hip.h"
 #include "igemm_common.h"
-#include "planes16.h"
-
+#include "split_ops.h"
 
 using namespace segmif;
 
 namespace {
-
-typedef __bf16 ig_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float ig_f32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t ig_u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t ig_pk_bf16(float a, float b) {
-  ig_f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, ig_bf16x2));
-}
-// x = p0 + p1 + p2, three bf16 each (round to nearest, exact residuals): the planes format's split (conv3x3_planes.hip)
-__device__ __forceinline__ void ig_split3(float x0, float x1, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
-  p0 = ig_pk_bf16(x0, x1);
-  float r0 = x0 - __uint_as_float(p0 << 16), r1 = x1 - __uint_as_float(p0 & 0xffff0000u);
-  p1 = ig_pk_bf16(r0, r1);
-  r0 -= __uint_as_float(p1 << 16);
-  r1 -= __uint_as_float(p1 & 0xffff0000u);
-  p2 = ig_pk_bf16(r0, r1);
-}
 
 enum { MODE_DENSE = 0, MODE_CONV = 1, MODE_GENERIC = 2, MODE_DENSE2 = 3 };
 
@@ -458,21 +439,21 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmK p) {
               const int chunk = (n0 + wn * WN + 32 * j) / 16 + q;
               unsigned char* dst = pl_px + (long long)chunk * p.pl_Hp * p.pl_Wp * pl_pitch;
               if (p.pl_f16) {
-                ig_u32x4 hi, lo;
+                u32x4 hi, lo;
                 p16::split8(yy, hi, lo);
-                *reinterpret_cast<ig_u32x4*>(dst) = hi;
-                *reinterpret_cast<ig_u32x4*>(dst + 32) = lo;
+                *reinterpret_cast<u32x4*>(dst) = hi;
+                *reinterpret_cast<u32x4*>(dst + 32) = lo;
                 pl_amx = p16::absmax_pk4(pl_amx, hi, lo);
               } else {
-                ig_u32x4 pp[3];
+                u32x4 pp[3];
   #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                   uint32_t a, b, c;
-                  ig_split3(yy[2 * e], yy[2 * e + 1], a, b, c);
+                  bf3::split3(yy[2 * e], yy[2 * e + 1], a, b, c);
                   pp[0][e] = a; pp[1][e] = b; pp[2][e] = c;
                 }
   #pragma unroll
-                for (int k = 0; k < 3; ++k) *reinterpret_cast<ig_u32x4*>(dst + k * 32) = pp[k];
+                for (int k = 0; k < 3; ++k) *reinterpret_cast<u32x4*>(dst + k * 32) = pp[k];
               }
             }
           }

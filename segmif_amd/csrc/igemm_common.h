@@ -4,9 +4,6 @@
 
 #include "segmif_hip.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace segmif {
 
 struct IgemmK {
@@ -36,7 +33,7 @@ struct IgemmK {
   unsigned char* planes;  // optional planes copy of the output (conv3x3_planes.hip format): chunks [pl_chunk0, pl_chunk0 + N/16)
   int pl_Hp, pl_Wp, pl_chunks, pl_chunk0;
   int pl_f16;             // planes are f16x3 half pairs (64 bytes per pixel) instead of bf16 triples (96)
-  uint32_t* pl_amax;      // f16x3: range slots receiving max |output| (planes16.h) or null
+  uint32_t* pl_amax;      // f16x3: range slots receiving max |output| (split_ops.h) or null
   int pl_amax_images;     // > 1: one slot per image (M = images x OH x OW), else everything reports to pl_amax[0]
   const float* mask;  // out = mask[m][n] > 0 ? y : 0, applied after the residual: the split 3x3 tile (DRDB backward) and the
   int ldm;            // dense tiles' 16-byte epilogue (CrossPath backward: a gradient written through the consumer's ReLU mask)
@@ -48,11 +45,6 @@ struct IgemmK {
   int out_amax_n;
   int vec4;  // epilogue may use 16-byte accesses: N, ldo, ldr, z strides multiples of 4 and out / res / bias / ws 16-byte aligned
 };
-
-__device__ __forceinline__ float gelu_exact(float x) {
-  return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
-}
-
 
 // halo-tiled 3x3 stride-1 convolution (conv3x3.hip); variant 0: 16-channel chunks, 1: 8-channel chunks
 bool conv3x3_halo_eligible(const IgemmK& k);

@@ -7,7 +7,7 @@
 //
 //   A      the tile's 14 x 18 halo of tokens (252 -> 8 row blocks of 32) is loaded ONCE, normalised (LayerNorm in registers:
 //          a token's row is split over the two half-waves, one cross-half shuffle per statistic) and split into half pairs
-//          straight into MFMA operand registers (f16x3 format, planes16.h) - no LDS for A;
+//          straight into MFMA operand registers (f16x3 format, split_ops.h) - no LDS for A;
 //   per chunk of 32 hidden channels (4C / 32 chunks):
 //   P1     fc1 on the matrix pipe (the chunk's weights + constants arrive as ONE LDS-DMA image, double-buffered and issued a
 //          whole chunk ahead; 3 products per MAC), + bias, zero outside the image (the dwconv's
@@ -27,7 +27,7 @@
 #include <stdint.h>
 
 #include "igemm_common.h"
-#include "planes16.h"
+#include "split_ops.h"
 #include "segmif_hip.h"
 
 #ifndef MF_DBG
@@ -49,10 +49,6 @@ __device__ unsigned long long mixffn_timeline[256][16][8];
 #else
 #define MF_TL(chunk, slot)
 #endif
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int MF_TH = 12, MF_TW = 16;          // output tile (pixels)
 constexpr int MF_HH = MF_TH + 2, MF_HW = MF_TW + 2;
@@ -92,37 +88,6 @@ struct MixFfnK {
   int amax_images;
 };
 
-// GELU(x) = x Phi(x) on ~16 vector-ALU operations (the libm erff of the stand-alone dwconv kernel costs ~60; this kernel is bound
-// by its vector ALU phase).  Phi through erfc(z), z = |x| / sqrt 2, in the rational-times-Gaussian form of Abramowitz & Stegun
-// 7.1.26 (|error of erf| <= 1.5e-7, i.e. <= 7.5e-8 |x| on GELU: about one fp32 ulp of x):
-//     erfc(z) ~ (a1 t + .. + a5 t^5) exp(-z^2),  t = 1 / (1 + p z);   Phi = x >= 0 ? 1 - erfc / 2 : erfc / 2.
-__device__ __forceinline__ float gelu_fast(float x) {
-  const float ax = fabsf(x);
-  const float t = __builtin_amdgcn_rcpf(fmaf(ax, 0.3275911f * 0.70710678118654752440f, 1.0f));
-  float q = fmaf(t, 0.5f * 1.061405429f, 0.5f * -1.453152027f);  // (coefficients carry the 1/2 of erfc / 2)
-  q = fmaf(q, t, 0.5f * 1.421413741f);
-  q = fmaf(q, t, 0.5f * -0.284496736f);
-  q = fmaf(q, t, 0.5f * 0.254829592f);
-  const float e = __builtin_amdgcn_exp2f(x * x * -0.72134752044448170368f);  // exp(-x^2 / 2)
-  const float half_erfc = q * t * e;
-  const float phi = x >= 0.f ? 1.0f - half_erfc : half_erfc;
-  return x * phi;
-}
-
-__device__ __forceinline__ f32x16 mfma16(const u32x4& a, const u32x4& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
-// (r6) SADDR form (csrc/conv3x3_planes.hip, dma16s): wave-uniform base in SGPRs + 32-bit lane offset
-__device__ __forceinline__ void mf_dma16s(const unsigned char* sbase, uint32_t voff, unsigned char* lds_wave_base) {
-  const uint32_t m = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)lds_wave_base;
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(m) : "memory", "m0");
-}
-__device__ __forceinline__ void mf_dma16(const unsigned char* src, unsigned char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
 template <int C, int NW>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2))) void mixffn_kernel(const MixFfnK p) {
   using G = MfGeom<C>;
@@ -155,7 +120,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
   auto dma = [&](int j) {
     const unsigned char* src = p.wimg + (long long)j * G::CHB;  // (uniform: SADDR form, the lane offset is a constant)
     unsigned char* dst = Wb + (j & 1) * G::CHB;
-    for (int i = wave; i < G::CHB / 1024; i += NW) mf_dma16s(src + i * 1024, (uint32_t)(lane * 16), dst + i * 1024);
+    for (int i = wave; i < G::CHB / 1024; i += NW) dma16s(src + i * 1024, (uint32_t)(lane * 16), lds_addr(dst + i * 1024));
   };
   dma(0);
 
@@ -320,7 +285,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #pragma unroll
             for (int e = 0; e < 4; ++e) a[e] = fmaf(win[dy][dx][e], wt[dy * 3 + dx][e], a[e]);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) a[e] = gelu_fast(a[e]);
+        for (int e = 0; e < 4; ++e) a[e] = gelu_as(a[e]);
         p16::split2(a[0], a[1], g_hi[i][0], g_lo[i][0]);
         p16::split2(a[2], a[3], g_hi[i][1], g_lo[i][1]);
         const bool ok = y0 + yb + i < p.H && x0 + xc < p.W;

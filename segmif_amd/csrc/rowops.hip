@@ -6,11 +6,10 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-#include "planes16.h"
+#include "split_ops.h"
 #include "segmif_hip.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+using namespace segmif;
 
 namespace {
 
@@ -85,7 +84,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 
 // (r5) LayerNorm writing PAIRS rows (gemm_pairs.hip: 16-channel groups of [16 hi | 16 lo] halves; the byte count is fp32's) with
 // max |y| folded into the range slot of each row's image.  Same arithmetic and launch shape as layernorm_kernel.  Its waves live
-// for a row or two, so (planes16.h, fold_pat_async) they report with a fire-and-forget atomic - no look first, whose latency
+// for a row or two, so (split_ops.h, fold_pat_async) they report with a fire-and-forget atomic - no look first, whose latency
 // every wave would end on - and the launch is given `nsub` ROWS of slots (a power of two, `sub_stride` words apart), workgroup i
 // reporting to row i % nsub: the 76 800 atomics of a stage-3 launch meet on nsub x images addresses instead of `images`.
 template <int G, int IT>
@@ -140,13 +139,13 @@ __global__ __launch_bounds__(1024) void layernorm_pairs_kernel(const float* __re
       segmif::p16::split2(o[0], o[1], ha, la);
       segmif::p16::split2(o[2], o[3], hb, lb);
       // (the quad u & ~3 .. u | 3 = one 16-channel group is active as a whole: C % 16 == 0)
-      *reinterpret_cast<segmif::p16::u4*>(y + row * ldy_bytes + (u >> 2) * 64 + (u & 3) * 16) = segmif::p16::quad_piece(ha, hb, la, lb);
+      *reinterpret_cast<u32x4*>(y + row * ldy_bytes + (u >> 2) * 64 + (u & 3) * 16) = segmif::p16::quad_piece(ha, hb, la, lb);
       amx = segmif::p16::absmax_pk(segmif::p16::absmax_pk(amx, ha, la), hb, lb);
     }
   }
   if (amax) {
     // The workgroup's RPB consecutive rows normally belong to one image: its 16 waves meet in LDS and one lane reports with a
-    // fire-and-forget atomic (planes16.h, fold_pat_block).  Slot words of neighbouring images share a cache line and atomics on one
+    // fire-and-forget atomic (split_ops.h, fold_pat_block).  Slot words of neighbouring images share a cache line and atomics on one
     // line queue up (~10 ns each): with one report per WAVE a stage-2 launch queued 9 600 of them per line and took 118 us
     // instead of 31.  A workgroup that straddles two images reports per wave.
     uint32_t* slots = amax + (long long)(blockIdx.x & (unsigned)(nsub - 1)) * sub_stride;
@@ -193,26 +192,6 @@ int launch_ln(const float* x, const float* g, const float* b, float* y, long lon
 // x-neighbours come from adjacent lanes' cache lines.
 // ---------------------------------------------------------------------------------------------
 constexpr int DW_TY = 8;
-
-__device__ __forceinline__ float gelu_exact(float x) {
-  return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
-}
-// (r6) The erf GELU as csrc/mixffn.hip computes it for stages 1-2 (Abramowitz & Stegun 7.1.26: |error of erf| <= 1.5e-7, i.e.
-// <= 7.5e-8 |x| on GELU - about one fp32 ulp of x; 12 instructions instead of erff's ~35), for the PAIRS producer of stages 3-4:
-// the same function on both halves of the encoder, inside the same guarded inference scope; the fp32 kernel (training, and the
-// path a tripped pair is repeated on) keeps erff.
-__device__ __forceinline__ float gelu_as(float x) {
-  const float ax = fabsf(x);
-  const float t = __builtin_amdgcn_rcpf(fmaf(ax, 0.3275911f * 0.70710678118654752440f, 1.0f));
-  float q = fmaf(t, 0.5f * 1.061405429f, 0.5f * -1.453152027f);  // (coefficients carry the 1/2 of erfc / 2)
-  q = fmaf(q, t, 0.5f * 1.421413741f);
-  q = fmaf(q, t, 0.5f * -0.284496736f);
-  q = fmaf(q, t, 0.5f * 0.254829592f);
-  const float e = __builtin_amdgcn_exp2f(x * x * -0.72134752044448170368f);  // exp(-x^2 / 2)
-  const float half_erfc = q * t * e;
-  const float phi = x >= 0.f ? 1.0f - half_erfc : half_erfc;
-  return x * phi;
-}
 
 template <bool GELU>
 __global__ __launch_bounds__(256) void dwconv3x3_gelu_kernel(const float* __restrict__ x, const float* __restrict__ w9,
@@ -719,7 +698,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_xt_kernel(const float* __restri
           segmif::p16::split2(o[2], o[3], hb, lb);
           // (threads c, c + 4, c + 8, c + 12 of one 16-channel group are four consecutive lanes with the same x0, j, live)
           unsigned char* d16 = reinterpret_cast<unsigned char*>(dst + (long long)j * C - c) + (c >> 4) * 64 + ((c >> 2) & 3) * 16;
-          *reinterpret_cast<segmif::p16::u4*>(d16) = segmif::p16::quad_piece(ha, hb, la, lb);
+          *reinterpret_cast<u32x4*>(d16) = segmif::p16::quad_piece(ha, hb, la, lb);
           amx = segmif::p16::absmax_pk(segmif::p16::absmax_pk(amx, ha, la), hb, lb);
         }
       } else {

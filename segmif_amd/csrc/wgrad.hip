@@ -20,7 +20,7 @@
 #include <string.h>
 
 #include "igemm_common.h"
-#include "planes16.h"
+#include "split_ops.h"
 #include "segmif_hip.h"
 
 #ifndef WG3_DBG
@@ -420,26 +420,6 @@ __global__ __launch_bounds__(256) void wgrad3x3_halo_kernel(const Wg3K p) {
 // bytes), splits them, and writes one 16-byte unit per plane.  Same tiling, strip partials, bias sums and wave
 // combine as the fp32 kernel; the partial slabs go through the same deterministic reduce.
 // ---------------------------------------------------------------------------------------------------
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
-typedef _Float16 wg_f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ uint32_t wg_pk_bf16(float a, float b) {
-  f32x2v v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2v));
-}
-
-// (x0, x1) -> three dwords, each (bf16 of x0 in the low half, of x1 in the high half); x = p0 + p1 + p2 to 24 bits
-__device__ __forceinline__ void wg_split3(float x0, float x1, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
-  p0 = wg_pk_bf16(x0, x1);
-  float r0 = x0 - __uint_as_float(p0 << 16), r1 = x1 - __uint_as_float(p0 & 0xffff0000u);
-  p1 = wg_pk_bf16(r0, r1);
-  r0 -= __uint_as_float(p1 << 16);
-  r1 -= __uint_as_float(p1 & 0xffff0000u);
-  p2 = wg_pk_bf16(r0, r1);
-}
 
 __global__ __launch_bounds__(256) void wgrad3x3_split_kernel(const Wg3K p) {
   constexpr int DIL = 2, TH = 8, TW = 32, HH = TH + 2 * DIL, HWD = TW + 2 * DIL;
@@ -517,7 +497,7 @@ __global__ __launch_bounds__(256) void wgrad3x3_split_kernel(const Wg3K p) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       uint32_t a, b, d;
-      wg_split3(v0[c], v1[c], a, b, d);
+      bf3::split3(v0[c], v1[c], a, b, d);
       w0[c] = a; w1[c] = b; w2[c] = d;
     }
     uint32_t* dst = base + unit * 4;  // (pair, quad) -> dword pair * 32 + quad * 4
@@ -639,7 +619,7 @@ __global__ __launch_bounds__(256) void wgrad3x3_split_kernel(const Wg3K p) {
 // partial slabs, reduce - is the one-team kernel's.
 // ---------------------------------------------------------------------------------------------------
 // F16 (round 4, default on the training path): both operands as half pairs x = hi + lo of the value scaled by the power of two
-// that puts the tensor's maximum (device range slots, planes16.h range_scale) in [2^13, 2^14) - lo is kept UNscaled here
+// that puts the tensor's maximum (device range slots, split_ops.h range_scale) in [2^13, 2^14) - lo is kept UNscaled here
 // (with the maximum pinned at 2^13 it stays a normal half down to 2^-3, i.e. 2^-16 of the maximum; below that its absolute
 // error is 2^-25, 2^-38 of the maximum) so that the three products hi.hi, hi.lo, lo.hi share one accumulator; the partial
 // slabs are written back unscaled (exact).  Half the matrix-pipe work and two thirds of the LDS traffic of the bf16x6 form.
@@ -726,12 +706,12 @@ __global__ __launch_bounds__(512) void wgrad3x3_split2_kernel(const Wg3K p) {
         u32x4 w0, w1;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          const p16::f2 v = {v0[c] * sc, v1[c] * sc};
-          const p16::h2 hi = __builtin_convertvector(v, p16::h2);  // round to nearest even
-          const p16::f2 back = __builtin_convertvector(hi, p16::f2);
-          const p16::f2 res = {v[0] - back[0], v[1] - back[1]};     // exact in fp32
+          const f32x2 v = {v0[c] * sc, v1[c] * sc};
+          const f16x2 hi = __builtin_convertvector(v, f16x2);  // round to nearest even
+          const f32x2 back = __builtin_convertvector(hi, f32x2);
+          const f32x2 res = {v[0] - back[0], v[1] - back[1]};     // exact in fp32
           w0[c] = __builtin_bit_cast(uint32_t, hi);
-          w1[c] = __builtin_bit_cast(uint32_t, __builtin_convertvector(res, p16::h2));
+          w1[c] = __builtin_bit_cast(uint32_t, __builtin_convertvector(res, f16x2));
         }
         *reinterpret_cast<u32x4*>(dst) = w0;
         *reinterpret_cast<u32x4*>(dst + npairs * 32) = w1;
@@ -740,7 +720,7 @@ __global__ __launch_bounds__(512) void wgrad3x3_split2_kernel(const Wg3K p) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           uint32_t a, b, d;
-          wg_split3(v0[c], v1[c], a, b, d);
+          bf3::split3(v0[c], v1[c], a, b, d);
           w0[c] = a; w1[c] = b; w2[c] = d;
         }
         *reinterpret_cast<u32x4*>(dst) = w0;
@@ -818,8 +798,8 @@ __global__ __launch_bounds__(512) void wgrad3x3_split2_kernel(const Wg3K p) {
               for (int i = 0; i < 4; ++i) bw[i] = __builtin_amdgcn_alignbit(b6[cb][pl][i + 1], b6[cb][pl][i], 16);
             }
             if constexpr (F16)
-              acc[ky * 3 + kx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wg_f16x8, a[ca][PA[t]]),
-                                                                        __builtin_bit_cast(wg_f16x8, bw), acc[ky * 3 + kx], 0, 0, 0);
+              acc[ky * 3 + kx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[ca][PA[t]]),
+                                                                        __builtin_bit_cast(f16x8, bw), acc[ky * 3 + kx], 0, 0, 0);
             else
               acc[ky * 3 + kx] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[ca][PA[t]]),
                                                                          __builtin_bit_cast(bf16x8, bw), acc[ky * 3 + kx], 0, 0, 0);
