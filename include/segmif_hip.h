@@ -482,6 +482,14 @@ int segmif_linattn_fold_f32(const double* partial, const float* wend, float* wef
  * path's context fold (core/model_fusion.py:281-286, :316-326, :357-360 under autograd). */
 int segmif_linattn_fold_bwd_f32(const double* ktv, const float* wend, int ldw, int wofs, const float* dweff, int ldweff, int kofs,
                                 float scale, double* dktv, float* dwend_part, int ldp, int B, int Nout, void* stream);
+/* Backward of segmif_linattn_fold_f32 at any geometry the forward takes: C = heads * d <= 64, C % 16 == 0, d <= 8 (the ablation
+ * networks' interaction modules run at dim 32 = 8 heads of 4).  Arguments as segmif_linattn_fold_bwd_f32 plus heads, d: ktv / dktv
+ * are (B, heads, d, d) fp64, dweff's columns [kofs, kofs + C) and wend's [wofs, wofs + C) are the fold's, and dwend_part[b][n][wofs + c]
+ * (c < C, pitch ldp floats) receives this image's share of d end_proj (the caller sums over b).  fp64 where the forward is: the
+ * softmax over the k index, dktv and dwend_part.  At heads = d = 8 it reproduces segmif_linattn_fold_bwd_f32. */
+int segmif_linattn_fold_bwd_generic_f32(const double* ktv, const float* wend, int ldw, int wofs, const float* dweff, int ldweff,
+                                        int kofs, float scale, double* dktv, float* dwend_part, int ldp, int B, int Nout, int heads,
+                                        int d, void* stream);
 
 /*
  * CrossPath in inference without its 128-wide intermediates (csrc/crosspath.hip; core/model_fusion.py:329-361).
@@ -564,6 +572,12 @@ int segmif_fuse_ycrcb_f32(const float* vis_nchw, const float* yf, float* out_nch
  * :807-813); mode 2 y = silu(a) (AttentionModule alone; b may be NULL) */
 int segmif_pointwise2_f32(const float* a, int lda, const float* b, int ldb, float* y, int ldy, int64_t rows, int C, int mode,
                           void* stream);
+/* Backward of modes 1 and 2 of segmif_pointwise2_f32 from the saved pre-activations: mode 1 da = dy * silu'(a) and
+ * db = dy * silu'(b); mode 2 da only (b, db may be NULL); silu'(z) = sigmoid(z) (1 + z (1 - sigmoid(z))).  Rows views in and out
+ * (rows x C, pitches in floats, C % 4 == 0, every pointer 16-byte aligned): the gradients may land in channel slices of wider
+ * buffers.  Mode 0 (a + b) has no kernel: its gradient passes through to both inputs. */
+int segmif_pointwise2_bwd_f32(const float* dy, int ldy, const float* a, int lda, const float* b, int ldb, float* da, int ldda,
+                              float* db, int lddb, int64_t rows, int C, int mode, void* stream);
 /* RGB2YCrCb / YCrCb2RGB themselves (core/model_fusion.py:69-91, :93-111; called at train.py:355, :365) and their backward, on
  * planar (B, 3, HW) images: mode 0 RGB -> YCrCb; mode 1 YCrCb -> RGB (ysrc != NULL supplies channel 0 from a (B, 1, HW)
  * tensor: train.py:362-364's clone + slice assignment folded in); mode 2 backward of 0 (in = d/dYCrCb -> d/dRGB); mode 3

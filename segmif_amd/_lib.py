@@ -231,6 +231,10 @@ SIGNATURES = {
     "segmif_linattn_fold_bwd_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_int,
                                           c_int, c_int, c_void_p]),
     "segmif_pointwise2_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_void_p]),
+    "segmif_linattn_fold_bwd_generic_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_float, c_void_p,
+                                                  c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "segmif_pointwise2_bwd_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int64,
+                                        c_int, c_int, c_void_p]),
     "segmif_argmax_nhwc_i32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "segmif_bilinear_argmax_i32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
 }

@@ -217,18 +217,25 @@ class ConvFn(torch.autograd.Function):
             and 16 <= N <= 256 and 16 <= cin <= 256
 
     @staticmethod
-    def forward(ctx, x, w, b, k, stride, pad, dil, act, slope):
+    def forward(ctx, x, w, b, k, stride, pad, dil, act, slope, out=None):
+        """out: optional Out placement of the result (a DRDB buffer's first channels, a half of conv2's input), stride 1 only."""
         _no_prelu(act)
         N = w.shape[0]
         xslot = None
+        o = None
+        if out is not None:
+            if stride != 1:
+                raise RuntimeError("ConvFn: an output placement needs a stride-1 conv")
+            o = out.t
         if ConvFn._f16(k, stride, pad, dil, x.shape[-1], N) and ops.aligned16(x):
             xslot = ops.range_slots(1, x.device).view(-1)  # max |x|: the kernel scales its staged input from it
             ops.amax_rows(x, xslot)
             y = ops.conv2d(x, ops.pack_weight_split16(w), N, k, stride=stride, pad=pad, dil=dil, bias=b, act=act, prelu=slope,
-                           in_amax=xslot)
+                           in_amax=xslot, out=o)
         else:
             y = ops.conv2d(x, _pack_conv(w, k, stride, pad, dil), N, k, stride=stride, pad=pad, dil=dil, bias=b, act=act,
-                           prelu=slope)
+                           prelu=slope, out=o)
+        ctx.placed = out is not None
         ctx.geom = (k, stride, pad, dil, act)
         ctx.has_bias = b is not None
         ctx.save_for_backward(x, w, y if act == ACT_RELU else None, xslot)
@@ -239,7 +246,7 @@ class ConvFn(torch.autograd.Function):
         x, w, y, xslot = ctx.saved_tensors
         k, stride, pad, dil, act = ctx.geom
         N, cin = w.shape[0], w.shape[1]
-        dy = dy.contiguous()
+        dy = _rows(dy) if ctx.placed else dy.contiguous()  # (a placed output's gradient: a channel slice, read in place)
         dz = act_bwd(dy, y, ACT_RELU) if act == ACT_RELU else dy
         dx = dw = db = None
         zslot = None
@@ -287,7 +294,7 @@ class ConvFn(torch.autograd.Function):
             dw, db = (r if want_b else (r, None))
         elif want_b:
             db = colsum(dz)
-        return dx, dw, db, None, None, None, None, None, None
+        return dx, dw, db, None, None, None, None, None, None, None
 
 
 class PReluFn(torch.autograd.Function):
@@ -640,9 +647,10 @@ class DRDBFn(torch.autograd.Function):
     the reference is a channel prefix of it)."""
 
     @staticmethod
-    def forward(ctx, x, home, *params):  # params = (w1, b1, ..., w5, b5, w6, b6)
+    def forward(ctx, x, home, out_at, *params):  # params = (w1, b1, ..., w5, b5, w6, b6)
         """home: Out holding the (B, H, W, total) buffer whose first C0 channels x already IS (its producer wrote there:
-        PReluFn / LayerNormFn with out=), or None (x is copied in)."""
+        PReluFn / LayerNormFn with out=), or None (x is copied in).  out_at: optional Out placement of the result (the next
+        block's concat buffer, a half of a concatenated conv input)."""
         B, H, W, C0 = x.shape
         growth = params[0].shape[0]
         total = C0 + 5 * growth
@@ -669,7 +677,8 @@ class DRDBFn(torch.autograd.Function):
                            out=buf[..., ch:ch + growth])
             ch += growth
         w6, b6 = params[10], params[11]
-        out = ops.linear(buf, ops.pack_weight(w6), C0, bias=b6, act=ACT_RELU, res=buf[..., :C0])
+        out = ops.linear(buf, ops.pack_weight(w6), C0, bias=b6, act=ACT_RELU, res=buf[..., :C0],
+                         out=out_at.t if out_at is not None else None)
         ctx.save_for_backward(buf, out, slots, *params)
         return out
 
@@ -731,7 +740,7 @@ class DRDBFn(torch.autograd.Function):
             ch -= growth
         # (a rows view of the gradient buffer: the consumers - PReluFn / LayerNormFn backward - read it in place)
         dx = dbuf[..., :C0] if ctx.needs_input_grad[0] else None
-        return (dx, None, *grads)
+        return (dx, None, None, *grads)
 
 
 class BatchedLinearFn(torch.autograd.Function):
@@ -1089,6 +1098,169 @@ class ContextFoldFn(torch.autograd.Function):
         return dka, dk3, dw, None, None
 
 
+class KvContextGenericFn(torch.autograd.Function):
+    """KvContextFn at any head geometry with C = heads * d <= 64, d <= 8 (the ablation networks' dim-32 CrossPaths: 8 heads of 4):
+    forward = the kv projection (one GEMM, no bias) + the generic K^T V partial sums (csrc/linattn.hip), summed in fp64 per image
+    -> (B, heads, d, d); backward as KvContextFn's: kv recomputed by one GEMM, dk / dv through per-image block-diagonal weights,
+    the input gradient through the ReLU mask into CrossProjFn's buffer when a sink is given."""
+
+    @staticmethod
+    def forward(ctx, y, wkv, heads, sink=None, which=None):
+        ctx.sink, ctx.which, ctx.heads = sink, which, heads
+        B, n, C = y.shape
+        d = C // heads
+        part = ops.linattn_partial(_gemm(y, wkv.detach().contiguous(), 2 * C), heads)
+        ctx.save_for_backward(y, wkv)
+        return part.sum(1).view(B, heads, d, d)  # fp64: these logits feed a saturated softmax
+
+    @staticmethod
+    def backward(ctx, dctx):
+        y, wkv = ctx.saved_tensors
+        B, n, C = y.shape
+        h = ctx.heads
+        d = C // h
+        w = wkv.detach().contiguous()
+        kv = _gemm(y, w, 2 * C)
+        dctx = dctx.float().contiguous()
+        # wk[b][h d + i][h d + j] = dctx[b][h][i][j], wv[b][h d + j][h d + i] = dctx[b][h][i][j] (see KvContextFn)
+        eye = torch.eye(h, device=y.device, dtype=torch.float32).view(1, h, 1, h, 1)
+        wk = (dctx.view(B, h, d, 1, d) * eye).reshape(B, C, C)
+        wv = (dctx.transpose(2, 3).reshape(B, h, d, 1, d) * eye).reshape(B, C, C)
+        dkv = torch.empty_like(kv)
+        ops.linear(kv[..., C:], wk, C, out=dkv[..., :C], batched_weight=True)
+        ops.linear(kv[..., :C], wv, C, out=dkv[..., C:], batched_weight=True)
+        dy = None
+        if ctx.needs_input_grad[0]:
+            sink = ctx.sink if ctx.sink is not None and ctx.sink.p is not None else None
+            if sink is not None:
+                out, mk = sink.slot(*ctx.which)
+                dy = ops.linear(dkv, w.t().contiguous(), C, out=out, mask=mk)
+                sink.done.add(tuple(ctx.which))
+            else:
+                dy = ops.linear(dkv, w.t().contiguous(), C)
+        dw = linear_wgrad(y, dkv, 2 * C) if ctx.needs_input_grad[1] else None
+        return dy, dw, None, None, None
+
+
+class ContextFoldGenericFn(torch.autograd.Function):
+    """ContextFoldFn at any head geometry, over one or two contexts: the q-th K^T V (B, heads, d, d) is folded into columns
+    [q C, (q + 1) C) of Weff (B, Nout, C * len(ktvs)) against the same columns of wend,
+        Weff[b][n][q C + h d + i] = sum_j softmax_i(ktv_q scale_q)[h][i][j] wend[n][q C + h d + j]
+    (CrossPath: the z half then the v half; CrossPath_S / _M: one half; an identity wend: the block-diagonal context itself).
+    Forward = segmif_linattn_fold_f32 per context, backward = segmif_linattn_fold_bwd_generic_f32 per context + one column sum
+    over the images for d wend."""
+
+    @staticmethod
+    def forward(ctx, wend, heads, scales, *ktvs):
+        B, _, d, _ = ktvs[0].shape
+        C = heads * d
+        w = wend.detach().contiguous()
+        ks = [k.contiguous() for k in ktvs]
+        weff = torch.empty((B, w.shape[0], C * len(ks)), device=w.device, dtype=torch.float32)
+        for q, (k, sc) in enumerate(zip(ks, scales)):
+            ops.linattn_fold(k.view(B, 1, C * d), w, weff, wofs=q * C, kofs=q * C, scale=sc, heads=heads)
+        ctx.save_for_backward(w, *ks)
+        ctx.heads, ctx.scales = heads, tuple(float(sc) for sc in scales)
+        return weff
+
+    @staticmethod
+    def backward(ctx, dweff):
+        w, *ks = ctx.saved_tensors
+        B, Nout, K = ks[0].shape[0], w.shape[0], dweff.shape[-1]
+        C = K // len(ks)
+        dweff = dweff.contiguous()
+        part = torch.empty((B, Nout, K), device=w.device, dtype=torch.float32)
+        dks = []
+        for q, (k, sc) in enumerate(zip(ks, ctx.scales)):
+            dk = torch.empty_like(k)
+            ops.linattn_fold_bwd(k, w, dweff, dk, part, q * C, q * C, sc, ctx.heads)
+            dks.append(dk)
+        dw = colsum(part.view(B, Nout * K)).view(Nout, K) if ctx.needs_input_grad[0] else None
+        return (dw, None, None, *dks)
+
+
+class TailOneFn(torch.autograd.Function):
+    """CrossPath's two closing projections with ONE attention kept (CrossPath_S: z only, CrossPath_M: v only):
+        t_i = x_i + s_i @ weff_i^T + b_i          s_1 = s_2 = y3 (z; s2 None) or s_i = u_i (v)
+    single-source batched GEMMs with the residual in the epilogue.  A shared source gets its two gradient images summed by the
+    second GEMM's epilogue (no autograd accumulation pass); with a ProjSink the source gradients go through the ReLU mask
+    straight into CrossProjFn's buffer (which = the sink slots of the sources: ((2, 0),) for y3, ((0, 1), (1, 1)) for u1, u2)."""
+
+    @staticmethod
+    def forward(ctx, s1, s2, weff1, weff2, b1, b2, x1, x2, sink=None, which=None):
+        N = weff1.shape[1]
+        ctx.sink, ctx.which, ctx.shared = sink, which, s2 is None
+        ctx.save_for_backward(s1, s2, weff1, weff2)
+        ctx.has_bias = (b1 is not None, b2 is not None)
+        t1 = ops.linear(s1, weff1.contiguous(), N, bias=b1, res=x1, batched_weight=True)
+        t2 = ops.linear(s1 if s2 is None else s2, weff2.contiguous(), N, bias=b2, res=x2, batched_weight=True)
+        return t1, t2
+
+    @staticmethod
+    def backward(ctx, dt1, dt2):
+        s1, s2, weff1, weff2 = ctx.saved_tensors
+        dt = (dt1.contiguous(), dt2.contiguous())
+        B, n, K = s1.shape
+        N = weff1.shape[1]
+        need = ctx.needs_input_grad
+        sink = ctx.sink if ctx.sink is not None and ctx.sink.p is not None else None
+        srcs = (s1, s1 if ctx.shared else s2)
+        ds, dw, db = [None, None], [None, None], [None, None]
+        for i, weff in enumerate((weff1, weff2)):
+            wt = weff.detach().transpose(1, 2).contiguous()  # (B, K, N)
+            j = 0 if ctx.shared else i  # which source this GEMM's gradient belongs to
+            if need[j]:
+                last = not ctx.shared or i == 1
+                if sink is not None and last:
+                    out, mk = sink.slot(*ctx.which[j])
+                    ds[j] = ops.linear(dt[i], wt, K, res=ds[j], out=out, mask=mk, batched_weight=True)
+                    sink.done.add(tuple(ctx.which[j]))
+                else:
+                    ds[j] = ops.linear(dt[i], wt, K, res=ds[j], out=ds[j], batched_weight=True)
+            want_b = ctx.has_bias[i] and need[4 + i]
+            if need[2 + i]:
+                dw[i] = torch.empty((B, N, K), device=s1.device, dtype=torch.float32)
+                db[i] = _bias_out(want_b, N, s1)
+                _batched_wgrad(srcs[i], dt[i], dw[i], 0, n, N, K, db=db[i])
+            elif want_b:
+                db[i] = colsum(dt[i])
+        # (the residuals' gradients are dt_i themselves: CrossProjFn adds them to its input gradients)
+        return ds[0], ds[1], dw[0], dw[1], db[0], db[1], (dt[0] if need[6] else None), (dt[1] if need[7] else None), None, None
+
+
+class SiluSumFn(torch.autograd.Function):
+    """y = silu(a) + silu(b) (b None: silu(a)) over rows views: the glue of Fusion_Network3_Average (att_i(x) + att_j(seg)) and
+    AttentionModule's closing z * sigmoid(z) (core/model_fusion.py:759-820), segmif_pointwise2_f32 modes 1 / 2 forward and
+    segmif_pointwise2_bwd_f32 backward from the saved pre-activations.  out: optional Out placement of y."""
+
+    @staticmethod
+    def forward(ctx, a, b, out=None):
+        ctx.save_for_backward(a, b)
+        return ops.pointwise2(a, b, 2 if b is None else 1, out=out.t if out is not None else None)
+
+    @staticmethod
+    def backward(ctx, dy):
+        a, b = ctx.saved_tensors
+        da, db = ops.pointwise2_bwd(_rows(dy), a, b, 2 if b is None else 1)
+        return da, db, None
+
+
+class AddSharedFn(torch.autograd.Function):
+    """(a1 + s, a2 + s) over rows views - Fusion_Network3_Add's x_i + seg (segmif_pointwise2_f32 mode 0) - as ONE node: the
+    gradients of a1 / a2 pass through, s's is their sum on the same kernel.  s then has one consumer: no autograd accumulation
+    pass, and the two pass-through gradients stay distinct tensors."""
+
+    @staticmethod
+    def forward(ctx, a1, a2, s):
+        return ops.pointwise2(a1, s, 0), ops.pointwise2(a2, s, 0)
+
+    @staticmethod
+    def backward(ctx, d1, d2):
+        d1, d2 = _rows(d1), _rows(d2)
+        ds = ops.pointwise2(d1, d2, 0) if ctx.needs_input_grad[2] else None
+        return d1, d2, ds
+
+
 class BatchNormReluFn(torch.autograd.Function):
     """Train-mode BatchNorm (batch statistics, biased variance) + ReLU over NHWC rows (rows, C).
     Returns (y, batch_mean, batch_var_biased); the caller updates the running statistics."""
@@ -1348,12 +1520,10 @@ def linear(x, w, b=None, act=ACT_NONE, slope=None, out=None):
 
 
 def conv2d(x, w, b=None, k=3, stride=1, pad=0, dil=1, act=ACT_NONE, slope=None, out=None):
-    """out (Out placement) is honoured for act == PReLU only (the activation node writes it)."""
+    """out: Out placement of the result (with act == PReLU the activation node writes it; otherwise the conv, stride 1 only)."""
     if act == ACT_PRELU:
         return PReluFn.apply(ConvFn.apply(x, w, b, k, stride, pad, dil, ACT_NONE, None), slope, out)
-    if out is not None:
-        raise RuntimeError("ag.conv2d: out= needs act == ACT_PRELU")
-    return ConvFn.apply(x, w, b, k, stride, pad, dil, act, slope)
+    return ConvFn.apply(x, w, b, k, stride, pad, dil, act, slope, out)
 
 
 def prelu(z, slope, out=None):
@@ -1389,8 +1559,8 @@ def softmax_ce(logits_nhwc, labels, ignore_index=255):
     return SoftmaxCEFn.apply(logits_nhwc, labels, ignore_index)
 
 
-def drdb(x, params, home=None):
-    return DRDBFn.apply(x, home, *params)
+def drdb(x, params, home=None, out=None):
+    return DRDBFn.apply(x, home, out, *params)
 
 
 def batched_linear(x, w, bias=None):
@@ -1407,6 +1577,28 @@ def kv_context(y, wkv, sink=None, which=None):
 
 def context_fold(ktv_a, ktv_3, wend, scale_a, scale_3):
     return ContextFoldFn.apply(ktv_a, ktv_3, wend, scale_a, scale_3)
+
+
+def kv_context_generic(y, wkv, heads, sink=None, which=None):
+    return KvContextGenericFn.apply(y, wkv, heads, sink, which)
+
+
+def context_fold_generic(wend, heads, scales, *ktvs):
+    """-> Weff (B, Nout, C * len(ktvs)); ktvs: (B, heads, d, d) fp64 K^T V, folded in this order with their scales."""
+    return ContextFoldGenericFn.apply(wend, heads, tuple(scales), *ktvs)
+
+
+def tail_one(s1, s2, weff1, weff2, b1, b2, x1, x2, sink=None, which=None):
+    return TailOneFn.apply(s1, s2, weff1, weff2, b1, b2, x1, x2, sink, which)
+
+
+def add_shared(a1, a2, s):
+    """-> (a1 + s, a2 + s)."""
+    return AddSharedFn.apply(a1, a2, s)
+
+
+def silu_sum(a, b=None, out=None):
+    return SiluSumFn.apply(a, b, out)
 
 
 def cross_proj(x1, x2, x3, w1, b1, w2, b2, w3, b3, sink=None):

@@ -169,9 +169,10 @@ class DRDB(nn.Module):
             ps += [conv.weight, conv.bias]
         return ps + [self.conv.weight, self.conv.bias]
 
-    def forward_train_nhwc(self, x, home=None):
-        """home: ag.Out of a new_buffer() whose first in_ch channels x already is (its producer wrote there): no copy in."""
-        return ag.drdb(x if home is not None else x.contiguous(), self._params(), home)
+    def forward_train_nhwc(self, x, home=None, out=None):
+        """home: ag.Out of a new_buffer() whose first in_ch channels x already is (its producer wrote there): no copy in.
+        out: optional ag.Out placement of the result (the next block's buffer, a half of a concatenated conv input)."""
+        return ag.drdb(x if home is not None else x.contiguous(), self._params(), home, out)
 
     def forward(self, x):
         require_device(x, "DRDB input")

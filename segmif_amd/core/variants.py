@@ -6,7 +6,13 @@ measured path, so they are compositions of the package's generic primitives - NH
 (`ops.conv2d`), the buffer form of the DRDB (any `in_ch`), `ops.linear`, `ops.layernorm`, the linear-attention partial sums and fold at
 any head geometry with dim <= 64 (csrc/linattn.hip, r6: these modules run at dim 32 = 8 heads of 4) and one pointwise kernel
 (`ops.pointwise2`) - with the reference's constructor / forward signatures and state_dict keys (tests/golden/variants_keys.json).
-Inference only: called with gradients wanted they raise (the training path exists for the classes train.py builds).
+
+When a call records gradients:
+  no gradient wanted (torch.no_grad(), or nothing requires grad)   the inference path above
+  gradient wanted, module.training                                 the HIP autograd path (`forward*_train`: segmif_amd.autograd
+                                                                   nodes, HIP kernels in forward and backward)
+  gradient wanted, .eval()                                         NotImplementedError (call .train())
+A freshly built module is in train mode, so a reference-style training loop trains these nets unchanged.
 
 Reference lines: Fusion_Network :158-183 (its forward cannot run upstream either: conv1 makes 64 channels, its DRDBs take 32 - the
 same RuntimeError is raised here), Network_fused :218-246, CrossPath_M :363-395, CrossPath_S :397-429, FeatureFusionModule_SoAM /
@@ -29,11 +35,32 @@ __all__ = ["Fusion_Network", "Network_fused", "CrossPath_M", "CrossPath_S", "Fea
 PRELU, RELU, NONE = ops.ACT_PRELU, ops.ACT_RELU, ops.ACT_NONE
 
 
-def _inference_only(module, *tensors):
-    if wants_grad(module, *tensors):
+def _train_path(module, *tensors):
+    """True when this call records gradients (the autograd path); False: the inference path.  Gradients wanted in eval mode
+    raise: the ablation variants train in train mode only."""
+    if not wants_grad(module, *tensors):
+        return False
+    if not module.training:
         raise NotImplementedError(
-            f"{type(module).__name__}: the ablation variants run inference only on the HIP path - call under torch.no_grad() "
-            "(the training path covers the classes train.py builds: Fusion_Network3_ac, Network3)")
+            f"{type(module).__name__}: gradients are wanted but the module is in eval mode - the ablation variants train in train "
+            "mode only: call .train() to train, or run under torch.no_grad() for inference")
+    return True
+
+
+def _tokens(t, B, N):
+    """(B, H, W, C) -> (B, N, C) token view of the same memory (a channel slice of a wider buffer stays one)."""
+    if t.is_contiguous():
+        return t.view(B, N, t.shape[-1])
+    return t.as_strided((B, N, t.shape[-1]), (N * t.stride(2), t.stride(2), 1), t.storage_offset())
+
+
+def _out_tokens(o, B, N):
+    return None if o is None else ag.Out(_tokens(o.t, B, N))
+
+
+def _nhwc1_train(x):
+    """x[:, 0:1] as NHWC on the training path (autograd-aware when x requires grad)."""
+    return x[:, 0:1].permute(0, 2, 3, 1).contiguous() if x.requires_grad else _first_channel_nhwc(x)
 
 
 def _first_channel_nhwc(x):
@@ -59,6 +86,15 @@ class _Convs(nn.Module):
             return ops.linear(x, wt, conv.out_channels, bias=conv.bias, act=act, prelu=prelu, out=out)
         return ops.conv2d(x, wt, conv.out_channels, k, pad=conv.padding[0], dil=conv.dilation[0], bias=conv.bias, act=act,
                           prelu=prelu, out=out)
+
+    def _conv_train(self, name, x, act=NONE, out=None, mod=None):
+        """_conv on the training path (ag.linear / ag.conv2d; the shared PReLU is its own node).  out: an ag.Out placement."""
+        conv = mod if mod is not None else getattr(self, name)
+        k = conv.kernel_size[0]
+        slope = self.relu.weight if act == PRELU else None
+        if k == 1:
+            return ag.linear(x, conv.weight, conv.bias, act=act, slope=slope, out=out)
+        return ag.conv2d(x, conv.weight, conv.bias, k=k, pad=conv.padding[0], dil=conv.dilation[0], act=act, slope=slope, out=out)
 
 
 def _drdb_run(drdb, buf, out=None):
@@ -145,10 +181,62 @@ class _CrossPathGeneric(nn.Module):
         z2 = self._apply_ctx(p3[..., :C], part[1], self.cross_attn2.scale)
         return res[0], res[1], [v1, z1, z2, v2]
 
-    def forward(self, x1, x2, segfeature):
+    def _ctx_map_train(self, q, ktv, scale):
+        """q @ softmax-context with gradient: a batched linear against the block-diagonal context (the fold against identity)."""
+        C = self.dim
+        eye = self._pk.get_multi(f"eye:{q.device}", (), lambda: torch.eye(C, device=q.device, dtype=torch.float32))
+        return ag.batched_linear(q, ag.context_fold_generic(eye, self.num_heads, (scale,), ktv))
+
+    def forward_tokens_train(self, x1, x2, seg, want_maps=False, outs=(None, None)):
+        """autograd path (CrossPath.forward_tokens_train at any head geometry, with the attention(s) named by USE): ag.cross_proj, the
+        generic K^T V context and fold nodes, then ag.tail_pair (zv) or ag.tail_one (one attention), LayerNorm into the optional
+        ag.Out placements outs.  want_maps: also [v1, z1, z2, v2] with gradient (their sources then have two consumers each, so
+        the ReLU-mask sink is not used)."""
+        h = self.num_heads
+        cp = [getattr(self, f"channel_proj{i}") for i in (1, 2, 3)]
+        sink = None if want_maps else ag.ProjSink()
+        y1, u1, y2, u2, y3, u3, x1r, x2r = ag.cross_proj(x1, x2, seg, cp[0].weight, cp[0].bias, cp[1].weight, cp[1].bias,
+                                                         cp[2].weight, cp[2].bias, sink)
+        k = {}
+        if "z" in self.USE:
+            k[1] = ag.kv_context_generic(y1, self.cross_attn2.kv1.weight, h, sink, (0, 0))
+            k[2] = ag.kv_context_generic(y2, self.cross_attn2.kv2.weight, h, sink, (1, 0))
+        if "v" in self.USE:
+            k[3] = ag.kv_context_generic(u3, self.cross_attn.kv3.weight, h, sink, (2, 1))
+        weffs = []
+        for i, end in ((1, self.end_proj1), (2, self.end_proj2)):
+            ktvs, scales = [], []
+            if "z" in self.USE:
+                ktvs.append(k[i])
+                scales.append(self.cross_attn2.scale)
+            if "v" in self.USE:
+                ktvs.append(k[3])
+                scales.append(self.cross_attn.scale)
+            weffs.append(ag.context_fold_generic(end.weight, h, scales, *ktvs))
+        b1, b2 = self.end_proj1.bias, self.end_proj2.bias
+        if self.USE == "zv":
+            t1, t2 = ag.tail_pair(y3, u1, u2, weffs[0], weffs[1], b1, b2, x1r, x2r, sink)
+        elif self.USE == "z":
+            t1, t2 = ag.tail_one(y3, None, weffs[0], weffs[1], b1, b2, x1r, x2r, sink, ((2, 0),))
+        else:
+            t1, t2 = ag.tail_one(u1, u2, weffs[0], weffs[1], b1, b2, x1r, x2r, sink, ((0, 1), (1, 1)))
+        r1 = ag.layernorm(t1, self.norm1.weight, self.norm1.bias, self.norm1.eps, out=outs[0])
+        r2 = ag.layernorm(t2, self.norm2.weight, self.norm2.bias, self.norm2.eps, out=outs[1])
+        if not want_maps:
+            return r1, r2
+        v1 = self._ctx_map_train(u1, k[3], self.cross_attn.scale)
+        z1 = self._ctx_map_train(y3, k[1], self.cross_attn2.scale)
+        z2 = self._ctx_map_train(y3, k[2], self.cross_attn2.scale)
+        v2 = self._ctx_map_train(u2, k[3], self.cross_attn.scale)
+        return r1, r2, [v1, z1, z2, v2]
+
+    def _forward(self, x1, x2, segfeature, want_maps=False):
         require_device(x1, f"{type(self).__name__} input")
-        _inference_only(self, x1, x2, segfeature)
-        return self.forward_tokens(x1.contiguous(), x2.contiguous(), segfeature.contiguous())
+        fn = self.forward_tokens_train if _train_path(self, x1, x2, segfeature) else self.forward_tokens
+        return fn(x1.contiguous(), x2.contiguous(), segfeature.contiguous(), want_maps=want_maps)
+
+    def forward(self, x1, x2, segfeature):
+        return self._forward(x1, x2, segfeature)
 
 
 class CrossPath_M(_CrossPathGeneric):
@@ -166,9 +254,7 @@ class CrossPath_showAttention(_CrossPathGeneric):
     USE = "zv"
 
     def forward(self, x1, x2, segfeature):
-        require_device(x1, "CrossPath_showAttention input")
-        _inference_only(self, x1, x2, segfeature)
-        return self.forward_tokens(x1.contiguous(), x2.contiguous(), segfeature.contiguous(), want_maps=True)
+        return self._forward(x1, x2, segfeature, want_maps=True)
 
 
 class _CrossPathAny(_CrossPathGeneric):
@@ -185,18 +271,28 @@ class _FfmGeneric(nn.Module):
         init_reference_style(self)
 
     def forward_nhwc(self, x1, x2, seg, out1=None, out2=None):
-        """NHWC in / out; out_i may be channel slices of wider buffers (a DRDB's concat buffer, the halves of conv2's input)."""
+        """NHWC in / out; out_i may be channel slices of wider buffers (a DRDB's concat buffer, the halves of conv2's input) - on
+        the training path ag.Out placements of them."""
         B, H, W, C = x1.shape
-        tok = lambda t: None if t is None else t.view(B, H * W, t.shape[-1]) if t.is_contiguous() else \
-            t.as_strided((B, H * W, t.shape[-1]), (H * W * t.stride(2), t.stride(2), 1), t.storage_offset())
+        if _train_path(self, x1, x2, seg):
+            tok = lambda t: t.reshape(B, H * W, t.shape[-1])
+            r1, r2 = self.cross.forward_tokens_train(tok(x1), tok(x2), tok(seg), outs=(_out_tokens(out1, B, H * W),
+                                                                                        _out_tokens(out2, B, H * W)))
+            return r1.view(B, H, W, C), r2.view(B, H, W, C)
+        tok = lambda t: None if t is None else _tokens(t, B, H * W)
         r = self.cross.forward_tokens(tok(x1), tok(x2), tok(seg), outs=(tok(out1), tok(out2)))
         return (out1 if out1 is not None else r[0].view(B, H, W, C)), (out2 if out2 is not None else r[1].view(B, H, W, C))
 
-    def forward(self, x1, x2, segfeature):
+    def _nchw(self, x1, x2, segfeature):
         require_device(x1, f"{type(self).__name__} input")
-        _inference_only(self, x1, x2, segfeature)
+        train = _train_path(self, x1, x2, segfeature)
         r1, r2 = self.forward_nhwc(ops.to_nhwc(x1), ops.to_nhwc(x2), ops.to_nhwc(segfeature))
+        if train:
+            return r1.permute(0, 3, 1, 2), r2.permute(0, 3, 1, 2)
         return ops.as_nchw(r1), ops.as_nchw(r2)
+
+    def forward(self, x1, x2, segfeature):
+        return self._nchw(x1, x2, segfeature)
 
 
 class FeatureFusionModule_SoAM(_FfmGeneric):
@@ -213,7 +309,9 @@ class FeatureFusionModule_ShowAttention(_FfmGeneric):
 
     def forward(self, x1, x2, segfeature):
         require_device(x1, "FeatureFusionModule_ShowAttention input")
-        _inference_only(self, x1, x2, segfeature)
+        if _train_path(self, x1, x2, segfeature):
+            r1, r2 = self._nchw(x1, x2, segfeature)
+            return r1, r2, [x1.detach().clone(), x2.detach().clone()]  # (the reference's copies are torch.tensor(x): no gradient)
         a, b = ops.to_nhwc(x1), ops.to_nhwc(x2)
         r1, r2 = self.forward_nhwc(a, b, ops.to_nhwc(segfeature))
         return ops.as_nchw(r1), ops.as_nchw(r2), [ops.as_nchw(a).clone(), ops.as_nchw(b).clone()]
@@ -271,11 +369,38 @@ class _FusionBase(_Convs):
         return cat
 
     def _check(self, ir, vis, out1=None, out2=None):
+        """-> True when this call takes the training path."""
         require_device(ir, f"{type(self).__name__} input")
-        _inference_only(self, ir, vis, out1, out2)
+        train = _train_path(self, ir, vis, out1, out2)
         if out1 is not None and (out1.shape[1] != 64 or out2.shape[1] != 128):
             raise RuntimeError(f"{type(self).__name__} expects 64/128-channel segmentation features, got "
                                f"{out1.shape[1]}/{out2.shape[1]} channels")
+        return train
+
+    # -- training path: autograd nodes with HIP kernels on both sides; each full-resolution intermediate is written by its
+    #    producer where its consumer reads it (ag.Out placements, ag.join), as Fusion_Network3_ac.forward_train --
+    USES_SEG_FEATURES = True  # forward takes (ir, vis, out1, out2); False: forward(ir, vis) - FusionTrainer then skips the encoder
+
+    @staticmethod
+    def _home(drdb, ir):
+        """(ag.Out of a fresh concat buffer of drdb, ag.Out of its first in_ch channels: where the block's producer writes)."""
+        B, _, H, W = ir.shape
+        buf = drdb.new_buffer(B, H, W, ir.device)
+        return ag.Out(buf), ag.Out(buf[..., :drdb.in_ch])
+
+    def _stem_train(self, ir, vis, o1=None, o2=None):
+        """_stem with gradient: conv1 + PReLU write the DRDB's concat buffer, the DRDBs write o1 / o2 (ag.Out) when given."""
+        r = []
+        for name, img, drdb, o in (("conv1_ir", ir, self.DRDB1, o1), ("conv1_vis", vis, self.DRDB2, o2)):
+            home, first = self._home(drdb, ir)
+            r.append(drdb.forward_train_nhwc(self._conv_train(name, _nhwc1_train(img), PRELU, out=first), home, out=o))
+        return r
+
+    @staticmethod
+    def _cat_train(ir, ch):
+        B, _, H, W = ir.shape
+        cat = torch.empty((B, H, W, 2 * ch), device=ir.device, dtype=torch.float32)
+        return cat, ag.Out(cat[..., :ch]), ag.Out(cat[..., ch:])
 
 
 class Fusion_Network3(_FusionBase):
@@ -310,8 +435,20 @@ class Fusion_Network3(_FusionBase):
         self.ffm.forward_nhwc(y1, y2, self._conv("conv4", ops.to_nhwc(out2)), out1=c1, out2=c2)
         return cat, a, b
 
+    def _body_train(self, ir, vis, out1, out2):
+        a, b = self._stem_train(ir, vis)
+        h3, o3 = self._home(self.DRDB3, ir)
+        h4, o4 = self._home(self.DRDB4, ir)
+        y1, y2 = self.ffm.forward_nhwc(a, b, self._conv_train("conv3", ops.to_nhwc(out1)), out1=o3, out2=o4)
+        y1, y2 = self.DRDB3.forward_train_nhwc(y1, h3), self.DRDB4.forward_train_nhwc(y2, h4)
+        cat, c1, c2 = self._cat_train(ir, 32)
+        z1, z2 = self.ffm.forward_nhwc(y1, y2, self._conv_train("conv4", ops.to_nhwc(out2)), out1=c1, out2=c2)
+        return ag.join(ag.Out(cat), z1, z2), a, b
+
     def forward(self, ir, vis, out1, out2):
-        self._check(ir, vis, out1, out2)
+        if self._check(ir, vis, out1, out2):
+            cat = self._body_train(ir, vis, out1, out2)[0]
+            return self._conv_train("conv21", self._conv_train("conv2", cat, PRELU), PRELU).permute(0, 3, 1, 2)
         return ops.as_nchw(self._tail(self._body(ir, vis, out1, out2)[0]))
 
 
@@ -332,7 +469,11 @@ class Fusion_Network3_obtainattention(Fusion_Network3):
     FFM = FeatureFusionModule_ShowAttention
 
     def forward(self, ir, vis, out1, out2):
-        self._check(ir, vis, out1, out2)
+        if self._check(ir, vis, out1, out2):
+            cat, a, b = self._body_train(ir, vis, out1, out2)
+            f2 = self._conv_train("conv2", cat)
+            f = self._conv_train("conv21", ag.prelu(f2, self.relu.weight), PRELU)
+            return f.permute(0, 3, 1, 2), [t.permute(0, 3, 1, 2) for t in (a, b, f2)]
         cat, a, b = self._body(ir, vis, out1, out2)
         f2 = self._conv("conv2", cat)
         f = self._conv("conv21", ag.prelu(f2, self.relu.weight), PRELU)
@@ -350,8 +491,28 @@ class _FusionNoFfm(_FusionBase):
         self.conv3 = nn.Conv2d(64, 32, 1, padding=0)
         self.conv4 = nn.Conv2d(128, 32, 1, padding=0)
 
+    def _mix_inputs(self, ir):
+        """Buffers the interaction reads its x inputs from, written in place by their DRDBs (the _Con concatenations); None."""
+        return None, None
+
+    def _forward_train(self, ir, vis, out1, out2):
+        place = lambda ins: [None if c is None else ag.Out(c[..., :self.CH]) for c in ins]
+        ins = self._mix_inputs(ir)
+        x1, x2 = self._stem_train(ir, vis, *place(ins))
+        h3, o3 = self._home(self.DRDB3, ir)
+        h4, o4 = self._home(self.DRDB4, ir)
+        y1, y2 = self._mix_train(x1, x2, ops.to_nhwc(out1), "conv3", 0, o3, o4, ins)
+        ins = self._mix_inputs(ir)
+        p1, p2 = place(ins)
+        y1, y2 = self.DRDB3.forward_train_nhwc(y1, h3, out=p1), self.DRDB4.forward_train_nhwc(y2, h4, out=p2)
+        cat, c1, c2 = self._cat_train(ir, self.CH)
+        z1, z2 = self._mix_train(y1, y2, ops.to_nhwc(out2), "conv4", 1, c1, c2, ins)
+        f = self._conv_train("conv2", ag.join(ag.Out(cat), z1, z2), PRELU)
+        return self._conv_train("conv21", f, PRELU).permute(0, 3, 1, 2)
+
     def forward(self, ir, vis, out1, out2):
-        self._check(ir, vis, out1, out2)
+        if self._check(ir, vis, out1, out2):
+            return self._forward_train(ir, vis, out1, out2)
         x1, x2 = self._stem(ir, vis)
         b3, b4, o3, o4 = self._bufs(ir)
         self._mix(x1, x2, self._conv("conv3", ops.to_nhwc(out1)), 0, o3, o4)
@@ -375,6 +536,19 @@ class Fusion_Network3_Con(_FusionNoFfm):
         self._conv(n1, self._cat(x1, s), out=o1)
         self._conv(n2, self._cat(x2, s), out=o2)
 
+    def _mix_inputs(self, ir):
+        B, _, H, W = ir.shape
+        return tuple(torch.empty((B, H, W, 2 * self.CH), device=ir.device, dtype=torch.float32) for _ in range(2))
+
+    def _mix_train(self, x1, x2, src, seg_conv, stage, o1, o2, ins):
+        """cat(x_i, s) -> conv: x_i is already in the buffer's first half (its DRDB wrote there); the 1x1 conv making s writes the
+        second half, once per buffer (a producer placement instead of a copy of s)."""
+        r = []
+        for x, n, c, o in ((x1, ("conv211", "conv411")[stage], ins[0], o1), (x2, ("conv221", "conv421")[stage], ins[1], o2)):
+            s = self._conv_train(seg_conv, src, out=ag.Out(c[..., self.CH:]))
+            r.append(self._conv_train(n, ag.join(ag.Out(c), x, s), out=o))
+        return r
+
 
 class Fusion_Network3_Add(_FusionNoFfm):
     """Interaction replaced by a sum + 3x3 conv (ref :714-757)."""
@@ -390,6 +564,11 @@ class Fusion_Network3_Add(_FusionNoFfm):
         self._conv(n1, ops.pointwise2(x1, s, 0), out=o1)
         self._conv(n2, ops.pointwise2(x2, s, 0), out=o2)
 
+    def _mix_train(self, x1, x2, src, seg_conv, stage, o1, o2, ins):
+        n1, n2 = (("conv211", "conv221"), ("conv411", "conv421"))[stage]
+        a1, a2 = ag.add_shared(x1, x2, self._conv_train(seg_conv, src))
+        return self._conv_train(n1, a1, out=o1), self._conv_train(n2, a2, out=o2)
+
 
 class AttentionModule(_Convs):
     """conv3x3 -> ReLU -> conv3x3 -> z * sigmoid(z)  (ref :759-770)."""
@@ -403,9 +582,14 @@ class AttentionModule(_Convs):
         h = self._conv("c0", x, RELU, mod=self.conv[0])
         return self._conv("c2", h, mod=self.conv[2])
 
+    def pre_train(self, x):
+        """pre_nhwc with gradient."""
+        return self._conv_train("c2", self._conv_train("c0", x, RELU, mod=self.conv[0]), mod=self.conv[2])
+
     def forward(self, x1):
         require_device(x1, "AttentionModule input")
-        _inference_only(self, x1)
+        if _train_path(self, x1):
+            return ag.silu_sum(self.pre_train(ops.to_nhwc(x1))).permute(0, 3, 1, 2)
         return ops.as_nchw(ops.pointwise2(self.pre_nhwc(ops.to_nhwc(x1)), None, 2))
 
 
@@ -421,9 +605,16 @@ class Fusion_Network3_Average(_FusionNoFfm):
         ops.pointwise2(a[0].pre_nhwc(x1), a[1].pre_nhwc(s), 1, out=o1)
         ops.pointwise2(a[2].pre_nhwc(x2), a[3].pre_nhwc(s), 1, out=o2)
 
+    def _mix_train(self, x1, x2, src, seg_conv, stage, o1, o2, ins):
+        a = (self.att1, self.att2, self.att3, self.att4) if stage == 0 else (self.att5, self.att6, self.att7, self.att8)
+        s = self._conv_train(seg_conv, src)
+        return (ag.silu_sum(a[0].pre_train(x1), a[1].pre_train(s), out=o1),
+                ag.silu_sum(a[2].pre_train(x2), a[3].pre_train(s), out=o2))
+
 
 class Fusion_Network_rmseg(_FusionBase):
     """Fusion_Network3_ac without the segmentation features and interactions: forward(ir, vis)  (ref :934-979)."""
+    USES_SEG_FEATURES = False
 
     def __init__(self):
         super().__init__()
@@ -434,7 +625,6 @@ class Fusion_Network_rmseg(_FusionBase):
         self.relu = nn.PReLU()
 
     def _run(self, ir, vis):
-        self._check(ir, vis)
         b3, b4, o3, o4 = self._bufs(ir)
         self._stem(ir, vis, o3, o4)  # DRDB1 / DRDB2 write straight into DRDB3's / DRDB4's concat buffers
         cat, c1, c2 = self._catbuf(ir, 64)
@@ -444,7 +634,19 @@ class Fusion_Network_rmseg(_FusionBase):
         f = self._conv("conv21", f, PRELU)
         return self._conv("conv22", f, PRELU), c1, c2
 
+    def _run_train(self, ir, vis):
+        h3, o3 = self._home(self.DRDB3, ir)
+        h4, o4 = self._home(self.DRDB4, ir)
+        x1, x2 = self._stem_train(ir, vis, o3, o4)
+        cat, c1, c2 = self._cat_train(ir, 64)
+        x1, x2 = self.DRDB3.forward_train_nhwc(x1, h3, out=c1), self.DRDB4.forward_train_nhwc(x2, h4, out=c2)
+        f = self._conv_train("conv2", ag.join(ag.Out(cat), x1, x2), PRELU)
+        f = self._conv_train("conv21", f, PRELU)
+        return self._conv_train("conv22", f, PRELU).permute(0, 3, 1, 2), x1, x2
+
     def forward(self, ir, vis):
+        if self._check(ir, vis):
+            return self._run_train(ir, vis)[0]
         return ops.as_nchw(self._run(ir, vis)[0])
 
 
@@ -452,6 +654,9 @@ class Fusion_Network_rmseg_att(Fusion_Network_rmseg):
     """...that also returns the two branch features [x1, x2]  (ref :981-1025)."""
 
     def forward(self, ir, vis):
+        if self._check(ir, vis):
+            f, x1, x2 = self._run_train(ir, vis)
+            return f, [x1.permute(0, 3, 1, 2), x2.permute(0, 3, 1, 2)]
         f, x1, x2 = self._run(ir, vis)
         return ops.as_nchw(f), [ops.as_nchw(x1), ops.as_nchw(x2)]
 

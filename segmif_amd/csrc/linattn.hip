@@ -328,6 +328,51 @@ __global__ __launch_bounds__(512) void linattn_fold_bwd_kernel(const double* __r
   }
 }
 
+// Backward of segmif_linattn_fold_f32 at any geometry the forward takes (C = heads d <= 64, d <= 8): the dim-32 interaction modules of
+// the ablation networks train through it (8 heads of 4).  Same formulas and the same fp64 arithmetic as the kernel above, entry
+// e = (h d + i) d + j owned by thread e; one workgroup per image (ktv is at most 512 doubles).
+__global__ __launch_bounds__(512) void linattn_fold_bwd_generic_kernel(const double* __restrict__ ktv, const float* __restrict__ wend,
+                                                                       int ldw, int wofs, const float* __restrict__ dweff, int ldweff,
+                                                                       int kofs, float scale, double* __restrict__ dktv,
+                                                                       float* __restrict__ dwend_part, int ldp, int Nout, int heads,
+                                                                       int d) {
+  __shared__ double ctx[512], dctx[512];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const int C = heads * d, E = C * d;
+  const int c = tid / d, j = tid % d, hh = c / d;  // tid = (h d + i) d + j, c = h d + i
+  if (tid < E) ctx[tid] = ktv[(long long)b * E + tid] * (double)scale;
+  __syncthreads();
+  if (tid < C) {  // one (h, j) column per thread: softmax over i
+    const int h2 = tid / d, j2 = tid % d;
+    double mx = -1e300, ev[8], sum = 0.0;
+    for (int q = 0; q < d; ++q) mx = fmax(mx, ctx[(h2 * d + q) * d + j2]);
+    for (int q = 0; q < d; ++q) {
+      ev[q] = exp(ctx[(h2 * d + q) * d + j2] - mx);
+      sum += ev[q];
+    }
+    for (int q = 0; q < d; ++q) ctx[(h2 * d + q) * d + j2] = ev[q] / sum;
+  }
+  const float* dw = dweff + (long long)b * Nout * ldweff + kofs;
+  if (tid < E) {
+    double acc = 0.0;
+    for (int n = 0; n < Nout; ++n) acc += (double)dw[(long long)n * ldweff + c] * (double)wend[(long long)n * ldw + wofs + hh * d + j];
+    dctx[tid] = acc;
+  }
+  __syncthreads();
+  if (tid < E) {
+    double dot = 0.0;
+    for (int q = 0; q < d; ++q) dot += ctx[(hh * d + q) * d + j] * dctx[(hh * d + q) * d + j];
+    dktv[(long long)b * E + tid] = (double)scale * ctx[tid] * (dctx[tid] - dot);
+  }
+  float* dp = dwend_part + (long long)b * Nout * ldp + wofs;
+  for (int o = tid; o < Nout * C; o += 512) {  // dWend_part[n][wofs + h d + j] = sum_i dWeff[n][kofs + h d + i] ctx[h][i][j]
+    const int n = o / C, cc = o % C, h2 = cc / d, j2 = cc % d;
+    double a = 0.0;
+    for (int q = 0; q < d; ++q) a += (double)dw[(long long)n * ldweff + h2 * d + q] * ctx[(h2 * d + q) * d + j2];
+    dp[(long long)n * ldp + cc] = (float)a;
+  }
+}
+
 }  // namespace
 
 extern "C" int segmif_linattn_num_blocks(int64_t N) { return (int)((N + LA_ROWS - 1) / LA_ROWS); }
@@ -390,5 +435,17 @@ extern "C" int segmif_linattn_fold_bwd_f32(const double* ktv, const float* wend,
   if (((uintptr_t)ktv | (uintptr_t)dktv) & 7) return SEGMIF_EINVAL;
   hipLaunchKernelGGL(linattn_fold_bwd_kernel, dim3((unsigned)B), dim3(512), 0, (hipStream_t)stream, ktv, wend, ldw, wofs, dweff, ldweff,
                      kofs, scale, dktv, dwend_part, ldp, Nout);
+  return (int)hipGetLastError();
+}
+
+extern "C" int segmif_linattn_fold_bwd_generic_f32(const double* ktv, const float* wend, int ldw, int wofs, const float* dweff,
+                                                   int ldweff, int kofs, float scale, double* dktv, float* dwend_part, int ldp, int B,
+                                                   int Nout, int heads, int d, void* stream) {
+  if (!ktv || !wend || !dweff || !dktv || !dwend_part || B <= 0 || Nout <= 0 || heads <= 0 || d <= 0 || d > 8) return SEGMIF_EINVAL;
+  const int C = heads * d;
+  if (C > 64 || (C & 15) || wofs < 0 || kofs < 0 || ldw < wofs + C || ldweff < kofs + C || ldp < wofs + C) return SEGMIF_EINVAL;
+  if (((uintptr_t)ktv | (uintptr_t)dktv) & 7) return SEGMIF_EINVAL;
+  hipLaunchKernelGGL(linattn_fold_bwd_generic_kernel, dim3((unsigned)B), dim3(512), 0, (hipStream_t)stream, ktv, wend, ldw, wofs, dweff,
+                     ldweff, kofs, scale, dktv, dwend_part, ldp, Nout, heads, d);
   return (int)hipGetLastError();
 }

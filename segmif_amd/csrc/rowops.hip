@@ -365,6 +365,31 @@ __global__ __launch_bounds__(256) void pointwise2_kernel(const float* __restrict
   *reinterpret_cast<float4*>(y + r * ldy + c) = va;
 }
 
+// Backward of modes 1 and 2 of pointwise2_kernel: da = dy silu'(a), db = dy silu'(b) (MODE 1; MODE 2: da only), with the saved
+// pre-activations, silu'(z) = s (1 + z (1 - s)), s = sigmoid(z).  expf, not __expf: the gradient is checked against fp64.
+__device__ __forceinline__ float dsilu_f(float z) {
+  const float s = 1.f / (1.f + expf(-z));
+  return s * (1.f + z * (1.f - s));
+}
+template <int MODE>
+__global__ __launch_bounds__(256) void pointwise2_bwd_kernel(const float* __restrict__ dy, int ldy, const float* __restrict__ a, int lda,
+                                                             const float* __restrict__ b, int ldb, float* __restrict__ da, int ldda,
+                                                             float* __restrict__ db, int lddb, long long rows, int C4) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= rows * C4) return;
+  const long long r = idx / C4;
+  const int c = (int)(idx - r * C4) * 4;
+  const float4 g = *reinterpret_cast<const float4*>(dy + r * ldy + c);
+  const float4 va = *reinterpret_cast<const float4*>(a + r * lda + c);
+  *reinterpret_cast<float4*>(da + r * ldda + c) =
+      make_float4(g.x * dsilu_f(va.x), g.y * dsilu_f(va.y), g.z * dsilu_f(va.z), g.w * dsilu_f(va.w));
+  if (MODE == 1) {
+    const float4 vb = *reinterpret_cast<const float4*>(b + r * ldb + c);
+    *reinterpret_cast<float4*>(db + r * lddb + c) =
+        make_float4(g.x * dsilu_f(vb.x), g.y * dsilu_f(vb.y), g.z * dsilu_f(vb.z), g.w * dsilu_f(vb.w));
+  }
+}
+
 // RGB2YCrCb / YCrCb2RGB (core/model_fusion.py:69-91, :93-111) and their backward, on planar (B, 3, HW) images.
 //   MODE 0  RGB -> YCrCb          Y = .299 R + .587 G + .114 B, Cr = (R - Y) .713 + .5, Cb = (B - Y) .564 + .5
 //   MODE 1  YCrCb -> RGB          ([Y, Cr, Cb] + [0, -.5, -.5]) M, M = [[1, 1, 1], [1.403, -.714, 0], [0, -.344, 1.773]], summed
@@ -893,6 +918,22 @@ extern "C" int segmif_pointwise2_f32(const float* a, int lda, const float* b, in
   if (mode == 0) hipLaunchKernelGGL(pointwise2_kernel<0>, grid, block, 0, s, a, lda, b, ldb, y, ldy, (long long)rows, C / 4);
   else if (mode == 1) hipLaunchKernelGGL(pointwise2_kernel<1>, grid, block, 0, s, a, lda, b, ldb, y, ldy, (long long)rows, C / 4);
   else hipLaunchKernelGGL(pointwise2_kernel<2>, grid, block, 0, s, a, lda, b, ldb, y, ldy, (long long)rows, C / 4);
+  return (int)hipGetLastError();
+}
+
+extern "C" int segmif_pointwise2_bwd_f32(const float* dy, int ldy, const float* a, int lda, const float* b, int ldb, float* da, int ldda,
+                                         float* db, int lddb, int64_t rows, int C, int mode, void* stream) {
+  if (!dy || !a || !da || rows <= 0 || C <= 0 || (C & 3) || (mode != 1 && mode != 2) || (mode == 1 && (!b || !db))) return SEGMIF_EINVAL;
+  if (ldy < C || lda < C || ldda < C || (mode == 1 && (ldb < C || lddb < C))) return SEGMIF_EINVAL;
+  if ((ldy & 3) || (lda & 3) || (ldda & 3) || (mode == 1 && ((ldb & 3) || (lddb & 3)))) return SEGMIF_EINVAL;
+  if (((uintptr_t)dy | (uintptr_t)a | (uintptr_t)da | (uintptr_t)b | (uintptr_t)db) & 15) return SEGMIF_EINVAL;
+  const long long total = (long long)rows * (C / 4);
+  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  if (mode == 1)
+    hipLaunchKernelGGL(pointwise2_bwd_kernel<1>, grid, block, 0, s, dy, ldy, a, lda, b, ldb, da, ldda, db, lddb, (long long)rows, C / 4);
+  else
+    hipLaunchKernelGGL(pointwise2_bwd_kernel<2>, grid, block, 0, s, dy, ldy, a, lda, b, ldb, da, ldda, db, lddb, (long long)rows, C / 4);
   return (int)hipGetLastError();
 }
 

@@ -1551,6 +1551,24 @@ def linattn_fold(part, wend, weff, wofs, kofs, scale, heads=8):
     return weff
 
 
+def linattn_fold_bwd(ktv, wend, dweff, dktv, dwend_part, wofs, kofs, scale, heads):
+    """Backward of linattn_fold at any geometry (heads * d <= 64, d <= 8): ktv / dktv (B, heads, d, d) fp64 contiguous, wend
+    (Nout, ldw), dweff (B, Nout, ldweff) and dwend_part (B, Nout, ldp) with unit column stride.  Writes dktv and
+    dwend_part[:, :, wofs:wofs + heads * d] (this image's share of d end_proj; the caller sums over images)."""
+    B, h, d, _ = ktv.shape
+    if h != heads or not ktv.is_contiguous() or not dktv.is_contiguous() or dktv.shape != ktv.shape:
+        raise RuntimeError("linattn_fold_bwd expects contiguous (B, heads, d, d) ktv / dktv")
+    for t, n in ((wend, "wend"), (dweff, "dweff"), (dwend_part, "dwend_part")):
+        if _req(t, n).stride(-1) != 1:
+            raise RuntimeError(f"linattn_fold_bwd: {n} needs unit column stride")
+    if dweff.stride(0) != dweff.shape[1] * dweff.stride(1) or dwend_part.stride(0) != dwend_part.shape[1] * dwend_part.stride(1):
+        raise RuntimeError("linattn_fold_bwd: dweff / dwend_part images must be packed")
+    _lib.check(_lib.load().segmif_linattn_fold_bwd_generic_f32(
+        ktv.data_ptr(), wend.data_ptr(), wend.stride(0), wofs, dweff.data_ptr(), dweff.stride(1), kofs, float(scale), dktv.data_ptr(),
+        dwend_part.data_ptr(), dwend_part.stride(1), B, wend.shape[0], heads, d, _stream()), "segmif_linattn_fold_bwd_generic_f32")
+    return dktv, dwend_part
+
+
 _LAZY_SEG = os.environ.get("SEGMIF_LAZY_SEG", "1") != "0"
 
 
@@ -1799,6 +1817,33 @@ def pointwise2(a, b, mode, out=None):
     _lib.check(_lib.load().segmif_pointwise2_f32(a.data_ptr(), lda, b.data_ptr() if b is not None else None, ldb, out.data_ptr(), ldo,
                                                  rows, C, mode, _stream()), "segmif_pointwise2_f32")
     return out
+
+
+def pointwise2_bwd(dy, a, b, mode, da=None, db=None):
+    """Backward of pointwise2 modes 1 (silu(a) + silu(b)) and 2 (silu(a)) from the pre-activations a, b: -> (da, db) with
+    da = dy silu'(a), db = dy silu'(b) (None in mode 2).  da / db: optional rows views (channel slices of wider buffers)."""
+    if mode not in (1, 2) or (mode == 1) != (b is not None):
+        raise RuntimeError("pointwise2_bwd: mode 1 takes a and b, mode 2 a only")
+    rows, C, ldy = rows_view(dy, "dy")
+    outs, lds = [], []
+    for src, o, n in ((a, da, "a"), (b, db, "b")):
+        if src is None:
+            outs.append(None)
+            lds += [0, 0]
+            continue
+        rs, cs, lds_ = rows_view(src, n)
+        if (rs, cs) != (rows, C):
+            raise RuntimeError(f"pointwise2_bwd: {n} and dy differ in shape")
+        o = torch.empty(src.shape, device=src.device, dtype=torch.float32) if o is None else o
+        ro, co, ldo = rows_view(o, "d" + n)
+        if (ro, co) != (rows, C):
+            raise RuntimeError(f"pointwise2_bwd: d{n} shape mismatch")
+        outs.append(o)
+        lds += [lds_, ldo]
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    _lib.check(_lib.load().segmif_pointwise2_bwd_f32(dy.data_ptr(), ldy, a.data_ptr(), lds[0], ptr(b), lds[2], outs[0].data_ptr(), lds[1],
+                                                     ptr(outs[1]), lds[3], rows, C, mode, _stream()), "segmif_pointwise2_bwd_f32")
+    return outs[0], outs[1]
 
 
 def argmax_nhwc(x):

@@ -94,6 +94,8 @@ class _WeightsFrozen:
 class FusionTrainer:
     """State of train_fusion's inner loop: the loss history behind its dynamic weights.
 
+    fusion_net: Fusion_Network3_ac or any of the ablation nets of core/variants.py (in train mode).
+
     seg_weight_grads: train_fusion's optimizer holds the fusion net only (train.py:316-327), yet the reference's
     backward also accumulates `.grad` on every segmentation-net parameter; nothing reads them (the seg phase's
     optimizer.zero_grad() at train.py:225 clears them, checkpoints are state_dicts).  False (default) back-propagates
@@ -113,19 +115,27 @@ class FusionTrainer:
     def step(self, ir3, vis3, mask3, labels, sync_loss_history=True):
         ir = ir3[:, 0:1]
         vis = RGB2YCrCb(vis3)
-        with torch.no_grad():
-            # (the frozen encoder pass is plain inference: a guarded scope puts it on the f16x3 kernels - fused Mix-FFN, half-pair
-            # GEMMs and attention -, per-image range slots, tripped images repeated on bf16x6)
-            enc = self.seg.denoise_net.encoder
+        # (fusion nets whose forward takes no segmentation features - the ablation nets with USES_SEG_FEATURES = False,
+        # Fusion_Network_rmseg / _rmseg_att - skip the encoder pass; a tuple output - the nets that also return feature maps -
+        # trains on its element 0)
+        if getattr(self.fus, "USES_SEG_FEATURES", True):
+            with torch.no_grad():
+                # (the frozen encoder pass is plain inference: a guarded scope puts it on the f16x3 kernels - fused Mix-FFN, half-pair
+                # GEMMs and attention -, per-image range slots, tripped images repeated on bf16x6)
+                enc = self.seg.denoise_net.encoder
 
-            def redo(out, idx):
-                sub = enc.forward_fusion(mask3.index_select(0, idx))
-                out[0].index_copy_(0, idx, sub[0])
-                out[1].index_copy_(0, idx, sub[1])
-                return out
+                def redo(out, idx):
+                    sub = enc.forward_fusion(mask3.index_select(0, idx))
+                    out[0].index_copy_(0, idx, sub[0])
+                    out[1].index_copy_(0, idx, sub[1])
+                    return out
 
-            out0, out1 = ops.run_guarded(lambda: enc.forward_fusion(mask3), mask3.device, images=mask3.shape[0], redo=redo)
-        fusion = self.fus(ir, vis, out0, out1)
+                out0, out1 = ops.run_guarded(lambda: enc.forward_fusion(mask3), mask3.device, images=mask3.shape[0], redo=redo)
+            fusion = self.fus(ir, vis, out0, out1)
+        else:
+            fusion = self.fus(ir, vis)
+        if isinstance(fusion, (tuple, list)):
+            fusion = fusion[0]
         _zero_grads(self.opt, self.reducer)
         if self.report_lap:
             with torch.no_grad():
