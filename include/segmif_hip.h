@@ -599,6 +599,21 @@ int segmif_quantize_u8(const float* x_nchw, uint8_t* out_nhwc, int32_t* minmax, 
 /* the way back, as test_segmentation.py's loader reads those PNGs (TaskFusion_dataset2.py:84-88): NHWC uint8 ->
  * NCHW fp32 = float(u) / 255 with an IEEE division (PairForward(uint8_roundtrip=True)) */
 int segmif_dequantize_u8(const uint8_t* in_nhwc, float* out_nchw, int B, int C, int64_t HW, void* stream);
+/* Fusion-quality statistics of fused_rgb / vis_rgb (B, H, W, 3) uint8 and ir (B, H, W) uint8, PER IMAGE, all integers:
+ * f = L(fused), v = L(vis), a = ir with L(R, G, B) = (299 R + 587 G + 114 B + 500) / 1000 (integer division).
+ *   joint_fa[b][f][a], joint_fv[b][f][v]   (B, 256, 256) int64 counts
+ *   sums[b][0..3]   int64: sum a v; sum_{x >= 1} (f[y][x] - f[y][x-1])^2; sum_{y >= 1} (f[y][x] - f[y-1][x])^2; H W
+ *   ag[b]           fp64: sum_{y < H-1, x < W-1} sqrt((dx^2 + dy^2) / 2), forward differences; the fp32 terms are summed
+ *                   exactly (as integers in units of 2^-24), so the value is bitwise reproducible and batch independent
+ * accumulate == 0: the call clears all four outputs itself (memset nodes when captured); != 0: it adds to them.  workspace:
+ * segmif_fusion_stats_workspace_bytes(B, H, W) bytes of 8-byte aligned scratch (0 = invalid sizes).  H, W >= 2, B >= 1,
+ * H W <= 2^30; nothing allocates or synchronises. */
+int64_t segmif_fusion_stats_workspace_bytes(int B, int H, int W);
+int segmif_fusion_stats_u8(const uint8_t* fused_rgb, const uint8_t* vis_rgb, const uint8_t* ir, int64_t* joint_fa, int64_t* joint_fv,
+                           int64_t* sums, double* ag, void* workspace, int B, int H, int W, int accumulate, void* stream);
+/* out[i] = palette[labels[i]] for labels int32 (n), palette uint8 (K, 3), 1 <= K <= 256; a label outside 0 .. K-1 gives
+ * (0, 0, 0) (util/util.py:21-29 leaves unmatched pixels zero) */
+int segmif_palette_u8(const int32_t* labels, const uint8_t* palette, uint8_t* out, int64_t n, int K, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * Training path (backward of the ops above; autograd in the reference: loss.backward() at

@@ -152,7 +152,10 @@ SIGNATURES = {
     "segmif_confusion_i32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "segmif_quantize_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p]),
     "segmif_dequantize_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p]),
-    "segmif_wgrad_workspace_size": (c_int64, [c_int64, c_int, c_int]),
+    "segmif_fusion_stats_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "segmif_fusion_stats_u8": (c_int, [c_void_p] * 8 + [c_int, c_int, c_int, c_int, c_void_p]),
+    "segmif_palette_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "segmif_wgrad_workspace_size":(c_int64, [c_int64, c_int, c_int]),
     "segmif_wgrad_f32": (c_int, [POINTER(SegmifIgemm), c_void_p, c_int, c_int64, c_void_p, c_int64, c_int64, c_void_p,
                                  c_void_p, c_int, c_void_p]),
     "segmif_wgrad_batched2_f32": (c_int, [POINTER(SegmifIgemm), c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64, c_int64,

@@ -1,0 +1,174 @@
+"""A data set end to end: uint8 frames in, fused uint8 images, label maps, mIoU and the fusion-quality scores out
+(test_fusion.py:83-126 followed by test_segmentation.py:160-195 and util/util.py:8-29, in memory and on the device).
+
+    python -m segmif_amd.evaluate --ir DIR --vis DIR --mask DIR [--label DIR] --out DIR [--backbone mit_b3]
+        [--seg-ckpt F] [--fusion-ckpt F] [--batch N] [--json F]
+
+reads the sorted file names of --vis (TaskFusion_dataset2.py:40-48) from every folder (.npy always, .png when PIL imports),
+and writes OUT/Fused/NAME, OUT/Seg/NAME (palette rendering) and a JSON of the results.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+from . import _lib
+from .pipeline import PairForward
+from .utils.fusion_metrics import MFNET_PALETTE, SCORE_NAMES, colorize, fusion_scores, fusion_stats
+from .utils.metrics import _dev, _stream, compute_results, confusion_matrix
+
+
+def _dequantize(u8_nhwc):
+    """(B, H, W, C) uint8 -> (B, C, H, W) fp32 = u / 255 (segmif_dequantize_u8: the loaders' float32 array / 255.0)"""
+    B, H, W, C = u8_nhwc.shape
+    out = torch.empty((B, C, H, W), device=u8_nhwc.device, dtype=torch.float32)
+    _lib.check(_lib.load().segmif_dequantize_u8(u8_nhwc.data_ptr(), out.data_ptr(), B, C, H * W, _stream()), "segmif_dequantize_u8")
+    return out
+
+
+def _nanmean(x):
+    x = x[~np.isnan(x)]
+    return float(x.mean()) if x.size else float("nan")
+
+
+class Evaluator:
+    """Accumulates the evaluation of (infrared, visible, mask) uint8 batches through PairForward(uint8_roundtrip=True,
+    return_u8=True): the min-max rescale of the fused image is per call = per batch, as the reference's is."""
+
+    def __init__(self, seg_net, fusion_net, n_class=9, graph=False):
+        self.pair = PairForward(seg_net, fusion_net, uint8_roundtrip=True, return_u8=True)
+        self.n_class = n_class
+        self.graph = graph
+        self._graph_shape = None
+        self._conf = None
+        self._scores = []
+
+    def update(self, ir_u8, vis_u8, mask_u8, label=None):
+        """ir_u8 (B, H, W), vis_u8 (B, H, W, 3), mask_u8 (B, H, W) uint8 and optionally label (B, H, W) int64, all on the device
+        -> (fused_u8 (B, H, W, 3) uint8, labels (B, H, W) int32) on the device.  With graph=True the first call captures the pair
+        forward for its batch shape and later calls of that shape replay it."""
+        ir_u8, vis_u8, mask_u8 = _dev(ir_u8, "ir_u8", torch.uint8), _dev(vis_u8, "vis_u8", torch.uint8), _dev(mask_u8, "mask_u8", torch.uint8)
+        if vis_u8.dim() != 4 or vis_u8.shape[3] != 3 or ir_u8.shape != vis_u8.shape[:3] or mask_u8.shape != vis_u8.shape[:3]:
+            raise RuntimeError(f"update expects ir (B, H, W), vis (B, H, W, 3), mask (B, H, W), got {tuple(ir_u8.shape)}, "
+                               f"{tuple(vis_u8.shape)}, {tuple(mask_u8.shape)}")
+        with torch.no_grad():
+            ir = _dequantize(ir_u8.unsqueeze(3))
+            vis = _dequantize(vis_u8)
+            mask3 = _dequantize(mask_u8.unsqueeze(3)).repeat(1, 3, 1, 1)  # the grey plane three times (test_fusion.py:90-99)
+            if self.graph:
+                if self._graph_shape is None:
+                    self.pair.capture(ir, vis, mask3)
+                    self._graph_shape = tuple(vis.shape)
+                if tuple(vis.shape) != self._graph_shape:
+                    raise RuntimeError(f"the captured graph serves batches of shape {self._graph_shape}, got {tuple(vis.shape)}")
+                _, labels, fused_u8 = self.pair.replay(ir, vis, mask3)
+                fused_u8, labels = fused_u8.clone(), labels.clone()  # (the graph's output buffers are overwritten by the next replay)
+            else:
+                _, labels, fused_u8 = self.pair.eager(ir, vis, mask3)
+            self._scores.append(fusion_stats(fused_u8, vis_u8, ir_u8))
+            if label is not None:
+                self._conf = confusion_matrix(labels, _dev(label, "label", torch.int64), self.n_class, out=self._conf)
+        return fused_u8, labels
+
+    def results(self):
+        """-> dict: every score of SCORE_NAMES as a per-image float64 array, 'mean' (name -> NaN-ignoring mean over the images)
+        and, when labels were given, 'precision' / 'recall' / 'iou' per class (compute_results) and 'mIoU' =
+        mean(nan_to_num(iou)), the figure test_segmentation.py prints for data that lack a class."""
+        per = [fusion_scores(s) for s in self._scores]
+        out = {k: np.concatenate([p[k] for p in per]) if per else np.zeros(0) for k in SCORE_NAMES}
+        out["mean"] = {k: _nanmean(out[k]) for k in SCORE_NAMES}
+        if self._conf is not None:
+            precision, recall, iou = compute_results(self._conf)
+            out.update(precision=precision, recall=recall, iou=iou, mIoU=float(np.mean(np.nan_to_num(iou))))
+        return out
+
+
+def _read(path):
+    if path.endswith(".npy"):
+        return np.load(path)
+    try:
+        from PIL import Image
+    except ImportError:
+        raise RuntimeError(f"{path}: reading images needs PIL; .npy arrays are always read")
+    return np.array(Image.open(path))
+
+
+def _write(path, arr):
+    if path.endswith(".npy"):
+        np.save(path, arr)
+        return
+    from PIL import Image
+    Image.fromarray(arr).save(path)
+
+
+def _names(folder):
+    return sorted(f for f in os.listdir(folder) if f.lower().endswith((".npy", ".png")))
+
+
+def _load_weights(net, path):
+    sd = torch.load(path, map_location="cpu")
+    net.load_state_dict(sd.get("state_dict", sd) if isinstance(sd, dict) else sd)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m segmif_amd.evaluate", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--ir", required=True)
+    ap.add_argument("--vis", required=True)
+    ap.add_argument("--mask", required=True)
+    ap.add_argument("--label")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--backbone", default="mit_b3")
+    ap.add_argument("--seg-ckpt")
+    ap.add_argument("--fusion-ckpt")
+    ap.add_argument("--batch", type=int, default=1)
+    ap.add_argument("--json")
+    args = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise RuntimeError("segmif_amd.evaluate needs the MI355X device (the HIP path has no CPU fallback)")
+    from .core import Fusion_Network3_ac, Network3
+
+    torch.manual_seed(0)
+    seg, fus = Network3(args.backbone, 9, pretrained=None), Fusion_Network3_ac()
+    for net, ckpt, what in ((seg, args.seg_ckpt, "segmentation"), (fus, args.fusion_ckpt, "fusion")):
+        if ckpt:
+            _load_weights(net, ckpt)
+        else:
+            print(f"[evaluate] no checkpoint for the {what} network: running on SEEDED RANDOM weights (torch.manual_seed(0))")
+    seg, fus = seg.cuda().eval(), fus.cuda().eval()
+    ev = Evaluator(seg, fus)
+    names = _names(args.vis)
+    if not names:
+        raise RuntimeError(f"no .npy / .png files in {args.vis}")
+    for sub in ("Fused", "Seg"):
+        os.makedirs(os.path.join(args.out, sub), exist_ok=True)
+
+    def batch_of(folder, chunk, dtype):
+        return torch.from_numpy(np.stack([np.asarray(_read(os.path.join(folder, n))) for n in chunk]).astype(dtype)).cuda()
+
+    for i in range(0, len(names), max(1, args.batch)):
+        chunk = names[i:i + max(1, args.batch)]
+        label = batch_of(args.label, chunk, np.int64) if args.label else None
+        fused_u8, labels = ev.update(batch_of(args.ir, chunk, np.uint8), batch_of(args.vis, chunk, np.uint8),
+                                     batch_of(args.mask, chunk, np.uint8), label)
+        fused_h, seg_h = fused_u8.cpu().numpy(), colorize(labels, MFNET_PALETTE).cpu().numpy()
+        for k, n in enumerate(chunk):
+            _write(os.path.join(args.out, "Fused", n), fused_h[k])
+            _write(os.path.join(args.out, "Seg", n), seg_h[k])
+            print(f"[evaluate] {n}")
+    res = ev.results()
+    doc = {"names": names, "seeded_weights": [w for w, c in (("seg", args.seg_ckpt), ("fusion", args.fusion_ckpt)) if not c]}
+    for k, v in res.items():
+        doc[k] = v.tolist() if isinstance(v, np.ndarray) else v
+    path = args.json or os.path.join(args.out, "results.json")
+    with open(path, "w") as f:
+        json.dump(doc, f, indent=1)
+    print("[evaluate] " + "  ".join(f"{k} {res['mean'][k]:.4f}" for k in SCORE_NAMES) + (f"  mIoU {res['mIoU']:.4f}" if "mIoU" in res else ""))
+    print(f"[evaluate] wrote {path}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -10,12 +10,18 @@ from .utils.metrics import dequantize_fused, quantize_fused
 
 
 class PairForward:
-    def __init__(self, seg_net, fusion_net, commute_resize=True, uint8_roundtrip=False):
+    def __init__(self, seg_net, fusion_net, commute_resize=True, uint8_roundtrip=False, return_u8=False):
         """uint8_roundtrip: the reference's scripted flow hands the fused image from test_fusion.py to
         test_segmentation.py through uint8 PNG files (uint8(255 x), global min-max rescale over the batch, uint8 -
         test_fusion.py:112-120; read back as float32 / 255 - TaskFusion_dataset2.py:84-88).  True reproduces that
         quantisation in memory: the segmentation net then sees exactly the pixels the script's PNGs hold
-        and the returned `fused` is that de-quantised image.  False (default) keeps the fp32 image."""
+        and the returned `fused` is that de-quantised image.  False (default) keeps the fp32 image.
+        return_u8 (needs uint8_roundtrip): every call returns a third value, the (B, H, W, 3) uint8 image quantize_fused
+        produced inside the body - the PNG pixels themselves (quantising the returned float again would truncate:
+        uint8(255 (u / 255)) is not u for every u, and the min-max rescale would run twice)."""
+        if return_u8 and not uint8_roundtrip:
+            raise ValueError("return_u8=True needs uint8_roundtrip=True (there is no uint8 image otherwise)")
+        self.return_u8 = return_u8
         self.seg, self.fus = seg_net, fusion_net
         self.commute_resize = commute_resize
         self.uint8_roundtrip = uint8_roundtrip
@@ -24,7 +30,7 @@ class PairForward:
         self._static = None
 
     def eager(self, ir, vis, mask3):
-        """-> (fused RGB (B,3,H,W), labels int32 (B,H,W)).  One guarded scope around the whole pair forward: the encoder's
+        """-> (fused RGB (B,3,H,W), labels int32 (B,H,W)) [, fused uint8 (B,H,W,3) with return_u8].  One guarded scope around the whole pair forward: the encoder's
         tall GEMMs and the fusion net's 3x3 convs run on f16x3 operands, their range slots - one per pair - are read back once
         at the end and exactly the pairs whose activations left the half's exponent range are computed again on the bf16x6
         kernels (a pair's result does not depend on what else is in the batch); (r5) pairs whose CrossPath context softmax
@@ -34,9 +40,12 @@ class PairForward:
 
     def _redo(self, out, idx, ir, vis, mask3):
         """Recompute the pairs `idx` (run_guarded has switched the f16x3 kernels off) and patch them into `out`."""
-        fused, labels = self._eager_body(ir.index_select(0, idx), vis.index_select(0, idx), mask3.index_select(0, idx))
+        part = self._eager_body(ir.index_select(0, idx), vis.index_select(0, idx), mask3.index_select(0, idx))
+        fused, labels = part[0], part[1]
         out[0].index_copy_(0, idx, fused)
         out[1].index_copy_(0, idx, labels)
+        if self.return_u8:
+            out[2].index_copy_(0, idx, part[2])
         return out
 
     def _eager_body(self, ir, vis, mask3):
@@ -48,8 +57,10 @@ class PairForward:
             y_f = self.fus(ir, vis, out0, out1)
         fused = fuse_to_rgb(vis, y_f)
         if self.uint8_roundtrip:
-            fused = dequantize_fused(quantize_fused(fused))
-        return fused, self.seg.predict_labels(fused, vis.shape[2:])
+            u8 = quantize_fused(fused)
+            fused = dequantize_fused(u8)
+        labels = self.seg.predict_labels(fused, vis.shape[2:])
+        return (fused, labels, u8) if self.return_u8 else (fused, labels)
 
     def capture(self, ir, vis, mask3, warmup=2):
         """Capture one step on static copies of the inputs; later calls to replay() copy new inputs
