@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SEGMIF_ABI_VERSION 3
+#define SEGMIF_ABI_VERSION 4
 #define SEGMIF_EINVAL (-22)
 #define SEGMIF_ENOSYS (-38)
 
@@ -454,9 +454,10 @@ int segmif_sr_attention_split16_f32(const float* q, const float* k, const float*
 
 /*
  * Linear ("efficient") cross attention context, step 1: per (batch, head) partial sums of
- * K^T V over row blocks.  kv: (B, N, 2*C), C = heads*d: k = cols [0,C), v = [C,2C).  heads = d = 8 (C = 64: the configuration
- * Fusion_Network3_ac instantiates) runs the tuned kernels; (r6) any other geometry with C <= 64, d <= 8 - the ablation networks'
- * dim-32 modules, core/model_fusion.py:363-429, :626-661 - a generic one with the same arithmetic.
+ * K^T V over row blocks.  kv: (B, N, 2*C), C = heads*d <= 64, d <= 8: k = cols [0,C), v = [C,2C).  heads = d = 8 (C = 64: the
+ * configuration Fusion_Network3_ac instantiates) has a partial-sum kernel with 16-byte loads; any other geometry - the ablation
+ * networks' dim-32 modules, core/model_fusion.py:363-429, :626-661 - one with scalar loads and the same arithmetic; step 2 is
+ * one kernel for all of them.
  * partial: (B, nblk, heads*d*d) DOUBLES with nblk = segmif_linattn_num_blocks(N) (fp32 inside a
  * 32-row run, fp64 across runs: the sum feeds a softmax).
  * Step 2 (segmif_linattn_fold_f32) reduces the partials in fp64, applies
@@ -475,21 +476,17 @@ int segmif_linattn_kvpartial_f32(const float* y, const float* wkv, double* parti
 int segmif_linattn_fold_f32(const double* partial, const float* wend, float* weff, int B, int nblk,
                             int heads, int d, int Nout, int ldw, int wofs, int ldweff, int kofs,
                             float scale, void* stream);
-/* (r6) Backward of segmif_linattn_fold_f32 (training path, heads = d = 8, C = 64): ktv (B, 8, 8, 8) = the per-head K^T V the fold
- * read (fp64; the sum of its partials), wend / wofs / kofs / scale as in the forward, dweff (B, Nout, ldweff) the gradient of the folded
- * weight.  Writes dktv (B, 8, 8, 8) fp64 - through the softmax over the k index - and, per image, this fold's share of d end_proj:
- * dwend_part[b][n][wofs + c] (pitch ldp floats; the caller sums over b).  Replaces the torch softmax / einsum / cat of the training
- * path's context fold (core/model_fusion.py:281-286, :316-326, :357-360 under autograd). */
+/* Backward of segmif_linattn_fold_f32 (training path) at any geometry the forward takes: C = heads * d <= 64, C % 16 == 0, d <= 8
+ * (Fusion_Network3_ac: 8 heads of 8; the ablation networks' interaction modules: dim 32 = 8 heads of 4).  ktv (B, heads, d, d) = the
+ * per-head K^T V the fold read (fp64; the sum of its partials), wend / wofs / kofs / scale as in the forward, dweff (B, Nout, ldweff)
+ * the gradient of the folded weight: its columns [kofs, kofs + C) and wend's [wofs, wofs + C) are the fold's.  Writes dktv
+ * (B, heads, d, d) fp64 - through the softmax over the k index - and, per image, this fold's share of d end_proj:
+ * dwend_part[b][n][wofs + c] (c < C, pitch ldp floats; the caller sums over b).  fp64 where the forward is.  EINVAL for a geometry
+ * outside the above, a pitch narrower than wofs + C / kofs + C, or fp64 pointers not 8-byte aligned.  Replaces the torch softmax /
+ * einsum / cat of the training path's context fold (core/model_fusion.py:281-286, :316-326, :357-360 under autograd). */
 int segmif_linattn_fold_bwd_f32(const double* ktv, const float* wend, int ldw, int wofs, const float* dweff, int ldweff, int kofs,
-                                float scale, double* dktv, float* dwend_part, int ldp, int B, int Nout, void* stream);
-/* Backward of segmif_linattn_fold_f32 at any geometry the forward takes: C = heads * d <= 64, C % 16 == 0, d <= 8 (the ablation
- * networks' interaction modules run at dim 32 = 8 heads of 4).  Arguments as segmif_linattn_fold_bwd_f32 plus heads, d: ktv / dktv
- * are (B, heads, d, d) fp64, dweff's columns [kofs, kofs + C) and wend's [wofs, wofs + C) are the fold's, and dwend_part[b][n][wofs + c]
- * (c < C, pitch ldp floats) receives this image's share of d end_proj (the caller sums over b).  fp64 where the forward is: the
- * softmax over the k index, dktv and dwend_part.  At heads = d = 8 it reproduces segmif_linattn_fold_bwd_f32. */
-int segmif_linattn_fold_bwd_generic_f32(const double* ktv, const float* wend, int ldw, int wofs, const float* dweff, int ldweff,
-                                        int kofs, float scale, double* dktv, float* dwend_part, int ldp, int B, int Nout, int heads,
-                                        int d, void* stream);
+                                float scale, double* dktv, float* dwend_part, int ldp, int B, int Nout, int heads, int d,
+                                void* stream);
 
 /*
  * CrossPath in inference without its 128-wide intermediates (csrc/crosspath.hip; core/model_fusion.py:329-361).

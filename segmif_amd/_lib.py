@@ -232,10 +232,8 @@ SIGNATURES = {
     "segmif_conv3x3_c1_f16x3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
                                       c_int, c_int, c_void_p, c_int, c_void_p]),
     "segmif_linattn_fold_bwd_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_int,
-                                          c_int, c_int, c_void_p]),
+                                          c_int, c_int, c_int, c_int, c_void_p]),
     "segmif_pointwise2_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_void_p]),
-    "segmif_linattn_fold_bwd_generic_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_float, c_void_p,
-                                                  c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "segmif_pointwise2_bwd_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int64,
                                         c_int, c_int, c_void_p]),
     "segmif_argmax_nhwc_i32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
@@ -268,7 +266,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: loud by design
         fn.restype = res
         fn.argtypes = args
-    if lib.segmif_abi_version() != 3:
+    if lib.segmif_abi_version() != 4:
         raise HipLibraryMissing("libsegmif_hip.so ABI version mismatch; rebuild")
     _lib = lib
     return lib

@@ -1021,97 +1021,21 @@ class JoinFn(torch.autograd.Function):
 
 
 class KvContextFn(torch.autograd.Function):
-    """ctx_raw[b][h] = K^T V per head with [K | V] = y @ wkv^T (no bias): the N-reduction of the linear
-    cross attention (core/model_fusion.py:281, 316-318).  Forward = fused projection + reduction kernel
-    (kv never hits HBM); backward recomputes kv with one GEMM."""
-
-    @staticmethod
-    def forward(ctx, y, wkv, sink=None, which=None):
-        """sink / which = (i, half): y is that half of a CrossProjFn output - its gradient is written through the ReLU mask."""
-        ctx.sink, ctx.which = sink, which
-        ctx.save_for_backward(y, wkv)
-        part = ops.linattn_kvpartial(y, wkv.contiguous())
-        B = y.shape[0]
-        return part.sum(1).view(B, 8, 8, 8)  # fp64: these logits feed a saturated softmax
-
-    @staticmethod
-    def backward(ctx, dctx):
-        y, wkv = ctx.saved_tensors
-        B, n, C = y.shape
-        kv = ops.linear(y, wkv.contiguous(), 2 * C)  # (B, n, 128)
-        dctx = dctx.float().contiguous()
-        # dk = v @ D1^T-form, dv = k @ D2^T-form with block-diagonal (B, 64, 64) weights [out][in]
-        # block-diagonal weights, one broadcast product each (not 8 slice assignments):
-        #   wk[b][h8+i][h8+j] = dctx[b][h][i][j]   dk[.., h8+i] = sum_j dctx[h][i][j] v[.., h8+j]
-        #   wv[b][h8+j][h8+i] = dctx[b][h][i][j]   dv[.., h8+j] = sum_i dctx[h][i][j] k[.., h8+i]
-        eye = torch.eye(8, device=y.device, dtype=torch.float32).view(1, 8, 1, 8, 1)
-        wk = (dctx.view(B, 8, 8, 1, 8) * eye).reshape(B, C, C)
-        wv = (dctx.transpose(2, 3).reshape(B, 8, 8, 1, 8) * eye).reshape(B, C, C)
-        dkv = torch.empty_like(kv)
-        ops.linear(kv[..., C:], wk, C, out=dkv[..., :C], batched_weight=True)
-        ops.linear(kv[..., :C], wv, C, out=dkv[..., C:], batched_weight=True)
-        dy = None
-        if ctx.needs_input_grad[0]:
-            sink = ctx.sink if ctx.sink is not None and ctx.sink.p is not None else None
-            if sink is not None:
-                out, mk = sink.slot(*ctx.which)
-                dy = ops.linear(dkv, wkv.t().contiguous(), C, out=out, mask=mk)
-                sink.done.add(tuple(ctx.which))
-            else:
-                dy = ops.linear(dkv, wkv.t().contiguous(), C)
-        dw = linear_wgrad(y, dkv, 2 * C) if ctx.needs_input_grad[1] else None
-        return dy, dw, None, None
-
-
-class ContextFoldFn(torch.autograd.Function):
-    """(r6) CrossPath's context fold on the training path as ONE node with HIP kernels on both sides:
-        Weff[b][n][0:64]   = sum_j softmax_i(ktv_a scale_a)[h][i][j] Wend[n][8h + j]        (the modality's own context: z half)
-        Weff[b][n][64:128] = sum_j softmax_i(ktv_3 scale_3)[h][i][j] Wend[n][64 + 8h + j]   (the segmentation context: v half)
-    so that cat(z_i, v_i) @ Wend^T == [y3 | u_i] @ Weff^T (core/model_fusion.py:281-286, :316-326, :357-360).  Forward = two
-    segmif_linattn_fold_f32 launches on the fp64 K^T V (one "partial" per image), backward = segmif_linattn_fold_bwd_f32 per half
-    + one column sum over the images for d end_proj - no torch softmax / einsum / cat."""
-
-    @staticmethod
-    def forward(ctx, ktv_a, ktv_3, wend, scale_a, scale_3):
-        B = ktv_a.shape[0]
-        ka, k3 = ktv_a.contiguous(), ktv_3.contiguous()
-        w = wend.contiguous()
-        weff = torch.empty((B, w.shape[0], 128), device=w.device, dtype=torch.float32)
-        ops.linattn_fold(ka.view(B, 1, 512), w, weff, wofs=0, kofs=0, scale=scale_a)
-        ops.linattn_fold(k3.view(B, 1, 512), w, weff, wofs=64, kofs=64, scale=scale_3)
-        ctx.save_for_backward(ka, k3, w)
-        ctx.scales = (float(scale_a), float(scale_3))
-        return weff
-
-    @staticmethod
-    def backward(ctx, dweff):
-        ka, k3, w = ctx.saved_tensors
-        B, Nout = ka.shape[0], w.shape[0]
-        dweff = dweff.contiguous()
-        dka, dk3 = torch.empty_like(ka), torch.empty_like(k3)
-        part = torch.empty((B, Nout, 128), device=w.device, dtype=torch.float32)
-        lib = _lib.load()
-        for k, dk, ofs, sc in ((ka, dka, 0, ctx.scales[0]), (k3, dk3, 64, ctx.scales[1])):
-            _lib.check(lib.segmif_linattn_fold_bwd_f32(k.data_ptr(), w.data_ptr(), 128, ofs, dweff.data_ptr(), 128, ofs, sc, dk.data_ptr(),
-                                                       part.data_ptr(), 128, B, Nout, _stream()), "segmif_linattn_fold_bwd_f32")
-        dw = colsum(part.view(B, Nout * 128)).view(Nout, 128) if ctx.needs_input_grad[2] else None
-        return dka, dk3, dw, None, None
-
-
-class KvContextGenericFn(torch.autograd.Function):
-    """KvContextFn at any head geometry with C = heads * d <= 64, d <= 8 (the ablation networks' dim-32 CrossPaths: 8 heads of 4):
-    forward = the kv projection (one GEMM, no bias) + the generic K^T V partial sums (csrc/linattn.hip), summed in fp64 per image
-    -> (B, heads, d, d); backward as KvContextFn's: kv recomputed by one GEMM, dk / dv through per-image block-diagonal weights,
-    the input gradient through the ReLU mask into CrossProjFn's buffer when a sink is given."""
+    """ctx_raw[b][h] = K^T V per head with [K | V] = y @ wkv^T (no bias): the N-reduction of the linear cross attention
+    (core/model_fusion.py:281, 316-318) at any head geometry with C = heads * d <= 64, d <= 8 -> (B, heads, d, d) fp64.
+    Forward: at 8 heads of 8 the fused projection + reduction kernel (kv never hits HBM), elsewhere one GEMM + the K^T V
+    partial sums (csrc/linattn.hip).  Backward: kv recomputed by one GEMM, dk / dv through per-image block-diagonal weights, the
+    input gradient through the ReLU mask into CrossProjFn's buffer when a sink is given."""
 
     @staticmethod
     def forward(ctx, y, wkv, heads, sink=None, which=None):
+        """sink / which = (i, half): y is that half of a CrossProjFn output - its gradient is written through the ReLU mask."""
         ctx.sink, ctx.which, ctx.heads = sink, which, heads
-        B, n, C = y.shape
-        d = C // heads
-        part = ops.linattn_partial(_gemm(y, wkv.detach().contiguous(), 2 * C), heads)
         ctx.save_for_backward(y, wkv)
-        return part.sum(1).view(B, heads, d, d)  # fp64: these logits feed a saturated softmax
+        B, n, C = y.shape
+        w = wkv.detach().contiguous()
+        part = ops.linattn_kvpartial(y, w) if ops.linattn_kv_fusable(C, heads) else ops.linattn_partial(_gemm(y, w, 2 * C), heads)
+        return part.sum(1).view(B, heads, C // heads, C // heads)  # fp64: these logits feed a saturated softmax
 
     @staticmethod
     def backward(ctx, dctx):
@@ -1120,9 +1044,16 @@ class KvContextGenericFn(torch.autograd.Function):
         h = ctx.heads
         d = C // h
         w = wkv.detach().contiguous()
-        kv = _gemm(y, w, 2 * C)
+        # The one place where the geometries launch different GEMM families.  Where the forward is the fused kernel, kv is
+        # recomputed on the fp32 tiles (ops.linear), as that kernel forms it on the fp32 matrix pipe; _gemm would route the
+        # full-resolution problem (2.4 M rows x 128 at 8 x 480 x 640) to the bf16x6 GEMM.  Elsewhere the recompute repeats the
+        # forward's own _gemm call.
+        kv = ops.linear(y, w, 2 * C) if ops.linattn_kv_fusable(C, h) else _gemm(y, w, 2 * C)  # (B, n, 2C)
         dctx = dctx.float().contiguous()
-        # wk[b][h d + i][h d + j] = dctx[b][h][i][j], wv[b][h d + j][h d + i] = dctx[b][h][i][j] (see KvContextFn)
+        # dk / dv as batched GEMMs against block-diagonal (B, C, C) weights [out][in], one broadcast product each (not h slice
+        # assignments):
+        #   wk[b][h d + i][h d + j] = dctx[b][h][i][j]   dk[.., h d + i] = sum_j dctx[h][i][j] v[.., h d + j]
+        #   wv[b][h d + j][h d + i] = dctx[b][h][i][j]   dv[.., h d + j] = sum_i dctx[h][i][j] k[.., h d + i]
         eye = torch.eye(h, device=y.device, dtype=torch.float32).view(1, h, 1, h, 1)
         wk = (dctx.view(B, h, d, 1, d) * eye).reshape(B, C, C)
         wv = (dctx.transpose(2, 3).reshape(B, h, d, 1, d) * eye).reshape(B, C, C)
@@ -1142,13 +1073,16 @@ class KvContextGenericFn(torch.autograd.Function):
         return dy, dw, None, None, None
 
 
-class ContextFoldGenericFn(torch.autograd.Function):
-    """ContextFoldFn at any head geometry, over one or two contexts: the q-th K^T V (B, heads, d, d) is folded into columns
-    [q C, (q + 1) C) of Weff (B, Nout, C * len(ktvs)) against the same columns of wend,
+class ContextFoldFn(torch.autograd.Function):
+    """CrossPath's context fold on the training path as ONE node with HIP kernels on both sides, over one or two contexts at any
+    head geometry: the q-th K^T V (B, heads, d, d) is folded into columns [q C, (q + 1) C) of Weff (B, Nout, C * len(ktvs))
+    against the same columns of wend,
         Weff[b][n][q C + h d + i] = sum_j softmax_i(ktv_q scale_q)[h][i][j] wend[n][q C + h d + j]
-    (CrossPath: the z half then the v half; CrossPath_S / _M: one half; an identity wend: the block-diagonal context itself).
-    Forward = segmif_linattn_fold_f32 per context, backward = segmif_linattn_fold_bwd_generic_f32 per context + one column sum
-    over the images for d wend."""
+    so that cat(z_i, v_i) @ Wend^T == [y3 | u_i] @ Weff^T (core/model_fusion.py:281-286, :316-326, :357-360; CrossPath: the
+    modality's own context = the z half, then the segmentation context = the v half; CrossPath_S / _M: one half; an identity wend:
+    the block-diagonal context itself).  Forward = segmif_linattn_fold_f32 per context on the fp64 K^T V (one "partial" per
+    image), backward = segmif_linattn_fold_bwd_f32 per context + one column sum over the images for d wend - no torch softmax /
+    einsum / cat."""
 
     @staticmethod
     def forward(ctx, wend, heads, scales, *ktvs):
@@ -1571,21 +1505,13 @@ def batched_linear2(xa, xb, w, bias=None, res=None):
     return BatchedLinear2Fn.apply(xa, xb, w, bias, res)
 
 
-def kv_context(y, wkv, sink=None, which=None):
-    return KvContextFn.apply(y, wkv, sink, which)
+def kv_context(y, wkv, heads, sink=None, which=None):
+    return KvContextFn.apply(y, wkv, heads, sink, which)
 
 
-def context_fold(ktv_a, ktv_3, wend, scale_a, scale_3):
-    return ContextFoldFn.apply(ktv_a, ktv_3, wend, scale_a, scale_3)
-
-
-def kv_context_generic(y, wkv, heads, sink=None, which=None):
-    return KvContextGenericFn.apply(y, wkv, heads, sink, which)
-
-
-def context_fold_generic(wend, heads, scales, *ktvs):
+def context_fold(wend, heads, scales, *ktvs):
     """-> Weff (B, Nout, C * len(ktvs)); ktvs: (B, heads, d, d) fp64 K^T V, folded in this order with their scales."""
-    return ContextFoldGenericFn.apply(wend, heads, tuple(scales), *ktvs)
+    return ContextFoldFn.apply(wend, heads, tuple(scales), *ktvs)
 
 
 def tail_one(s1, s2, weff1, weff2, b1, b2, x1, x2, sink=None, which=None):

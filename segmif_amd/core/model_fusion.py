@@ -203,7 +203,7 @@ class _LinearCrossAttention(nn.Module):
                                       "configuration SegMiF instantiates)")
 
     def _partial(self, lin, name, x):
-        if lin.bias is None:  # the configuration SegMiF uses: fused projection + reduction
+        if lin.bias is None and ops.linattn_kv_fusable(self.dim, self.num_heads):  # SegMiF's own: fused projection + reduction
             return ops.linattn_kvpartial(x, lin.weight, self.num_heads)
         kv = ops.linear(x, self._pk.get(name, lin.weight, ops.pack_weight), 2 * self.dim, bias=lin.bias)
         return ops.linattn_partial(kv, self.num_heads)
@@ -220,7 +220,7 @@ class _LinearCrossAttention(nn.Module):
         if lin.bias is not None:
             raise NotImplementedError("training through a linear cross attention with qkv_bias=True is not implemented "
                                       "(SegMiF builds these modules without bias)")
-        ctx = torch.softmax(ag.kv_context(x, lin.weight) * self.scale, dim=-2)  # (B, 8, 8, 8) fp64, [h][i][j]
+        ctx = torch.softmax(ag.kv_context(x, lin.weight, self.num_heads) * self.scale, dim=-2)  # (B, 8, 8, 8) fp64, [h][i][j]
         return _block_diag_batched(ctx).float()
 
     @staticmethod
@@ -292,52 +292,85 @@ class CrossAttention2(_LinearCrossAttention):
 
 
 class CrossPath(nn.Module):
+    """channel_proj x 3 -> ReLU -> chunk (y | u) -> linear cross attention(s) -> end_proj -> residual -> LayerNorm (ref :329-361),
+    at every geometry the linear-attention kernels take: dim = num_heads * d <= 64 a multiple of 16, d <= 8, reduction 1 - so
+    CrossPath(dim=32, num_heads=8), the ablation networks' interaction (ref :639), constructs like dim 64; any other dim raises
+    NotImplementedError.  `USE` names the attention(s) kept: 'v' CrossAttention on u, 'z' CrossAttention2 on y (the ablations
+    CrossPath_M / _S of .variants, ref :385-395, :419-429), 'zv' both.  Three token-level forms: forward_tokens (GEMM form),
+    forward_tokens_gram (inference, where gram_ok()) and forward_tokens_train (autograd)."""
+    USE = "zv"
+
     def __init__(self, dim, reduction=1, num_heads=8, norm_layer=nn.LayerNorm):
         super().__init__()
-        if reduction != 1 or dim // num_heads != 8 or num_heads != 8:
-            raise NotImplementedError("the linear-attention kernels are built for dim 64, 8 heads of 8 (the "
-                                      "only configuration SegMiF instantiates)")
-        self.dim = dim
+        if reduction != 1 or dim % num_heads or dim > 64 or dim // num_heads > 8 or dim % 16:
+            raise NotImplementedError("the linear-attention kernels take dim <= 64 (a multiple of 16), head size <= 8, reduction 1")
+        self.dim, self.num_heads = dim, num_heads
         self.channel_proj1 = nn.Linear(dim, dim * 2)
         self.channel_proj2 = nn.Linear(dim, dim * 2)
         self.channel_proj3 = nn.Linear(dim, dim * 2)
         self.act1 = nn.ReLU(inplace=True)
         self.act2 = nn.ReLU(inplace=True)
         self.act3 = nn.ReLU(inplace=True)
-        self.cross_attn = CrossAttention(dim, num_heads=num_heads)
-        self.cross_attn2 = CrossAttention2(dim, num_heads=num_heads)
-        self.end_proj1 = nn.Linear(dim * 2, dim)
-        self.end_proj2 = nn.Linear(dim * 2, dim)
+        if "v" in self.USE:
+            self.cross_attn = CrossAttention(dim, num_heads=num_heads)
+        if "z" in self.USE:
+            self.cross_attn2 = CrossAttention2(dim, num_heads=num_heads)
+        self.end_proj1 = nn.Linear(dim * len(self.USE), dim)
+        self.end_proj2 = nn.Linear(dim * len(self.USE), dim)
         self.norm1 = norm_layer(dim)
         self.norm2 = norm_layer(dim)
         self._pk = PackedCache()
 
-    def forward_tokens(self, x1, x2, seg, out1=None, out2=None):
-        """x1, x2, seg: (B, N, 64) rows views.  Returns LN(x_i + end_proj_i(cat(z_i, v_i))) written to out_i."""
+    def _eye(self, dev):
+        return self._pk.get_multi(f"eye:{dev}", (), lambda: torch.eye(self.dim, device=dev, dtype=torch.float32))
+
+    def _apply_ctx(self, q, part, scale):
+        """q @ softmax-context, materialised (the attention maps the *_showAttention classes hand back)."""
         C = self.dim
+        w = torch.empty((q.shape[0], C, C), device=q.device, dtype=torch.float32)
+        ops.linattn_fold(part, self._eye(q.device), w, wofs=0, kofs=0, scale=scale, heads=self.num_heads)
+        return ops.linear(q, w, C, batched_weight=True)
+
+    def forward_tokens(self, x1, x2, seg, out1=None, out2=None, want_maps=False):
+        """x1, x2, seg: (B, N, C) rows views.  Returns LN(x_i + end_proj_i(cat(z_i, v_i))) (one attention: the matching half)
+        written to out_i - optional rows views, channel slices of wider buffers; want_maps: also [v1, z1, z2, v2] ('zv')."""
+        C, h = self.dim, self.num_heads
         pk = self._pk
         proj = []
         for i, x in ((1, x1), (2, x2), (3, seg)):
             lin = getattr(self, f"channel_proj{i}")
             proj.append(ops.linear(x, pk.get(f"cp{i}", lin.weight, ops.pack_weight), 2 * C, bias=lin.bias,
                                    act=ops.ACT_RELU))
-        p1, p2, p3 = proj  # each (B, N, 128) = [y_i | u_i]   (ref :351-353)
-        part3 = self.cross_attn.context_partial(p3[..., C:])  # ctx3 from u3
-        part1 = self.cross_attn2.context_partial(1, p1[..., :C])  # ctx1 from y1
-        part2 = self.cross_attn2.context_partial(2, p2[..., :C])  # ctx2 from y2
+        p1, p2, p3 = proj  # each (B, N, 2C) = [y_i | u_i]   (ref :351-353)
+        part3 = self.cross_attn.context_partial(p3[..., C:]) if "v" in self.USE else None  # ctx3 from u3
+        parts = [self.cross_attn2.context_partial(i, p[..., :C]) if "z" in self.USE else None  # ctx_i from y_i
+                 for i, p in ((1, p1), (2, p2))]
         B = x1.shape[0]
         outs = []
-        for i, (x, p, part, o) in enumerate(((x1, p1, part1, out1), (x2, p2, part2, out2)), start=1):
-            end = getattr(self, f"end_proj{i}")
-            weff = torch.empty((B, C, 2 * C), device=x.device, dtype=torch.float32)
+        for i, (x, p, o) in enumerate(((x1, p1, out1), (x2, p2, out2))):
+            end, norm = getattr(self, f"end_proj{i + 1}"), getattr(self, f"norm{i + 1}")
+            weff = torch.empty((B, C, C * len(self.USE)), device=x.device, dtype=torch.float32)
             # cat(z_i, v_i) @ Wend^T  ==  [y3 | u_i] @ Weff^T with the contexts folded in (ref :357-360)
-            ops.linattn_fold(part, end.weight, weff, wofs=0, kofs=0, scale=self.cross_attn2.scale)
-            ops.linattn_fold(part3, end.weight, weff, wofs=C, kofs=C, scale=self.cross_attn.scale)
-            norm = getattr(self, f"norm{i}")
-            # LN(x + [y3 | u_i] @ Weff^T + b): GEMM, residual and LayerNorm in one kernel
-            outs.append(ops.linear(p3[..., :C], weff, C, bias=end.bias, res=x, x2=p[..., C:], batched_weight=True,
-                                   ln=(norm.weight, norm.bias, norm.eps), out=o))
-        return outs[0], outs[1]
+            k = 0
+            if "z" in self.USE:
+                ops.linattn_fold(parts[i], end.weight, weff, wofs=0, kofs=0, scale=self.cross_attn2.scale, heads=h)
+                k = C
+            if "v" in self.USE:
+                ops.linattn_fold(part3, end.weight, weff, wofs=k, kofs=k, scale=self.cross_attn.scale, heads=h)
+            src, src2 = (p[..., C:], None) if self.USE == "v" else (p3[..., :C], p[..., C:] if self.USE == "zv" else None)
+            ln = (norm.weight, norm.bias, norm.eps)
+            if ops.conv_ln_fusable(C):  # LN(x + [y3 | u_i] @ Weff^T + b): GEMM, residual and LayerNorm in one kernel
+                outs.append(ops.linear(src, weff, C, bias=end.bias, res=x, x2=src2, batched_weight=True, ln=ln, out=o))
+            else:
+                t = ops.linear(src, weff, C, bias=end.bias, res=x, x2=src2, batched_weight=True)
+                outs.append(ops.layernorm(t, *ln, out=t if o is None else o))
+        if not want_maps:
+            return outs[0], outs[1]
+        v1 = self._apply_ctx(p1[..., C:], part3, self.cross_attn.scale)
+        v2 = self._apply_ctx(p2[..., C:], part3, self.cross_attn.scale)
+        z1 = self._apply_ctx(p3[..., :C], parts[0], self.cross_attn2.scale)
+        z2 = self._apply_ctx(p3[..., :C], parts[1], self.cross_attn2.scale)
+        return outs[0], outs[1], [v1, z1, z2, v2]
 
     def forward_tokens_gram(self, x1, x2, seg, out1=None, out2=None, planes1=None, planes2=None, hw=None, planes_only=False):
         """forward_tokens without the 128-wide intermediates (csrc/crosspath.hip): K^T V = Wk (Y^T Y) Wv^T needs only the
@@ -376,40 +409,76 @@ class CrossPath(nn.Module):
         return outs[0], outs[1]
 
     def gram_ok(self):
-        return ops.crosspath_mode() == "gram" and self.cross_attn.kv3.bias is None and self.cross_attn2.kv1.bias is None \
-            and self.cross_attn2.kv2.bias is None \
+        """The Gram-form kernels are built for the one configuration SegMiF instantiates: dim 64, 8 heads of 8, both attentions."""
+        return ops.crosspath_mode() == "gram" and self.USE == "zv" and ops.linattn_kv_fusable(self.dim, self.num_heads) \
+            and self.cross_attn.kv3.bias is None and self.cross_attn2.kv1.bias is None and self.cross_attn2.kv2.bias is None \
             and ops.aligned16(*(p for p in self.parameters() if p.dim() == 1))  # 16-byte bias / LayerNorm loads in the tail
 
-    def forward_tokens_train(self, x1, x2, seg, out1=None, out2=None):
-        """autograd path: every node a HIP Function - the heavy contractions and, (r6), the 8x8 context softmaxes with their fold
+    def _ctx_map_train(self, q, ktv, scale):
+        """q @ softmax-context with gradient: a batched linear against the block-diagonal context (the fold against identity)."""
+        return ag.batched_linear(q, ag.context_fold(self._eye(q.device), self.num_heads, (scale,), ktv))
+
+    def forward_tokens_train(self, x1, x2, seg, out1=None, out2=None, want_maps=False):
+        """autograd path: every node a HIP Function - the heavy contractions and the d x d context softmaxes with their fold
         into end_proj (ag.context_fold; tensors of a few KB).  out_i: optional ag.Out placements of the two results.
-        (r4) Three nodes carry the full-resolution tensors - ag.cross_proj (the three channel_proj with every 64-channel half
-        its own output), ag.kv_context x 3, ag.tail_pair (both closing projections) - arranged so that each big tensor has one
-        consumer: no autograd accumulation passes, no zero-padded slice gradients."""
-        C = self.dim
+        Three nodes carry the full-resolution tensors - ag.cross_proj (the three channel_proj with every half its own output),
+        ag.kv_context per attention input, ag.tail_pair ('zv': both closing projections) or ag.tail_one (one attention) -
+        arranged so that each big tensor has one consumer: no autograd accumulation passes, no zero-padded slice gradients.
+        want_maps: also [v1, z1, z2, v2] with gradient (their sources then have two consumers each, so the ReLU-mask sink is
+        not used)."""
+        h = self.num_heads
         cp = [getattr(self, f"channel_proj{i}") for i in (1, 2, 3)]
         # (the sink lets the consumers' backward GEMMs write each half's gradient through its ReLU mask into cross_proj's buffer)
-        sink = ag.ProjSink()
+        sink = None if want_maps else ag.ProjSink()
         y1, u1, y2, u2, y3, u3, x1r, x2r = ag.cross_proj(x1, x2, seg, cp[0].weight, cp[0].bias, cp[1].weight, cp[1].bias,
                                                          cp[2].weight, cp[2].bias, sink)
-        # (r6) the 8 x 8 context softmaxes and their fold into end_proj are one autograd node with HIP kernels on both sides
-        # (ag.context_fold): no torch softmax / einsum / cat on the way
-        k3 = ag.kv_context(u3, self.cross_attn.kv3.weight, sink, (2, 1))
-        k1 = ag.kv_context(y1, self.cross_attn2.kv1.weight, sink, (0, 0))
-        k2 = ag.kv_context(y2, self.cross_attn2.kv2.weight, sink, (1, 0))
-        weffs = [ag.context_fold(k_i, k3, end.weight, self.cross_attn2.scale, self.cross_attn.scale)
-                 for end, k_i in ((self.end_proj1, k1), (self.end_proj2, k2))]
-        # x_i + [y3 | u_i] @ Weff_i^T + b_i for both modalities as one node (two-source GEMMs, residual in the epilogue)
-        t1, t2 = ag.tail_pair(y3, u1, u2, weffs[0], weffs[1], self.end_proj1.bias, self.end_proj2.bias, x1r, x2r, sink)
-        return (ag.layernorm(t1, self.norm1.weight, self.norm1.bias, self.norm1.eps, out=out1),
-                ag.layernorm(t2, self.norm2.weight, self.norm2.bias, self.norm2.eps, out=out2))
+        k = {}
+        if "v" in self.USE:
+            k[3] = ag.kv_context(u3, self.cross_attn.kv3.weight, h, sink, (2, 1))
+        if "z" in self.USE:
+            k[1] = ag.kv_context(y1, self.cross_attn2.kv1.weight, h, sink, (0, 0))
+            k[2] = ag.kv_context(y2, self.cross_attn2.kv2.weight, h, sink, (1, 0))
+        # the context softmaxes and their fold into end_proj are one autograd node with HIP kernels on both sides: no torch
+        # softmax / einsum / cat on the way
+        weffs = []
+        for i, end in ((1, self.end_proj1), (2, self.end_proj2)):
+            ktvs = [(k[i], self.cross_attn2.scale)] if "z" in self.USE else []
+            if "v" in self.USE:
+                ktvs.append((k[3], self.cross_attn.scale))
+            weffs.append(ag.context_fold(end.weight, h, [sc for _, sc in ktvs], *(kt for kt, _ in ktvs)))
+        b1, b2 = self.end_proj1.bias, self.end_proj2.bias
+        # x_i + [y3 | u_i] @ Weff_i^T + b_i for both modalities as one node (residual in the epilogue)
+        if self.USE == "zv":
+            t1, t2 = ag.tail_pair(y3, u1, u2, weffs[0], weffs[1], b1, b2, x1r, x2r, sink)
+        elif self.USE == "z":
+            t1, t2 = ag.tail_one(y3, None, weffs[0], weffs[1], b1, b2, x1r, x2r, sink, ((2, 0),))
+        else:
+            t1, t2 = ag.tail_one(u1, u2, weffs[0], weffs[1], b1, b2, x1r, x2r, sink, ((0, 1), (1, 1)))
+        r1 = ag.layernorm(t1, self.norm1.weight, self.norm1.bias, self.norm1.eps, out=out1)
+        r2 = ag.layernorm(t2, self.norm2.weight, self.norm2.bias, self.norm2.eps, out=out2)
+        if not want_maps:
+            return r1, r2
+        v1 = self._ctx_map_train(u1, k[3], self.cross_attn.scale)
+        z1 = self._ctx_map_train(y3, k[1], self.cross_attn2.scale)
+        z2 = self._ctx_map_train(y3, k[2], self.cross_attn2.scale)
+        v2 = self._ctx_map_train(u2, k[3], self.cross_attn.scale)
+        return r1, r2, [v1, z1, z2, v2]
+
+    def _train_path(self, *tensors):
+        """True when this call records gradients (the autograd path, in train and eval mode alike)."""
+        return wants_grad(self, *tensors)
+
+    def _forward(self, x1, x2, segfeature, want_maps=False):
+        require_device(x1, f"{type(self).__name__} input")
+        args = x1.contiguous(), x2.contiguous(), segfeature.contiguous()
+        if self._train_path(x1, x2, segfeature):
+            return self.forward_tokens_train(*args, want_maps=want_maps)
+        if self.gram_ok() and not want_maps:
+            return self.forward_tokens_gram(*args)
+        return self.forward_tokens(*args, want_maps=want_maps)
 
     def forward(self, x1, x2, segfeature):
-        require_device(x1, "CrossPath input")
-        if wants_grad(self, x1, x2, segfeature):
-            return self.forward_tokens_train(x1.contiguous(), x2.contiguous(), segfeature.contiguous())
-        fn = self.forward_tokens_gram if self.gram_ok() else self.forward_tokens
-        return fn(x1.contiguous(), x2.contiguous(), segfeature.contiguous())
+        return self._forward(x1, x2, segfeature)
 
 
 class FeatureFusionModule(nn.Module):

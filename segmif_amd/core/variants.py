@@ -25,7 +25,7 @@ import torch.nn as nn
 from .. import autograd as ag
 from .. import ops
 from ._util import PackedCache, init_reference_style, require_device, wants_grad
-from .model_fusion import DRDB, CrossAttention, CrossAttention2, FeatureFusionModule, WeTr
+from .model_fusion import DRDB, CrossPath, WeTr
 
 __all__ = ["Fusion_Network", "Network_fused", "CrossPath_M", "CrossPath_S", "FeatureFusionModule_SoAM", "FeatureFusionModule_MoAM",
            "CrossPath_showAttention", "FeatureFusionModule_ShowAttention", "Fusion_Network3", "Fusion_Network3_Con",
@@ -103,167 +103,35 @@ def _drdb_run(drdb, buf, out=None):
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------
-# interaction modules at any dim <= 64 (heads * d), tokens (B, N, C)
+# interaction modules at any dim <= 64 (heads * d), tokens (B, N, C): model_fusion.CrossPath with the attention(s) named by USE
 # ----------------------------------------------------------------------------------------------------------------------------------
-class _CrossPathGeneric(nn.Module):
-    """channel_proj x 3 -> ReLU -> chunk (y | u) -> linear cross attention(s) -> end_proj -> residual -> LayerNorm, with
-    the attention(s) named by `USE` ('v': CrossAttention on u, 'z': CrossAttention2 on y; ref :351-361, :385-395, :419-429)."""
-    USE = "zv"
+class _AblationPath(CrossPath):
+    """CrossPath under the ablation variants' policy: gradients wanted in eval mode raise."""
 
-    def __init__(self, dim, reduction=1, num_heads=8, norm_layer=nn.LayerNorm):
-        super().__init__()
-        if reduction != 1 or dim % num_heads or dim > 64 or dim // num_heads > 8 or dim % 16:
-            raise NotImplementedError("the generic linear-attention kernels take dim <= 64 (a multiple of 16), head size <= 8, reduction 1")
-        self.dim, self.num_heads = dim, num_heads
-        self.channel_proj1 = nn.Linear(dim, dim * 2)
-        self.channel_proj2 = nn.Linear(dim, dim * 2)
-        self.channel_proj3 = nn.Linear(dim, dim * 2)
-        self.act1 = nn.ReLU(inplace=True)
-        self.act2 = nn.ReLU(inplace=True)
-        self.act3 = nn.ReLU(inplace=True)
-        if "v" in self.USE:
-            self.cross_attn = CrossAttention(dim, num_heads=num_heads)
-        if "z" in self.USE:
-            self.cross_attn2 = CrossAttention2(dim, num_heads=num_heads)
-        self.end_proj1 = nn.Linear(dim * len(self.USE), dim)
-        self.end_proj2 = nn.Linear(dim * len(self.USE), dim)
-        self.norm1 = norm_layer(dim)
-        self.norm2 = norm_layer(dim)
-        self._pk = PackedCache()
-
-    def _kv_partial(self, lin, name, x):
-        kv = ops.linear(x, self._pk.get(name, lin.weight, ops.pack_weight), 2 * self.dim, bias=lin.bias)
-        return ops.linattn_partial(kv, self.num_heads)
-
-    def _apply_ctx(self, q, part, scale):
-        """q @ softmax-context, materialised (the attention maps the *_showAttention classes hand back)."""
-        C = self.dim
-        eye = self._pk.get_multi(f"eye:{q.device}", (), lambda: torch.eye(C, device=q.device, dtype=torch.float32))
-        w = torch.empty((q.shape[0], C, C), device=q.device, dtype=torch.float32)
-        ops.linattn_fold(part, eye, w, wofs=0, kofs=0, scale=scale, heads=self.num_heads)
-        return ops.linear(q, w, C, batched_weight=True)
-
-    def forward_tokens(self, x1, x2, seg, want_maps=False, outs=(None, None)):
-        """outs: optional (B, N, C) rows views (channel slices of wider buffers) receiving the two results."""
-        C, pk = self.dim, self._pk
-        p = []
-        for i, x in ((1, x1), (2, x2), (3, seg)):
-            lin = getattr(self, f"channel_proj{i}")
-            p.append(ops.linear(x, pk.get(f"cp{i}", lin.weight, ops.pack_weight), 2 * C, bias=lin.bias, act=RELU))
-        p1, p2, p3 = p  # [y_i | u_i]
-        B = x1.shape[0]
-        part3 = self._kv_partial(self.cross_attn.kv3, "kv3", p3[..., C:]) if "v" in self.USE else None
-        part = [self._kv_partial(getattr(self.cross_attn2, f"kv{i}"), f"kv{i}", pp[..., :C]) if "z" in self.USE else None
-                for i, pp in ((1, p1), (2, p2))]
-        res = []
-        for i, (x, pp) in enumerate(((x1, p1), (x2, p2))):
-            end, norm = getattr(self, f"end_proj{i + 1}"), getattr(self, f"norm{i + 1}")
-            weff = torch.empty((B, C, C * len(self.USE)), device=x.device, dtype=torch.float32)
-            # cat(z_i, v_i) @ Wend^T == [y3 | u_i] @ Weff^T with the contexts folded in; one attention only: the matching half
-            k = 0
-            if "z" in self.USE:
-                ops.linattn_fold(part[i], end.weight, weff, wofs=k, kofs=k, scale=self.cross_attn2.scale, heads=self.num_heads)
-                k += C
-            if "v" in self.USE:
-                ops.linattn_fold(part3, end.weight, weff, wofs=k, kofs=k, scale=self.cross_attn.scale, heads=self.num_heads)
-            if self.USE == "zv":
-                t = ops.linear(p3[..., :C], weff, C, bias=end.bias, res=x, x2=pp[..., C:], batched_weight=True)
-            elif self.USE == "z":
-                t = ops.linear(p3[..., :C], weff, C, bias=end.bias, res=x, batched_weight=True)
-            else:
-                t = ops.linear(pp[..., C:], weff, C, bias=end.bias, res=x, batched_weight=True)
-            res.append(ops.layernorm(t, norm.weight, norm.bias, norm.eps, out=t if outs[i] is None else outs[i]))
-        if not want_maps:
-            return res[0], res[1]
-        v1 = self._apply_ctx(p1[..., C:], part3, self.cross_attn.scale)
-        v2 = self._apply_ctx(p2[..., C:], part3, self.cross_attn.scale)
-        z1 = self._apply_ctx(p3[..., :C], part[0], self.cross_attn2.scale)
-        z2 = self._apply_ctx(p3[..., :C], part[1], self.cross_attn2.scale)
-        return res[0], res[1], [v1, z1, z2, v2]
-
-    def _ctx_map_train(self, q, ktv, scale):
-        """q @ softmax-context with gradient: a batched linear against the block-diagonal context (the fold against identity)."""
-        C = self.dim
-        eye = self._pk.get_multi(f"eye:{q.device}", (), lambda: torch.eye(C, device=q.device, dtype=torch.float32))
-        return ag.batched_linear(q, ag.context_fold_generic(eye, self.num_heads, (scale,), ktv))
-
-    def forward_tokens_train(self, x1, x2, seg, want_maps=False, outs=(None, None)):
-        """autograd path (CrossPath.forward_tokens_train at any head geometry, with the attention(s) named by USE): ag.cross_proj, the
-        generic K^T V context and fold nodes, then ag.tail_pair (zv) or ag.tail_one (one attention), LayerNorm into the optional
-        ag.Out placements outs.  want_maps: also [v1, z1, z2, v2] with gradient (their sources then have two consumers each, so
-        the ReLU-mask sink is not used)."""
-        h = self.num_heads
-        cp = [getattr(self, f"channel_proj{i}") for i in (1, 2, 3)]
-        sink = None if want_maps else ag.ProjSink()
-        y1, u1, y2, u2, y3, u3, x1r, x2r = ag.cross_proj(x1, x2, seg, cp[0].weight, cp[0].bias, cp[1].weight, cp[1].bias,
-                                                         cp[2].weight, cp[2].bias, sink)
-        k = {}
-        if "z" in self.USE:
-            k[1] = ag.kv_context_generic(y1, self.cross_attn2.kv1.weight, h, sink, (0, 0))
-            k[2] = ag.kv_context_generic(y2, self.cross_attn2.kv2.weight, h, sink, (1, 0))
-        if "v" in self.USE:
-            k[3] = ag.kv_context_generic(u3, self.cross_attn.kv3.weight, h, sink, (2, 1))
-        weffs = []
-        for i, end in ((1, self.end_proj1), (2, self.end_proj2)):
-            ktvs, scales = [], []
-            if "z" in self.USE:
-                ktvs.append(k[i])
-                scales.append(self.cross_attn2.scale)
-            if "v" in self.USE:
-                ktvs.append(k[3])
-                scales.append(self.cross_attn.scale)
-            weffs.append(ag.context_fold_generic(end.weight, h, scales, *ktvs))
-        b1, b2 = self.end_proj1.bias, self.end_proj2.bias
-        if self.USE == "zv":
-            t1, t2 = ag.tail_pair(y3, u1, u2, weffs[0], weffs[1], b1, b2, x1r, x2r, sink)
-        elif self.USE == "z":
-            t1, t2 = ag.tail_one(y3, None, weffs[0], weffs[1], b1, b2, x1r, x2r, sink, ((2, 0),))
-        else:
-            t1, t2 = ag.tail_one(u1, u2, weffs[0], weffs[1], b1, b2, x1r, x2r, sink, ((0, 1), (1, 1)))
-        r1 = ag.layernorm(t1, self.norm1.weight, self.norm1.bias, self.norm1.eps, out=outs[0])
-        r2 = ag.layernorm(t2, self.norm2.weight, self.norm2.bias, self.norm2.eps, out=outs[1])
-        if not want_maps:
-            return r1, r2
-        v1 = self._ctx_map_train(u1, k[3], self.cross_attn.scale)
-        z1 = self._ctx_map_train(y3, k[1], self.cross_attn2.scale)
-        z2 = self._ctx_map_train(y3, k[2], self.cross_attn2.scale)
-        v2 = self._ctx_map_train(u2, k[3], self.cross_attn.scale)
-        return r1, r2, [v1, z1, z2, v2]
-
-    def _forward(self, x1, x2, segfeature, want_maps=False):
-        require_device(x1, f"{type(self).__name__} input")
-        fn = self.forward_tokens_train if _train_path(self, x1, x2, segfeature) else self.forward_tokens
-        return fn(x1.contiguous(), x2.contiguous(), segfeature.contiguous(), want_maps=want_maps)
-
-    def forward(self, x1, x2, segfeature):
-        return self._forward(x1, x2, segfeature)
+    def _train_path(self, *tensors):
+        return _train_path(self, *tensors)
 
 
-class CrossPath_M(_CrossPathGeneric):
+class CrossPath_M(_AblationPath):
     """CrossAttention only: out_i = LN(x_i + end_proj_i(u_i @ ctx3))  (ref :363-395)."""
     USE = "v"
 
 
-class CrossPath_S(_CrossPathGeneric):
+class CrossPath_S(_AblationPath):
     """CrossAttention2 only: out_i = LN(x_i + end_proj_i(y3 @ ctx_i))  (ref :397-429)."""
     USE = "z"
 
 
-class CrossPath_showAttention(_CrossPathGeneric):
+class CrossPath_showAttention(_AblationPath):
     """CrossPath that also returns its four attention results [v1, z1, z2, v2]  (ref :538-572)."""
-    USE = "zv"
 
     def forward(self, x1, x2, segfeature):
         return self._forward(x1, x2, segfeature, want_maps=True)
 
 
-class _CrossPathAny(_CrossPathGeneric):
-    """The reference's CrossPath at a dim the tuned kernels are not built for (dim 32 inside Fusion_Network3, ref :639)."""
-    USE = "zv"
-
-
 class _FfmGeneric(nn.Module):
-    PATH = _CrossPathAny
+    """FeatureFusionModule of the ablation networks (dim 32) - and, by PATH, its one-attention / attention-showing variants."""
+    PATH = CrossPath
 
     def __init__(self, dim, reduction=1, num_heads=8, norm_layer=nn.BatchNorm2d):
         super().__init__()
@@ -276,11 +144,10 @@ class _FfmGeneric(nn.Module):
         B, H, W, C = x1.shape
         if _train_path(self, x1, x2, seg):
             tok = lambda t: t.reshape(B, H * W, t.shape[-1])
-            r1, r2 = self.cross.forward_tokens_train(tok(x1), tok(x2), tok(seg), outs=(_out_tokens(out1, B, H * W),
-                                                                                        _out_tokens(out2, B, H * W)))
+            r1, r2 = self.cross.forward_tokens_train(tok(x1), tok(x2), tok(seg), _out_tokens(out1, B, H * W), _out_tokens(out2, B, H * W))
             return r1.view(B, H, W, C), r2.view(B, H, W, C)
         tok = lambda t: None if t is None else _tokens(t, B, H * W)
-        r = self.cross.forward_tokens(tok(x1), tok(x2), tok(seg), outs=(tok(out1), tok(out2)))
+        r = self.cross.forward_tokens(tok(x1), tok(x2), tok(seg), tok(out1), tok(out2))
         return (out1 if out1 is not None else r[0].view(B, H, W, C)), (out2 if out2 is not None else r[1].view(B, H, W, C))
 
     def _nchw(self, x1, x2, segfeature):
@@ -315,11 +182,6 @@ class FeatureFusionModule_ShowAttention(_FfmGeneric):
         a, b = ops.to_nhwc(x1), ops.to_nhwc(x2)
         r1, r2 = self.forward_nhwc(a, b, ops.to_nhwc(segfeature))
         return ops.as_nchw(r1), ops.as_nchw(r2), [ops.as_nchw(a).clone(), ops.as_nchw(b).clone()]
-
-
-def _ffm(dim):
-    """FeatureFusionModule at `dim`: the tuned Gram-form module at 64, the generic composition elsewhere (same state_dict keys)."""
-    return FeatureFusionModule(dim) if dim == 64 else _FfmGeneric(dim)
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------
@@ -406,7 +268,7 @@ class _FusionBase(_Convs):
 class Fusion_Network3(_FusionBase):
     """The 32-channel interaction network val_performance.py:565 builds (ref :626-660): as Fusion_Network3_ac with 32-channel
     blocks and without conv22."""
-    FFM = staticmethod(_ffm)
+    FFM = _FfmGeneric
 
     def __init__(self):
         super().__init__()
@@ -416,7 +278,7 @@ class Fusion_Network3(_FusionBase):
         self.relu = nn.PReLU()
         self.ffm = self.FFM(32)
         if self.HAS_FFM2:
-            self.ffm2 = _ffm(32)  # present in checkpoints, never used by forward (as in Fusion_Network3_ac)
+            self.ffm2 = _FfmGeneric(32)  # present in checkpoints, never used by forward (as in Fusion_Network3_ac)
         self.conv3 = nn.Conv2d(64, 32, 1, padding=0)
         self.conv4 = nn.Conv2d(128, 32, 1, padding=0)
 

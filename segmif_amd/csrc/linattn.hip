@@ -29,6 +29,18 @@ namespace {
 constexpr int LA_ROWS = 1024;  // rows per block
 constexpr int LA_CHUNK = 32;  // rows per LDS chunk / fp32 accumulation run
 
+// ctx[h][i][j] (fp64, in LDS) -> softmax over i of column (h, j), in place: one thread per column (dim = -2 of the reference).
+__device__ inline void softmax_over_i(double* ctx, int hh, int j, int d) {
+  double mx = -1e300, sum = 0.0;
+  for (int i = 0; i < d; ++i) mx = fmax(mx, ctx[(hh * d + i) * d + j]);
+  for (int i = 0; i < d; ++i) {
+    const double ev = exp(ctx[(hh * d + i) * d + j] - mx);
+    ctx[(hh * d + i) * d + j] = ev;
+    sum += ev;
+  }
+  for (int i = 0; i < d; ++i) ctx[(hh * d + i) * d + j] /= sum;
+}
+
 // heads*d == 64, d == 8: 512 (h, i, j) entries, two per thread.
 __global__ __launch_bounds__(256) void linattn_partial_kernel(const float* __restrict__ kv, double* __restrict__ partial,
                                                               long long N, int ldkv, int nblk) {
@@ -66,43 +78,36 @@ __global__ __launch_bounds__(256) void linattn_partial_kernel(const float* __res
   dst[1] = acc1;
 }
 
+// Step 2 at every admitted geometry (C = heads d <= 64, d <= 8: E = C d <= 512 entries e = (h d + i) d + j).  The row-block partials
+// are summed in fp64 by four slices in a fixed order, part[4][E] then ((p0 + p1) + p2) + p3: deterministic, and 300 partials per
+// image at 480 x 640 are four chains of 75, not one of 300.
 __global__ __launch_bounds__(1024) void linattn_fold_kernel(const double* __restrict__ partial,
                                                             const float* __restrict__ wend, float* __restrict__ weff,
                                                             int nblk, int Nout, int ldw, int wofs, int ldweff, int kofs,
-                                                            float scale) {
+                                                            float scale, int heads, int d) {
   __shared__ double part[4][512];
   __shared__ double ctx[512];  // [h][i][j]
   const int tid = threadIdx.x, b = blockIdx.x;
+  const int C = heads * d, E = C * d;
   const int e = tid & 255, slice = tid >> 8;
-  const double* p = partial + (long long)b * nblk * 512;
+  const bool own0 = e < E, own1 = e + 256 < E;
+  const double* p = partial + (long long)b * nblk * E;
   double a0 = 0.0, a1 = 0.0;
   for (int k = slice; k < nblk; k += 4) {  // fixed order per slice: deterministic
-    a0 += p[(long long)k * 512 + e];
-    a1 += p[(long long)k * 512 + 256 + e];
+    if (own0) a0 += p[(long long)k * E + e];
+    if (own1) a1 += p[(long long)k * E + 256 + e];
   }
   part[slice][e] = a0;
   part[slice][256 + e] = a1;
   __syncthreads();
-  if (tid < 512) ctx[tid] = (((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid]) * (double)scale;
+  if (tid < E) ctx[tid] = (((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid]) * (double)scale;
   __syncthreads();
-  if (tid < 64) {  // one (h, j) column per thread: softmax over i (dim = -2)
-    const int hh = tid >> 3, j = tid & 7;
-    double mx = -1e300;
-    for (int i = 0; i < 8; ++i) mx = fmax(mx, ctx[hh * 64 + i * 8 + j]);
-    double ev[8], sum = 0.0;
-    for (int i = 0; i < 8; ++i) {
-      ev[i] = exp(ctx[hh * 64 + i * 8 + j] - mx);
-      sum += ev[i];
-    }
-    for (int i = 0; i < 8; ++i) ctx[hh * 64 + i * 8 + j] = ev[i] / sum;
-  }
+  if (tid < C) softmax_over_i(ctx, tid / d, tid % d, d);
   __syncthreads();
-  // Weff[b][n][kofs + c] for c = h*8 + i in [0, 64)
-  for (int o = tid; o < Nout * 64; o += 1024) {
-    const int n = o >> 6, c = o & 63, hh = c >> 3, i = c & 7;
+  for (int o = tid; o < Nout * C; o += 1024) {  // Weff[b][n][kofs + h d + i] = sum_j ctx[h][i][j] Wend[n][wofs + h d + j]
+    const int n = o / C, c = o % C, hh = c / d;
     float acc = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc = fmaf((float)ctx[hh * 64 + i * 8 + j], wend[(long long)n * ldw + wofs + hh * 8 + j], acc);
+    for (int j = 0; j < d; ++j) acc = fmaf((float)ctx[c * d + j], wend[(long long)n * ldw + wofs + hh * d + j], acc);
     weff[((long long)b * Nout + n) * ldweff + kofs + c] = acc;
   }
 }
@@ -209,10 +214,10 @@ __global__ __launch_bounds__(256) void linattn_kvpartial_kernel(const float* __r
 }
 
 // ---------------------------------------------------------------------------------------------
-// (r6) Any head geometry with heads * d <= 64 and d <= 8 - the reference's ablation networks build their interaction
-// modules at dim 32 (8 heads of 4: model_fusion.py:639-640, :832, :867).  Same arithmetic as the two kernels above (fp32 inside a
-// 32-row run, fp64 across runs and blocks, fixed order), entry e = (h d + i) d + j owned by thread e (and e + 256): these
-// problems are small (32-channel maps), so one generic kernel instead of one instantiation per geometry.
+// Step 1 at any other head geometry with heads * d <= 64 and d <= 8 - the reference's ablation networks build their interaction
+// modules at dim 32 (8 heads of 4: model_fusion.py:639-640, :832, :867).  Same arithmetic as linattn_partial_kernel (fp32 inside a
+// 32-row run, fp64 across runs, fixed order), entry e = (h d + i) d + j owned by thread e (and e + 256), scalar loads at any width
+// where the 8 x 8 kernel has 16-byte loads and a conflict-free pitch at 128 columns: segmif_linattn_partial_f32 chooses.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void linattn_partial_generic_kernel(const float* __restrict__ kv, double* __restrict__ partial,
                                                                       long long N, int ldkv, int nblk, int heads, int d) {
@@ -253,105 +258,25 @@ __global__ __launch_bounds__(256) void linattn_partial_generic_kernel(const floa
     if (tid + 256 * u < E) dst[tid + 256 * u] = acc[u];
 }
 
-__global__ __launch_bounds__(512) void linattn_fold_generic_kernel(const double* __restrict__ partial, const float* __restrict__ wend,
-                                                                   float* __restrict__ weff, int nblk, int Nout, int ldw, int wofs,
-                                                                   int ldweff, int kofs, float scale, int heads, int d) {
-  __shared__ double ctx[512];  // [h][i][j]
-  const int tid = threadIdx.x, b = blockIdx.x;
-  const int C = heads * d, E = C * d;
-  if (tid < E) {
-    const double* p = partial + (long long)b * nblk * E + tid;
-    double a = 0.0;
-    for (int k = 0; k < nblk; ++k) a += p[(long long)k * E];  // fixed order: deterministic
-    ctx[tid] = a * (double)scale;
-  }
-  __syncthreads();
-  if (tid < C) {  // one (h, j) column per thread: softmax over i (dim = -2)
-    const int hh = tid / d, j = tid % d;
-    double mx = -1e300, ev[8], sum = 0.0;
-    for (int i = 0; i < d; ++i) mx = fmax(mx, ctx[(hh * d + i) * d + j]);
-    for (int i = 0; i < d; ++i) {
-      ev[i] = exp(ctx[(hh * d + i) * d + j] - mx);
-      sum += ev[i];
-    }
-    for (int i = 0; i < d; ++i) ctx[(hh * d + i) * d + j] = ev[i] / sum;
-  }
-  __syncthreads();
-  for (int o = tid; o < Nout * C; o += 512) {  // Weff[b][n][kofs + h d + i] = sum_j ctx[h][i][j] Wend[n][wofs + h d + j]
-    const int n = o / C, c = o % C, hh = c / d;
-    float acc = 0.f;
-    for (int j = 0; j < d; ++j) acc = fmaf((float)ctx[c * d + j], wend[(long long)n * ldw + wofs + hh * d + j], acc);
-    weff[((long long)b * Nout + n) * ldweff + kofs + c] = acc;
-  }
-}
-
-// (r6) Backward of segmif_linattn_fold_f32 for the training path (heads = d = 8): given ktv = K^T V per head (fp64, [h][i][j]), the
-// end_proj weight and dWeff, one workgroup per image forms
-//     ctx = softmax_i(ktv scale);   dctx[h][i][j] = sum_n dWeff[n][kofs + 8h + i] Wend[n][wofs + 8h + j]
-//     dktv[h][i][j] = scale ctx_ij (dctx_ij - sum_i' ctx_i'j dctx_i'j)                       (softmax over i = dim -2)
-//     dWend_part[b][n][wofs + 8h + j] = sum_i dWeff[n][kofs + 8h + i] ctx[h][i][j]           (summed over images by the caller)
-// - the softmax / einsum / cat that CrossPath's training path ran as torch ops on (B, 8, 8, 8) tensors (core/model_fusion.py:281-286,
+// Backward of segmif_linattn_fold_f32 at every geometry the forward takes (C = heads d <= 64, d <= 8): given ktv = K^T V per head
+// (fp64, [h][i][j]), the end_proj weight and dWeff, one workgroup per image (ktv is at most 512 doubles, entry e = (h d + i) d + j
+// owned by thread e) forms
+//     ctx = softmax_i(ktv scale);   dctx[h][i][j] = sum_n dWeff[n][kofs + h d + i] Wend[n][wofs + h d + j]
+//     dktv[h][i][j] = scale ctx_ij (dctx_ij - sum_i' ctx_i'j dctx_i'j)                         (softmax over i = dim -2)
+//     dWend_part[b][n][wofs + h d + j] = sum_i dWeff[n][kofs + h d + i] ctx[h][i][j]           (summed over images by the caller)
+// - the softmax / einsum / cat that CrossPath's training path ran as torch ops on (B, heads, d, d) tensors (core/model_fusion.py:281-286,
 // :316-326, :357-360 under autograd).  fp64 where the forward is.
 __global__ __launch_bounds__(512) void linattn_fold_bwd_kernel(const double* __restrict__ ktv, const float* __restrict__ wend, int ldw,
                                                                int wofs, const float* __restrict__ dweff, int ldweff, int kofs,
                                                                float scale, double* __restrict__ dktv, float* __restrict__ dwend_part,
-                                                               int ldp, int Nout) {
-  __shared__ double ctx[512], dctx[512];
-  const int tid = threadIdx.x, b = blockIdx.x;
-  const int hh = tid >> 6, i = (tid >> 3) & 7, j = tid & 7;
-  ctx[tid] = ktv[(long long)b * 512 + tid] * (double)scale;
-  __syncthreads();
-  if (tid < 64) {  // one (h, j) column per thread: softmax over i
-    const int h2 = tid >> 3, j2 = tid & 7;
-    double mx = -1e300, ev[8], sum = 0.0;
-    for (int q = 0; q < 8; ++q) mx = fmax(mx, ctx[h2 * 64 + q * 8 + j2]);
-    for (int q = 0; q < 8; ++q) {
-      ev[q] = exp(ctx[h2 * 64 + q * 8 + j2] - mx);
-      sum += ev[q];
-    }
-    for (int q = 0; q < 8; ++q) ctx[h2 * 64 + q * 8 + j2] = ev[q] / sum;
-  }
-  const float* dw = dweff + (long long)b * Nout * ldweff + kofs;
-  double acc = 0.0;
-  for (int n = 0; n < Nout; ++n) acc += (double)dw[(long long)n * ldweff + hh * 8 + i] * (double)wend[(long long)n * ldw + wofs + hh * 8 + j];
-  dctx[tid] = acc;
-  __syncthreads();
-  double dot = 0.0;
-  for (int q = 0; q < 8; ++q) dot += ctx[hh * 64 + q * 8 + j] * dctx[hh * 64 + q * 8 + j];
-  dktv[(long long)b * 512 + tid] = (double)scale * ctx[tid] * (dctx[tid] - dot);
-  float* dp = dwend_part + (long long)b * Nout * ldp + wofs;
-  for (int o = tid; o < Nout * 64; o += 512) {
-    const int n = o >> 6, c = o & 63, h2 = c >> 3, j2 = c & 7;
-    double a = 0.0;
-    for (int q = 0; q < 8; ++q) a += (double)dw[(long long)n * ldweff + h2 * 8 + q] * ctx[h2 * 64 + q * 8 + j2];
-    dp[(long long)n * ldp + c] = (float)a;
-  }
-}
-
-// Backward of segmif_linattn_fold_f32 at any geometry the forward takes (C = heads d <= 64, d <= 8): the dim-32 interaction modules of
-// the ablation networks train through it (8 heads of 4).  Same formulas and the same fp64 arithmetic as the kernel above, entry
-// e = (h d + i) d + j owned by thread e; one workgroup per image (ktv is at most 512 doubles).
-__global__ __launch_bounds__(512) void linattn_fold_bwd_generic_kernel(const double* __restrict__ ktv, const float* __restrict__ wend,
-                                                                       int ldw, int wofs, const float* __restrict__ dweff, int ldweff,
-                                                                       int kofs, float scale, double* __restrict__ dktv,
-                                                                       float* __restrict__ dwend_part, int ldp, int Nout, int heads,
-                                                                       int d) {
+                                                               int ldp, int Nout, int heads, int d) {
   __shared__ double ctx[512], dctx[512];
   const int tid = threadIdx.x, b = blockIdx.x;
   const int C = heads * d, E = C * d;
   const int c = tid / d, j = tid % d, hh = c / d;  // tid = (h d + i) d + j, c = h d + i
   if (tid < E) ctx[tid] = ktv[(long long)b * E + tid] * (double)scale;
   __syncthreads();
-  if (tid < C) {  // one (h, j) column per thread: softmax over i
-    const int h2 = tid / d, j2 = tid % d;
-    double mx = -1e300, ev[8], sum = 0.0;
-    for (int q = 0; q < d; ++q) mx = fmax(mx, ctx[(h2 * d + q) * d + j2]);
-    for (int q = 0; q < d; ++q) {
-      ev[q] = exp(ctx[(h2 * d + q) * d + j2] - mx);
-      sum += ev[q];
-    }
-    for (int q = 0; q < d; ++q) ctx[(h2 * d + q) * d + j2] = ev[q] / sum;
-  }
+  if (tid < C) softmax_over_i(ctx, tid / d, tid % d, d);
   const float* dw = dweff + (long long)b * Nout * ldweff + kofs;
   if (tid < E) {
     double acc = 0.0;
@@ -365,7 +290,7 @@ __global__ __launch_bounds__(512) void linattn_fold_bwd_generic_kernel(const dou
     dktv[(long long)b * E + tid] = (double)scale * ctx[tid] * (dctx[tid] - dot);
   }
   float* dp = dwend_part + (long long)b * Nout * ldp + wofs;
-  for (int o = tid; o < Nout * C; o += 512) {  // dWend_part[n][wofs + h d + j] = sum_i dWeff[n][kofs + h d + i] ctx[h][i][j]
+  for (int o = tid; o < Nout * C; o += 512) {
     const int n = o / C, cc = o % C, h2 = cc / d, j2 = cc % d;
     double a = 0.0;
     for (int q = 0; q < d; ++q) a += (double)dw[(long long)n * ldweff + h2 * d + q] * ctx[(h2 * d + q) * d + j2];
@@ -397,13 +322,8 @@ extern "C" int segmif_linattn_fold_f32(const double* partial, const float* wend,
                                        int heads, int d, int Nout, int ldw, int wofs, int ldweff, int kofs, float scale,
                                        void* stream) {
   if (!partial || !wend || !weff || B <= 0 || nblk <= 0 || heads <= 0 || d <= 0 || d > 8 || heads * d > 64 || Nout <= 0) return SEGMIF_EINVAL;
-  if (heads != 8 || d != 8) {
-    hipLaunchKernelGGL(linattn_fold_generic_kernel, dim3((unsigned)B), dim3(512), 0, (hipStream_t)stream, partial, wend, weff, nblk,
-                       Nout, ldw, wofs, ldweff, kofs, scale, heads, d);
-    return (int)hipGetLastError();
-  }
   hipLaunchKernelGGL(linattn_fold_kernel, dim3((unsigned)B), dim3(1024), 0, (hipStream_t)stream,
-                     partial, wend, weff, nblk, Nout, ldw, wofs, ldweff, kofs, scale);
+                     partial, wend, weff, nblk, Nout, ldw, wofs, ldweff, kofs, scale, heads, d);
   return (int)hipGetLastError();
 }
 
@@ -428,24 +348,12 @@ extern "C" int segmif_linattn_kvpartial_f32(const float* y, const float* wkv, do
 
 extern "C" int segmif_linattn_fold_bwd_f32(const double* ktv, const float* wend, int ldw, int wofs, const float* dweff, int ldweff,
                                            int kofs, float scale, double* dktv, float* dwend_part, int ldp, int B, int Nout,
-                                           void* stream) {
-  if (!ktv || !wend || !dweff || !dktv || !dwend_part || B <= 0 || Nout <= 0 || wofs < 0 || kofs < 0 || ldw < wofs + 64 ||
-      ldweff < kofs + 64 || ldp < wofs + 64)
-    return SEGMIF_EINVAL;
-  if (((uintptr_t)ktv | (uintptr_t)dktv) & 7) return SEGMIF_EINVAL;
-  hipLaunchKernelGGL(linattn_fold_bwd_kernel, dim3((unsigned)B), dim3(512), 0, (hipStream_t)stream, ktv, wend, ldw, wofs, dweff, ldweff,
-                     kofs, scale, dktv, dwend_part, ldp, Nout);
-  return (int)hipGetLastError();
-}
-
-extern "C" int segmif_linattn_fold_bwd_generic_f32(const double* ktv, const float* wend, int ldw, int wofs, const float* dweff,
-                                                   int ldweff, int kofs, float scale, double* dktv, float* dwend_part, int ldp, int B,
-                                                   int Nout, int heads, int d, void* stream) {
+                                           int heads, int d, void* stream) {
   if (!ktv || !wend || !dweff || !dktv || !dwend_part || B <= 0 || Nout <= 0 || heads <= 0 || d <= 0 || d > 8) return SEGMIF_EINVAL;
   const int C = heads * d;
   if (C > 64 || (C & 15) || wofs < 0 || kofs < 0 || ldw < wofs + C || ldweff < kofs + C || ldp < wofs + C) return SEGMIF_EINVAL;
   if (((uintptr_t)ktv | (uintptr_t)dktv) & 7) return SEGMIF_EINVAL;
-  hipLaunchKernelGGL(linattn_fold_bwd_generic_kernel, dim3((unsigned)B), dim3(512), 0, (hipStream_t)stream, ktv, wend, ldw, wofs, dweff,
-                     ldweff, kofs, scale, dktv, dwend_part, ldp, Nout, heads, d);
+  hipLaunchKernelGGL(linattn_fold_bwd_kernel, dim3((unsigned)B), dim3(512), 0, (hipStream_t)stream, ktv, wend, ldw, wofs, dweff, ldweff,
+                     kofs, scale, dktv, dwend_part, ldp, Nout, heads, d);
   return (int)hipGetLastError();
 }

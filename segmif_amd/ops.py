@@ -1524,6 +1524,12 @@ def linattn_partial(kv, heads=8):
     return part
 
 
+def linattn_kv_fusable(C, heads):
+    """The one geometry linattn_kvpartial (kv projection + K^T V reduction in one kernel) is built for: C = 64, 8 heads of 8.
+    Every caller that chooses between it and GEMM + linattn_partial asks here."""
+    return C == 64 and heads == 8
+
+
 def linattn_kvpartial(y, wkv, heads=8):
     """Fused kv projection (no bias) + K^T V partial sums. y: (B, N, 64) rows view; wkv: raw (128, 64)
     Linear weight -> fp64 partial sums (B, nblk, 512); kv itself never reaches HBM."""
@@ -1552,7 +1558,7 @@ def linattn_fold(part, wend, weff, wofs, kofs, scale, heads=8):
 
 
 def linattn_fold_bwd(ktv, wend, dweff, dktv, dwend_part, wofs, kofs, scale, heads):
-    """Backward of linattn_fold at any geometry (heads * d <= 64, d <= 8): ktv / dktv (B, heads, d, d) fp64 contiguous, wend
+    """Backward of linattn_fold (heads * d <= 64 a multiple of 16, d <= 8): ktv / dktv (B, heads, d, d) fp64 contiguous, wend
     (Nout, ldw), dweff (B, Nout, ldweff) and dwend_part (B, Nout, ldp) with unit column stride.  Writes dktv and
     dwend_part[:, :, wofs:wofs + heads * d] (this image's share of d end_proj; the caller sums over images)."""
     B, h, d, _ = ktv.shape
@@ -1563,9 +1569,9 @@ def linattn_fold_bwd(ktv, wend, dweff, dktv, dwend_part, wofs, kofs, scale, head
             raise RuntimeError(f"linattn_fold_bwd: {n} needs unit column stride")
     if dweff.stride(0) != dweff.shape[1] * dweff.stride(1) or dwend_part.stride(0) != dwend_part.shape[1] * dwend_part.stride(1):
         raise RuntimeError("linattn_fold_bwd: dweff / dwend_part images must be packed")
-    _lib.check(_lib.load().segmif_linattn_fold_bwd_generic_f32(
+    _lib.check(_lib.load().segmif_linattn_fold_bwd_f32(
         ktv.data_ptr(), wend.data_ptr(), wend.stride(0), wofs, dweff.data_ptr(), dweff.stride(1), kofs, float(scale), dktv.data_ptr(),
-        dwend_part.data_ptr(), dwend_part.stride(1), B, wend.shape[0], heads, d, _stream()), "segmif_linattn_fold_bwd_generic_f32")
+        dwend_part.data_ptr(), dwend_part.stride(1), B, wend.shape[0], heads, d, _stream()), "segmif_linattn_fold_bwd_f32")
     return dktv, dwend_part
 
 

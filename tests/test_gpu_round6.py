@@ -476,7 +476,7 @@ def test_context_fold_node_vs_fp64_autograd(ops, B, spread):
     wend = (torch.randn(64, 128, generator=g0) * 0.1).cuda().requires_grad_(True)
     dweff = torch.randn(B, 64, 128, generator=g0).cuda()
     sa, s3 = 8 ** -0.5, 0.31
-    weff = ag.context_fold(ka, k3, wend, sa, s3)
+    weff = ag.context_fold(wend, 8, (sa, s3), ka, k3)
     weff.backward(dweff)
     ka64, k364, w64 = (t.detach().double().cpu().requires_grad_(True) for t in (ka, k3, wend))
     ca, c3 = torch.softmax(ka64 * sa, dim=-2), torch.softmax(k364 * s3, dim=-2)

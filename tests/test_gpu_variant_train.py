@@ -1,5 +1,5 @@
 """GPU tests of the ablation variants' training path (segmif_amd/core/variants.py in train mode with gradients wanted):
-  * the generic linear-attention fold backward (segmif_linattn_fold_bwd_generic_f32) and the SiLU backward
+  * the linear-attention fold backward at every head geometry (segmif_linattn_fold_bwd_f32) and the SiLU backward
     (segmif_pointwise2_bwd_f32) against float64 torch autograd;
   * every trainable variant class - forward, parameter and input gradients - against float64 CPU autograd through the oracle's
     restatements (pinned to the real reference's forward records by tests/test_oracle_golden.py);
@@ -49,12 +49,11 @@ def _flat(res):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
-# 1. generic fold backward
+# 1. fold backward at every head geometry
 # ------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("halves", [1, 2])
 @pytest.mark.parametrize("heads,d", [(8, 2), (8, 4), (4, 8), (2, 8), (8, 8)])
 def test_linattn_fold_bwd_generic_vs_fp64_autograd(ops, heads, d, halves):
-    from segmif_amd import _lib
     B, Nout = 2, 40
     C = heads * d
     K = C * halves
@@ -82,17 +81,6 @@ def test_linattn_fold_bwd_generic_vs_fp64_autograd(ops, heads, d, halves):
         # only this fold's columns of dwend_part are written
         other = torch.cat([part[:, :, :q * C], part[:, :, (q + 1) * C:]], dim=-1)
         assert bool(torch.isnan(other).all())
-        if (heads, d) == (8, 8):  # the tuned kernel at its own geometry
-            dk2 = torch.empty_like(dk)
-            part2 = torch.full((B, Nout, K), float("nan"), device="cuda")
-            w_d, dw_d = wend.cuda(), dweff.cuda()
-            kd = ktv.cuda()
-            _lib.check(_lib.load().segmif_linattn_fold_bwd_f32(
-                kd.data_ptr(), w_d.data_ptr(), K, q * C, dw_d.data_ptr(), K, q * C, scale, dk2.data_ptr(), part2.data_ptr(), K, B, Nout,
-                ops._stream()), "segmif_linattn_fold_bwd_f32")
-            torch.cuda.synchronize()
-            assert rel(dk, dk2) < 1e-12
-            assert rel(part[:, :, q * C:(q + 1) * C], part2[:, :, q * C:(q + 1) * C]) < 1e-6
     observed(f"fold_bwd_generic_dktv[{heads}x{d},{halves}]", worst_k)
     observed(f"fold_bwd_generic_dwend[{heads}x{d},{halves}]", worst_w)
 
@@ -104,11 +92,11 @@ def test_linattn_fold_bwd_generic_rejects_bad_geometry(ops):
     lib = _lib.load()
     s = ops._stream()
     for heads, d in ((16, 8), (8, 9), (3, 2)):  # C > 64, d > 8, C % 16 != 0
-        assert lib.segmif_linattn_fold_bwd_generic_f32(t.data_ptr(), f.data_ptr(), 64, 0, f.data_ptr(), 64, 0, 1.0, t.data_ptr(),
-                                                       f.data_ptr(), 64, 1, 8, heads, d, s) != 0
+        assert lib.segmif_linattn_fold_bwd_f32(t.data_ptr(), f.data_ptr(), 64, 0, f.data_ptr(), 64, 0, 1.0, t.data_ptr(),
+                                               f.data_ptr(), 64, 1, 8, heads, d, s) != 0
     # a pitch too narrow for the fold's columns
-    assert lib.segmif_linattn_fold_bwd_generic_f32(t.data_ptr(), f.data_ptr(), 32, 16, f.data_ptr(), 64, 0, 1.0, t.data_ptr(),
-                                                   f.data_ptr(), 64, 1, 8, 8, 4, s) != 0
+    assert lib.segmif_linattn_fold_bwd_f32(t.data_ptr(), f.data_ptr(), 32, 16, f.data_ptr(), 64, 0, 1.0, t.data_ptr(),
+                                           f.data_ptr(), 64, 1, 8, 8, 4, s) != 0
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
