@@ -613,6 +613,47 @@ int segmif_fusion_stats_u8(const uint8_t* fused_rgb, const uint8_t* vis_rgb, con
 int segmif_palette_u8(const int32_t* labels, const uint8_t* palette, uint8_t* out, int64_t n, int K, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * Training data on the device: the loader's augmentation (datasets/voc_fusion3.py:169-216 with
+ * datasets/imutils.py) over uint8 frames resident in device memory - ir, mask, label (N, h, w),
+ * vis (N, h, w, 3).  The host draws the random parameters; the kernels read every geometry value
+ * from one record per sample, so a batch is one upload and two launches, without a host sync.
+ * ---------------------------------------------------------------------------------------------- */
+#define SEGMIF_AUGMENT_MAX_SIDE 4096
+/* One sample of a batch.  `tab` (the second device buffer of a batch, int32 words) holds, at the word offsets below,
+ *   tab_x:  nw entries of (2 + taps_x) words: first source column, tap count n <= taps_x, n coefficients  } Pillow's bilinear
+ *   tab_y:  nh entries of (2 + taps_y) words, the same for rows                                            } tables, 22 bits
+ *   near_x: nw source columns, near_y: nh source rows (Pillow's nearest resize, for the label)
+ * A dimension that keeps its size has the identity table (one tap of 2^22).  A pixel of a pass is
+ * clip8((2^21 + sum k_i p_i) >> 22); the horizontal pass runs first and is rounded to uint8.  in / out <= 4 per axis. */
+typedef struct {
+  int32_t src, h, w;               /* frame index and the frames' size (must equal the h, w of the call) */
+  int32_t nw, nh;                  /* scaled size (int(ratio w), int(ratio h)) */
+  int32_t flip;                    /* np.fliplr after the resize */
+  int32_t bright_on; float beta;   /* visible image only: uint8(clip(float32(v) + beta, 0, 255)), then */
+  int32_t contrast_on; float alpha;/*                     uint8(clip(float32(v) * alpha, 0, 255)) */
+  int32_t pad_h, pad_w;            /* where the image sits in the padded canvas */
+  int32_t H, W;                    /* canvas: max(crop_h, nh), max(crop_w, nw) */
+  int32_t cand[20];                /* ten candidate crop origins (row, column) on the canvas */
+  int32_t box_h, box_w, chosen;    /* the kept origin and its index: written by segmif_augment_pick_u8 (or by the host) */
+  int32_t ticket, accept_mask;     /* pick's scratch: zero on entry, zero again on exit */
+  int32_t accepted;                /* written by pick: bit c set = candidate c passed the class-balance test */
+  int32_t tab_x, tab_y, near_x, near_y, taps_x, taps_y;
+  int32_t reserved[2];
+} SegmifAugmentRec;
+int segmif_augment_record_bytes(void);
+/* imutils.py:223-238 for every sample: counts the classes of each candidate window of the virtual label (nearest-resized,
+ * flipped, padded with 255) and keeps the first with a non-ignore pixel and 4 max_count < 3 sum_count (= max / sum < 0.75
+ * in float64 for counts below 2^18; `len(cnt > 1)` there is len(cnt)), else the tenth.  Writes box_h, box_w, chosen, accepted. */
+int segmif_augment_pick_u8(const uint8_t* label, int N, int h, int w, SegmifAugmentRec* rec, const int32_t* tab, int64_t tab_words,
+                           int B, int crop_h, int crop_w, void* stream);
+/* The batch itself: ir3, vis3, mask3 (B, 3, crop_h, crop_w) fp32 = value / 255 (IEEE division) and label_out (B, crop_h, crop_w)
+ * int64, from box_h / box_w of the records.  Outside the image: float32(123.675 | 116.28 | 103.53) / 255 per channel in all
+ * three images (random_crop2 pads the grey ones the same way) and label 255.  crop_w % 4 == 0, outputs 16-byte aligned. */
+int segmif_augment_apply_u8(const uint8_t* ir, const uint8_t* vis, const uint8_t* mask, const uint8_t* label, int N, int h, int w,
+                            const SegmifAugmentRec* rec, const int32_t* tab, int64_t tab_words, int B, int crop_h, int crop_w,
+                            float* ir3, float* vis3, float* mask3, int64_t* label_out, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
  * Training path (backward of the ops above; autograd in the reference: loss.backward() at
  * train.py:226, :384).  Contractions reuse segmif_igemm_f32 (input gradients, with transposed /
  * rotated weights) and segmif_wgrad_f32; the entries below cover the rest.  Every reduction is

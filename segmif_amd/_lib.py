@@ -82,6 +82,15 @@ class SegmifMixFfn(ctypes.Structure):
                 ("amax_a", c_void_p), ("amax_g", c_void_p), ("amax_images", c_int32)]
 
 
+class SegmifAugmentRec(ctypes.Structure):
+    _fields_ = [("src", c_int32), ("h", c_int32), ("w", c_int32), ("nw", c_int32), ("nh", c_int32), ("flip", c_int32),
+                ("bright_on", c_int32), ("beta", c_float), ("contrast_on", c_int32), ("alpha", c_float),
+                ("pad_h", c_int32), ("pad_w", c_int32), ("H", c_int32), ("W", c_int32), ("cand", c_int32 * 20),
+                ("box_h", c_int32), ("box_w", c_int32), ("chosen", c_int32), ("ticket", c_int32), ("accept_mask", c_int32),
+                ("accepted", c_int32), ("tab_x", c_int32), ("tab_y", c_int32), ("near_x", c_int32), ("near_y", c_int32),
+                ("taps_x", c_int32), ("taps_y", c_int32), ("reserved", c_int32 * 2)]
+
+
 # name -> (restype, argtypes); must list every symbol include/segmif_hip.h declares
 SIGNATURES = {
     "segmif_abi_version": (c_int, []),
@@ -155,6 +164,10 @@ SIGNATURES = {
     "segmif_fusion_stats_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "segmif_fusion_stats_u8": (c_int, [c_void_p] * 8 + [c_int, c_int, c_int, c_int, c_void_p]),
     "segmif_palette_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "segmif_augment_record_bytes": (c_int, []),
+    "segmif_augment_pick_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
+    "segmif_augment_apply_u8": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int]
+                                + [c_void_p] * 5),
     "segmif_wgrad_workspace_size":(c_int64, [c_int64, c_int, c_int]),
     "segmif_wgrad_f32": (c_int, [POINTER(SegmifIgemm), c_void_p, c_int, c_int64, c_void_p, c_int64, c_int64, c_void_p,
                                  c_void_p, c_int, c_void_p]),

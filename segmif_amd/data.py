@@ -1,0 +1,349 @@
+"""Training batches made on the device: the reference loader's `(name, ir3, vis3, mask3, label)` tuples
+(datasets/voc_fusion3.py:142-216 with datasets/imutils.py; train.py:137-142, :211-215) from uint8 frames that stay resident
+in device memory.  Per batch the host draws the random parameters and builds Pillow's resize tables (numpy, float64); the
+pixels are produced by csrc/augment.hip and never cross the host link.
+
+    ds = DeviceDataset.from_folder(PairFolder(root, lists, "train"))        # or DeviceDataset.from_arrays(**synthetic_pairs(...))
+    for names, ir3, vis3, mask3, label in AugmentedBatches(ds, batch=8, seed=0):
+        ...
+
+What differs from the reference's loader is listed in INTEGRATION.md section 5: saturation and hue are not applied, all ten
+crop candidates are always drawn, images are float32 (the reference's are float32 too, its labels float32: ours int64).
+"""
+import os
+import random
+
+import numpy as np
+import torch
+
+from . import dist
+from .evaluate import _read
+
+PRECISION_BITS = 22  # Pillow, Resample.c: 32 - 8 - 2
+MEAN_RGB = (123.675, 116.28, 103.53)
+PHOTOMETRIC = ("brightness", "contrast")
+N_CANDIDATES = 10
+MAX_SHRINK = 4  # csrc/augment.hip holds the horizontal-pass rows of one 16-row tile in LDS: in / out <= 4 per axis
+
+
+# ------------------------------------------------------------------------------------------------------------ resize tables
+
+def bilinear_table(in_size, out_size):
+    """Pillow's coefficients of a BILINEAR resize of one axis, 8 bits per channel (Resample.c: precompute_coeffs with the
+    triangle filter, then normalize_coeffs_8bpc) -> (taps, table) with table (out_size, 2 + taps) int32: first source index,
+    tap count, fixed-point weights (22 bits).  An axis that keeps its size is not resampled by Pillow: identity table."""
+    if in_size == out_size:
+        t = np.zeros((out_size, 3), dtype=np.int32)
+        t[:, 0] = np.arange(out_size)
+        t[:, 1] = 1
+        t[:, 2] = 1 << PRECISION_BITS
+        return 1, t
+    scale = float(in_size) / float(out_size)
+    fs = max(scale, 1.0)
+    support = 1.0 * fs
+    taps = int(np.ceil(support)) * 2 + 1
+    center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)  # (int) truncates; the argument is > -1 where it is negative
+    xmax = np.minimum((center + support + 0.5).astype(np.int64), in_size)
+    n = xmax - xmin
+    ss = 1.0 / fs
+    x = np.arange(taps, dtype=np.float64)[None, :]
+    arg = np.abs((x + xmin[:, None] - center[:, None] + 0.5) * ss)
+    wgt = np.where((arg < 1.0) & (x < n[:, None]), 1.0 - arg, 0.0)
+    ww = np.zeros(out_size, dtype=np.float64)
+    for i in range(taps):  # (the C loop's order of additions)
+        ww = ww + wgt[:, i]
+    wgt = np.where(ww[:, None] != 0.0, wgt / np.where(ww == 0.0, 1.0, ww)[:, None], wgt)
+    k = (0.5 + wgt * float(1 << PRECISION_BITS)).astype(np.int64)  # weights are >= 0 for this filter
+    k[x.repeat(out_size, 0) >= n[:, None]] = 0
+    t = np.empty((out_size, 2 + taps), dtype=np.int32)
+    t[:, 0], t[:, 1], t[:, 2:] = xmin, n, k
+    return taps, t
+
+
+def nearest_table(in_size, out_size):
+    """Source index of every output index of Pillow's NEAREST resize (Geometry.c, ImagingScaleAffine): xo starts at a / 2 with
+    a = in / out and is ADVANCED by a, the sum accumulating in double; int((x + 0.5) * a) differs at some ratios."""
+    if in_size == out_size:
+        return np.arange(out_size, dtype=np.int32)
+    a = float(in_size) / float(out_size)
+    xo = np.add.accumulate(np.concatenate(([a * 0.5], np.full(out_size - 1, a, dtype=np.float64))))  # sequential, as the C loop
+    return np.minimum(xo.astype(np.int64), in_size - 1).astype(np.int32)
+
+
+# ---------------------------------------------------------------------------------------------------------------- parameters
+
+def sample_params(py, npr, h, w, crop_h, crop_w, rescale_range=(0.5, 2.0), fliplr=True, photometric=PHOTOMETRIC):
+    """One sample's random parameters with the reference's distributions, from a private random.Random `py` and
+    numpy.random.RandomState `npr` (the reference draws from the two global generators in the same roles)."""
+    p = {"ratio": 1.0, "flip": False, "bright_on": False, "beta": 0.0, "contrast_on": False, "alpha": 1.0}
+    if rescale_range:
+        lo, hi = rescale_range
+        p["ratio"] = py.uniform(lo, hi)                      # imutils.py:40
+    p["nw"], p["nh"] = int(p["ratio"] * w), int(p["ratio"] * h)  # imutils.py:73
+    if fliplr:
+        p["flip"] = py.random() > 0.5                        # imutils.py:126
+    if "brightness" in photometric and npr.randint(2):       # imutils.py:316-320
+        p["bright_on"], p["beta"] = True, py.uniform(-32, 32)
+    if "contrast" in photometric and npr.randint(2):         # imutils.py:325-328
+        p["contrast_on"], p["alpha"] = True, py.uniform(0.5, 1.5)
+    H, W = max(crop_h, p["nh"]), max(crop_w, p["nw"])        # imutils.py:202-203
+    p["H"], p["W"] = H, W
+    p["pad_h"] = int(npr.randint(H - p["nh"] + 1))           # imutils.py:213-214
+    p["pad_w"] = int(npr.randint(W - p["nw"] + 1))
+    p["cand"] = [(py.randrange(0, H - crop_h + 1), py.randrange(0, W - crop_w + 1)) for _ in range(N_CANDIDATES)]
+    return p
+
+
+def identity_params(h, w):
+    """aug=False: the frame as it is (crop = the frame, box fixed at the origin)."""
+    return {"ratio": 1.0, "nw": w, "nh": h, "flip": False, "bright_on": False, "beta": 0.0, "contrast_on": False, "alpha": 1.0,
+            "H": h, "W": w, "pad_h": 0, "pad_w": 0, "cand": [(0, 0)] * N_CANDIDATES, "box": (0, 0)}
+
+
+# word offsets of SegmifAugmentRec (include/segmif_hip.h; segmif_amd._lib.SegmifAugmentRec is the ctypes mirror)
+REC_WORDS = 48
+_SRC, _H, _W, _NW, _NH, _FLIP, _BON, _BETA, _CON, _ALPHA, _PADH, _PADW, _CH, _CW, _CAND = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14
+_BOXH, _BOXW, _CHOSEN, _TICKET, _AMASK, _ACCEPTED, _TABX, _TABY, _NEARX, _NEARY, _TAPSX, _TAPSY = 34, 35, 36, 37, 38, 39, 40, 41, 42, 43, 44, 45
+
+
+def pack_records(indices, params, h, w):
+    """-> (rec (B, REC_WORDS) int32, tab (words,) int32): the records of a batch and the resize tables they point into."""
+    B = len(indices)
+    rec = np.zeros((B, REC_WORDS), dtype=np.int32)
+    recf = rec.view(np.float32)
+    parts, at = [], 0
+    for b, (src, p) in enumerate(zip(indices, params)):
+        nw, nh = p["nw"], p["nh"]
+        if nw < 1 or nh < 1 or w > MAX_SHRINK * nw or h > MAX_SHRINK * nh:
+            raise RuntimeError(f"augment: a {h} x {w} frame scaled to {nh} x {nw} is outside the kernels' range (in / out <= {MAX_SHRINK})")
+        tx, bx = bilinear_table(w, nw)
+        ty, by = bilinear_table(h, nh)
+        r = rec[b]
+        r[_SRC], r[_H], r[_W], r[_NW], r[_NH], r[_FLIP] = src, h, w, nw, nh, int(p["flip"])
+        r[_BON], r[_CON] = int(p["bright_on"]), int(p["contrast_on"])
+        recf[b, _BETA], recf[b, _ALPHA] = np.float32(p["beta"]), np.float32(p["alpha"])
+        r[_PADH], r[_PADW], r[_CH], r[_CW] = p["pad_h"], p["pad_w"], p["H"], p["W"]
+        r[_CAND:_CAND + 2 * N_CANDIDATES] = np.asarray(p["cand"], dtype=np.int32).reshape(-1)
+        if "box" in p:
+            r[_BOXH], r[_BOXW] = p["box"]
+        r[_TAPSX], r[_TAPSY] = tx, ty
+        for word, arr in ((_TABX, bx.reshape(-1)), (_TABY, by.reshape(-1)), (_NEARX, nearest_table(w, nw)), (_NEARY, nearest_table(h, nh))):
+            r[word] = at
+            parts.append(arr)
+            at += arr.size
+    return rec, np.concatenate(parts)
+
+
+# ------------------------------------------------------------------------------------------------------------------- sources
+
+class PairFolder:
+    """The reference's directory contract (voc_fusion3.py:25-30): ROOT/Infrared, Visible, Mask2, Label hold NAME.png (or
+    NAME.npy) for every NAME listed in NAME_LIST_DIR/SPLIT.txt.  .npy is always read, .png when PIL imports."""
+
+    SUBDIRS = {"ir": "Infrared", "vis": "Visible", "mask": "Mask2", "label": "Label"}
+
+    def __init__(self, root_dir, name_list_dir, split="train"):
+        self.root_dir = root_dir
+        path = os.path.join(name_list_dir, split + ".txt")
+        with open(path) as f:
+            self.names = [ln.split()[0] for ln in f if ln.strip()]
+        if not self.names:
+            raise RuntimeError(f"{path} lists no frames")
+
+    def __len__(self):
+        return len(self.names)
+
+    def _file(self, kind, name):
+        base = os.path.join(self.root_dir, self.SUBDIRS[kind], name)
+        for ext in (".png", ".npy"):
+            if os.path.isfile(base + ext):
+                return base + ext
+        raise FileNotFoundError(f"{base}.png / .npy not found")
+
+    def __getitem__(self, i):
+        """-> (name, ir (h, w), vis (h, w, 3), mask (h, w), label (h, w)) uint8 arrays"""
+        name = self.names[i]
+        ir, vis, mask, label = (np.asarray(_read(self._file(k, name))) for k in ("ir", "vis", "mask", "label"))
+        if ir.ndim != 2 or mask.ndim != 2 or label.ndim != 2 or vis.ndim != 3 or vis.shape[2] != 3:
+            raise RuntimeError(f"{name}: expected grey infrared / mask / label and an RGB visible image, got shapes "
+                               f"{ir.shape}, {vis.shape}, {mask.shape}, {label.shape}")
+        return name, ir.astype(np.uint8), vis.astype(np.uint8), mask.astype(np.uint8), label.astype(np.uint8)
+
+
+def synthetic_pairs(n, H, W, seed, n_class=9):
+    """A seeded stand-in data set: uint8 frames with image-like statistics (smooth large-scale structure plus fine noise, an
+    infrared plane correlated with the visible luma, a saliency-like mask) and blocky label maps of rectangles over class 0.
+    -> dict(names, ir (n, H, W), vis (n, H, W, 3), mask (n, H, W), label (n, H, W)), numpy uint8.  NOT data: for smoke runs,
+    tests and timing only."""
+    rng = np.random.default_rng(seed)
+
+    def smooth(channels):
+        gh, gw = max(2, H // 32 + 2), max(2, W // 32 + 2)
+        g = rng.random((channels, gh, gw))
+        ys, xs = np.linspace(0, gh - 1, H), np.linspace(0, gw - 1, W)
+        y0, x0 = np.minimum(ys.astype(int), gh - 2), np.minimum(xs.astype(int), gw - 2)
+        fy, fx = (ys - y0)[None, :, None], (xs - x0)[None, None, :]
+        a, b = g[:, y0][:, :, x0], g[:, y0][:, :, x0 + 1]
+        c, d = g[:, y0 + 1][:, :, x0], g[:, y0 + 1][:, :, x0 + 1]
+        return (a * (1 - fx) + b * fx) * (1 - fy) + (c * (1 - fx) + d * fx) * fy
+
+    out = {"names": [f"syn{seed}_{i:05d}" for i in range(n)], "ir": np.empty((n, H, W), np.uint8), "vis": np.empty((n, H, W, 3), np.uint8),
+           "mask": np.empty((n, H, W), np.uint8), "label": np.zeros((n, H, W), np.uint8)}
+    for i in range(n):
+        vis = smooth(3) * 0.8 + 0.1 + rng.normal(0, 0.03, (3, H, W))
+        luma = vis.mean(0)
+        ir = 0.5 * luma + 0.5 * smooth(1)[0] + rng.normal(0, 0.02, (H, W))
+        lab = out["label"][i]
+        for _ in range(int(rng.integers(3, 9))):
+            rh, rw = int(rng.integers(max(2, H // 12), max(3, H // 2))), int(rng.integers(max(2, W // 12), max(3, W // 2)))
+            y, x = int(rng.integers(0, max(1, H - rh))), int(rng.integers(0, max(1, W - rw)))
+            lab[y:y + rh, x:x + rw] = rng.integers(1, n_class)
+        out["vis"][i] = np.clip(vis.transpose(1, 2, 0) * 255, 0, 255).astype(np.uint8)
+        out["ir"][i] = np.clip(ir * 255, 0, 255).astype(np.uint8)
+        out["mask"][i] = np.where(lab > 0, 255, 0).astype(np.uint8)
+    return out
+
+
+class DeviceDataset:
+    """The whole set as uint8 tensors on the device: ir, mask, label (N, H, W) and vis (N, H, W, 3).  MFNet's training split
+    (1 569 frames of 480 x 640) is 2.9 GB this way."""
+
+    def __init__(self, names, ir, vis, mask, label):
+        for t, what in ((ir, "ir"), (vis, "vis"), (mask, "mask"), (label, "label")):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise RuntimeError(f"segmif_amd: DeviceDataset {what} must be a tensor on the MI355X device (the HIP path has no CPU "
+                                   "fallback); DeviceDataset.from_arrays uploads host arrays")
+            if t.dtype != torch.uint8:
+                raise RuntimeError(f"segmif_amd: DeviceDataset {what} must be uint8, got {t.dtype}")
+        N, H, W = ir.shape
+        if tuple(vis.shape) != (N, H, W, 3) or tuple(mask.shape) != (N, H, W) or tuple(label.shape) != (N, H, W) or len(names) != N:
+            raise RuntimeError(f"DeviceDataset: ir {tuple(ir.shape)}, vis {tuple(vis.shape)}, mask {tuple(mask.shape)}, label "
+                               f"{tuple(label.shape)} and {len(names)} names do not describe one set of frames")
+        self.names = list(names)
+        self.ir, self.vis, self.mask, self.label = ir.contiguous(), vis.contiguous(), mask.contiguous(), label.contiguous()
+        self.shape = (H, W)
+
+    def __len__(self):
+        return len(self.names)
+
+    @classmethod
+    def from_arrays(cls, names, ir, vis, mask, label, device="cuda"):
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(device)
+        return cls(names, up(ir), up(vis), up(mask), up(label))
+
+    @classmethod
+    def from_folder(cls, folder, device="cuda"):
+        items = [folder[i] for i in range(len(folder))]
+        stack_same_size(items)
+        return cls.from_arrays([it[0] for it in items], *(np.stack([it[k] for it in items]) for k in (1, 2, 3, 4)), device=device)
+
+    def augment(self, rec, tab, crop_h, crop_w, pick=True):
+        """rec (B, REC_WORDS), tab: host int32 arrays of pack_records -> (ir3, vis3, mask3, label, rec_dev).  One pinned,
+        asynchronous upload, then the two kernels on the current stream."""
+        from . import ops
+        B = rec.shape[0]
+        blob = self._staging(rec.size + tab.size)
+        blob[:rec.size].copy_(torch.from_numpy(rec.reshape(-1)))
+        blob[rec.size:rec.size + tab.size].copy_(torch.from_numpy(tab))
+        dev = torch.empty(rec.size + tab.size, dtype=torch.int32, device=self.ir.device)
+        dev.copy_(blob[:rec.size + tab.size], non_blocking=True)
+        self._staged[self._turn][1].record()
+        rec_d, tab_d = dev[:rec.size].view(B, REC_WORDS), dev[rec.size:]
+        if pick:
+            ops.augment_pick(self.label, rec_d, tab_d, crop_h, crop_w)
+        return ops.augment_apply(self.ir, self.vis, self.mask, self.label, rec_d, tab_d, crop_h, crop_w) + (rec_d,)
+
+    def _staging(self, words):
+        """Two pinned buffers used in turn; a buffer is rewritten only after the copy that last read it has completed."""
+        if not hasattr(self, "_staged"):
+            self._staged, self._turn = [None, None], 0
+        self._turn ^= 1
+        slot = self._staged[self._turn]
+        if slot is None or slot[0].numel() < words:
+            if slot is not None:
+                slot[1].synchronize()
+            slot = [torch.empty(max(words, 1 << 18), dtype=torch.int32).pin_memory(), torch.cuda.Event()]
+            self._staged[self._turn] = slot
+        else:
+            slot[1].synchronize()
+        return slot[0]
+
+
+def stack_same_size(items):
+    """Raises unless every (name, ir, vis, mask, label) item has the size of the first."""
+    h, w = items[0][1].shape
+    for name, ir, vis, mask, label in items:
+        for a, what in ((ir, "infrared"), (vis, "visible"), (mask, "mask"), (label, "label")):
+            if a.shape[:2] != (h, w):
+                raise RuntimeError(f"DeviceDataset holds frames of ONE size: {name} has a {a.shape[0]} x {a.shape[1]} {what} image, "
+                                   f"{items[0][0]} is {h} x {w}.  Resize the set, or split it by size into several data sets.")
+
+
+# ------------------------------------------------------------------------------------------------------------------ iterator
+
+class AugmentedBatches:
+    """Endless iterator of `(names, ir3, vis3, mask3, label)`: ir3, vis3, mask3 (B, 3, crop, crop) float32 in NCHW (ir3 and
+    mask3 are STORED with three channels: they are equal inside the image and differ in the padding, as random_crop2's are),
+    label (B, crop, crop) int64 with 255 in the padding.
+
+    Order: the rank's slice (segmif_amd.dist.shard) of the data set front to back, no shuffle, the last partial batch
+    dropped (train.py:137-142); when the slice is used up it starts again (train.py:211-215).
+
+    Randomness: a private random.Random(seed + rank) and numpy RandomState(seed + rank); the global generators are not
+    touched.  The distributions are the reference's.  The STREAM is not: the reference stops drawing crop candidates at the
+    first accepted one, this class always draws all ten (the kernel then keeps the first accepted), so the same seed gives
+    other numbers while the distribution of the results is the same.
+
+    photometric: any subset of ("brightness", "contrast"); saturation and hue are not available.
+    aug=False: every frame whole, value / 255, no resize, flip, distortion or crop."""
+
+    def __init__(self, dataset, batch, crop_size=512, rescale_range=(0.5, 2.0), fliplr=True, photometric=PHOTOMETRIC, seed=0,
+                 rank=0, world=1, aug=True):
+        unknown = [p for p in photometric if p not in PHOTOMETRIC]
+        if unknown:
+            raise ValueError(f"photometric: {unknown} not available; this loader applies {PHOTOMETRIC} only (saturation and hue go "
+                             "through OpenCV's HSV conversion in the reference and are left out)")
+        if batch < 1 or crop_size < 1 or crop_size % 4:
+            raise ValueError("batch must be positive and crop_size a positive multiple of 4")
+        if rescale_range and not 0 < rescale_range[0] <= rescale_range[1]:
+            raise ValueError(f"rescale_range {rescale_range}")
+        if not aug and dataset.shape[1] % 4:
+            raise ValueError(f"aug=False hands over whole frames through 16-byte stores: the frame width must be a multiple of 4, "
+                             f"this data set's is {dataset.shape[1]}")
+        self.dataset, self.batch, self.crop = dataset, batch, crop_size
+        self.rescale_range, self.fliplr, self.photometric, self.aug = rescale_range, fliplr, tuple(photometric), aug
+        self.indices = list(dist.shard(len(dataset), rank, world))
+        if len(self.indices) < batch:
+            raise RuntimeError(f"rank {rank} of {world} holds {len(self.indices)} frames, fewer than one batch of {batch}")
+        self._py, self._np = random.Random(seed + rank), np.random.RandomState(seed + rank)
+        self._at = 0
+        self.last_params = None
+
+    def __len__(self):
+        """batches per pass (drop_last)"""
+        return len(self.indices) // self.batch
+
+    def __iter__(self):
+        return self
+
+    def draw(self, n):
+        h, w = self.dataset.shape
+        if not self.aug:
+            return [identity_params(h, w) for _ in range(n)]
+        return [sample_params(self._py, self._np, h, w, self.crop, self.crop, self.rescale_range, self.fliplr, self.photometric)
+                for _ in range(n)]
+
+    def __next__(self):
+        if self._at + self.batch > len(self.indices):  # drop_last, then a fresh pass
+            self._at = 0
+        idx = self.indices[self._at:self._at + self.batch]
+        self._at += self.batch
+        self.last_params = params = self.draw(len(idx))
+        return (tuple(self.dataset.names[i] for i in idx),) + tuple(self._device_step(idx, params))
+
+    def _device_step(self, idx, params):
+        h, w = self.dataset.shape
+        rec, tab = pack_records(idx, params, h, w)
+        ch, cw = (self.crop, self.crop) if self.aug else (h, w)
+        return self.dataset.augment(rec, tab, ch, cw, pick=self.aug)[:4]

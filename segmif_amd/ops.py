@@ -1858,3 +1858,53 @@ def argmax_nhwc(x):
     _lib.check(_lib.load().segmif_argmax_nhwc_i32(x.data_ptr(), out.data_ptr(), rows, C, ldx, _stream()),
                "segmif_argmax_nhwc_i32")
     return out
+
+
+AUGMENT_REC_WORDS = ctypes.sizeof(_lib.SegmifAugmentRec) // 4
+
+
+def _req_u8(t, name, shape=None, dtype=torch.uint8):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"segmif_amd: {name} must be a tensor on the MI355X device (the HIP path has no CPU fallback)")
+    if t.dtype != dtype or not t.is_contiguous():
+        raise RuntimeError(f"segmif_amd: {name} must be a contiguous {dtype} tensor, got {t.dtype}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"segmif_amd: {name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    return t
+
+
+def _augment_args(label, rec, tab, crop_h, crop_w):
+    _req_u8(label, "label")
+    if label.dim() != 3:
+        raise RuntimeError("augment: label must be (N, h, w) uint8")
+    _req_u8(rec, "rec", dtype=torch.int32)
+    _req_u8(tab, "tab", dtype=torch.int32)
+    if rec.dim() != 2 or rec.shape[1] != AUGMENT_REC_WORDS or rec.shape[0] < 1:
+        raise RuntimeError(f"augment: rec must be (B, {AUGMENT_REC_WORDS}) int32 (one SegmifAugmentRec per sample)")
+    if crop_h < 1 or crop_w < 1 or crop_w % 4:
+        raise RuntimeError(f"augment: the crop must be positive and its width a multiple of 4, got {crop_h} x {crop_w}")
+    return label.shape
+
+
+def augment_pick(label, rec, tab, crop_h, crop_w):
+    """segmif_augment_pick_u8: chooses each sample's crop box among its ten candidates (imutils.py:223-238) and writes it
+    into `rec` (B, AUGMENT_REC_WORDS) int32 on the device.  label: the resident (N, h, w) uint8 label maps."""
+    N, h, w = _augment_args(label, rec, tab, crop_h, crop_w)
+    _lib.check(_lib.load().segmif_augment_pick_u8(label.data_ptr(), N, h, w, rec.data_ptr(), tab.data_ptr(), tab.numel(), rec.shape[0],
+                                                  crop_h, crop_w, _stream()), "segmif_augment_pick_u8")
+    return rec
+
+
+def augment_apply(ir, vis, mask, label, rec, tab, crop_h, crop_w):
+    """segmif_augment_apply_u8: the augmented batch of the records' boxes -> ir3, vis3, mask3 (B, 3, crop_h, crop_w) fp32 and
+    label (B, crop_h, crop_w) int64.  ir, mask, label (N, h, w) and vis (N, h, w, 3) are the resident uint8 frames."""
+    N, h, w = _augment_args(label, rec, tab, crop_h, crop_w)
+    _req_u8(ir, "ir", (N, h, w)), _req_u8(mask, "mask", (N, h, w)), _req_u8(vis, "vis", (N, h, w, 3))
+    B = rec.shape[0]
+    ir3, vis3, mask3 = (torch.empty((B, 3, crop_h, crop_w), device=label.device, dtype=torch.float32) for _ in range(3))
+    out = torch.empty((B, crop_h, crop_w), device=label.device, dtype=torch.int64)
+    _lib.check(_lib.load().segmif_augment_apply_u8(ir.data_ptr(), vis.data_ptr(), mask.data_ptr(), label.data_ptr(), N, h, w,
+                                                   rec.data_ptr(), tab.data_ptr(), tab.numel(), B, crop_h, crop_w, ir3.data_ptr(),
+                                                   vis3.data_ptr(), mask3.data_ptr(), out.data_ptr(), _stream()),
+               "segmif_augment_apply_u8")
+    return ir3, vis3, mask3, out

@@ -7,7 +7,17 @@
 Data parallelism (one process per GPU): pass a segmif_amd.parallel.GradAllReducer; gradients are
 averaged over ranks in overlapped buckets before the optimizer step, and the two scalar losses that
 feed train.py:369-374's dynamic weights are averaged too so every rank applies identical weights.
+
+    python -m segmif_amd.train --root DIR --name-lists DIR [--split train] [--val-split val] [--out checkpoint] ...
+    python -m segmif_amd.train --synthetic N ...
+
+runs the whole schedule of train.py:424-434 - seven rounds of a fusion phase then a segmentation phase - on batches that
+segmif_amd.data makes on the device (main() below; one process, one GPU).
 """
+import argparse
+import os
+import sys
+
 import torch
 
 from . import losses, ops
@@ -166,3 +176,175 @@ class FusionTrainer:
             self.reducer.finish()
         self.opt.step()
         return loss.detach()
+
+
+# ------------------------------------------------------------------------------------------------------------- command line
+
+SEG_CKPT, FUSION_CKPT = "model-fusion_add_final2.pth", "modelfusion-final2.pth"  # train.py:237-238, :403-407
+
+
+def make_seg_optimizer(seg_net, iter_curr=0, lr=8e-5, weight_decay=0.01, betas=(0.9, 0.999), warmup_iter=3000, max_iter=160000,
+                       warmup_ratio=1e-6, power=1.0):
+    """train.py:173-200: [encoder non-norm | encoder norm, no decay | decoder + classifier at 10 x lr]"""
+    from .utils.optimizer import PolyWarmupAdamW_seg
+    g = seg_net.denoise_net.get_param_groups()
+    return PolyWarmupAdamW_seg(
+        params=[{"params": g[0], "lr": lr, "weight_decay": weight_decay}, {"params": g[1], "lr": lr, "weight_decay": 0.0},
+                {"params": g[2], "lr": lr * 10, "weight_decay": weight_decay}],
+        lr=lr, weight_decay=weight_decay, betas=list(betas), iter_curr=iter_curr, warmup_iter=warmup_iter, max_iter=max_iter,
+        warmup_ratio=warmup_ratio, power=power)
+
+
+def make_fusion_optimizer(fusion_net, iter_, lr=8e-5, weight_decay=0.01, betas=(0.9, 0.999), max_iter=160000, warmup_ratio=1e-6,
+                          power=1.0):
+    """train.py:316-332: one group at lr / iter_; the default 3e-4 / iter_ and warmup_iter = 3e-5 / iter_ are constants of the
+    reference's code (the warm-up branch is never taken)"""
+    from .utils.optimizer import PolyWarmupAdamW
+    return PolyWarmupAdamW(params=[{"params": list(fusion_net.parameters()), "lr": lr / iter_, "weight_decay": weight_decay}],
+                           lr=3e-4 / iter_, weight_decay=weight_decay, betas=list(betas), warmup_iter=3e-5 / iter_, max_iter=max_iter,
+                           warmup_ratio=warmup_ratio, power=power)
+
+
+def _miou(seg, fus, val, batch):
+    """mIoU of the pair forward (fusion net -> segmentation net) over a DeviceDataset, through segmif_amd.evaluate.Evaluator"""
+    from .evaluate import Evaluator
+    seg.eval(), fus.eval()
+    ev = Evaluator(seg, fus)
+    for i in range(0, len(val), batch):
+        ev.update(val.ir[i:i + batch], val.vis[i:i + batch], val.mask[i:i + batch], val.label[i:i + batch].long())
+    seg.train(), fus.train()
+    return ev.results()["mIoU"]
+
+
+def _fused_frames(seg, fus, ds, batch):
+    """The training set fused by the current nets, uint8 (N, H, W, 3) on the device: what train.py:410-411 (val_fusion_train)
+    writes to disk after every fusion phase for the segmentation phase to read."""
+    from .evaluate import Evaluator
+    seg.eval(), fus.eval()
+    ev = Evaluator(seg, fus)
+    out = torch.empty_like(ds.vis)
+    for i in range(0, len(ds), batch):
+        out[i:i + batch] = ev.update(ds.ir[i:i + batch], ds.vis[i:i + batch], ds.mask[i:i + batch])[0]
+    seg.train(), fus.train()
+    return out
+
+
+def main(argv=None):
+    ours = " (this project's choice: the reference reads it from a configs/*.yaml it does not ship)"
+    ap = argparse.ArgumentParser(prog="python -m segmif_amd.train", description="The reference's training schedule (train.py:424-434) "
+                                 "on device-made batches: per round a fusion phase (FusionTrainer) then a segmentation phase "
+                                 "(seg_train_step).  Constants of the reference's code are fixed: 3e-4 / round as the fusion optimizer's "
+                                 "default rate, 6000 / 4000 fusion and 10000 segmentation iterations, loss weights 0.4 / round and 0.8, "
+                                 "7 rounds; --rounds / --fusion-iters / --seg-iters shorten a run.")
+    ap.add_argument("--root", help="data set root: Infrared/ Visible/ Mask2/ Label/ (voc_fusion3.py:25-28)")
+    ap.add_argument("--name-lists", help="folder of SPLIT.txt name lists")
+    ap.add_argument("--split", default="train")
+    ap.add_argument("--val-split", default="val", help="split whose mIoU decides which segmentation checkpoint is kept")
+    ap.add_argument("--synthetic", type=int, metavar="N", help="train on N seeded synthetic frames instead of a data set")
+    ap.add_argument("--synthetic-size", type=int, nargs=2, default=(480, 640), metavar=("H", "W"))
+    ap.add_argument("--out", default="checkpoint", help=f"folder of {SEG_CKPT} and {FUSION_CKPT}")
+    ap.add_argument("--backbone", default="mit_b3", help="mit_b1 .. mit_b5; mit_b0's 32/64-channel features do not fit "
+                    "the fusion net's conv3 / conv4, in the reference either" + ours)
+    ap.add_argument("--pretrained", action="store_true", help="load the backbone's ImageNet weights from pretrained/BACKBONE.pth as the "
+                    "reference does (model_fusion.py:49); without it: random initialisation")
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--fusion-iters", type=int, help="fusion iterations per round (default 6000 in round 1, then 4000)")
+    ap.add_argument("--seg-iters", type=int, help="segmentation iterations per round (default 10000)")
+    ap.add_argument("--samples-per-gpu", type=int, default=8, help="the loaders' batch is HALF of it (train.py:138, :290)" + ours)
+    ap.add_argument("--crop-size", type=int, default=512, help="crop" + ours)
+    ap.add_argument("--rescale-range", type=float, nargs=2, default=(0.5, 2.0), help="random scaling" + ours)
+    ap.add_argument("--lr", type=float, default=8e-5, help="learning rate of both phases, / round in the fusion phase" + ours)
+    ap.add_argument("--weight-decay", type=float, default=0.01, help=ours.strip(" ()"))
+    ap.add_argument("--betas", type=float, nargs=2, default=(0.9, 0.999), help=ours.strip(" ()"))
+    ap.add_argument("--warmup-iter", type=int, default=3000, help="segmentation warm-up" + ours)
+    ap.add_argument("--warmup-ratio", type=float, default=1e-6, help=ours.strip(" ()"))
+    ap.add_argument("--power", type=float, default=1.0, help="polynomial decay" + ours)
+    ap.add_argument("--max-iters", type=int, default=160000, help="horizon of both schedules" + ours)
+    ap.add_argument("--log-iters", type=int, default=100)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise RuntimeError("segmif_amd.train needs the MI355X device (the HIP path has no CPU fallback)")
+    if (args.synthetic is None) == (args.root is None):
+        ap.error("give either --root DIR --name-lists DIR or --synthetic N")
+    if args.backbone == "mit_b0":
+        ap.error("--backbone mit_b0: Fusion_Network3_ac takes 64/128-channel segmentation features, mit_b0 gives 32/64")
+    from .core import Fusion_Network3_ac, Network3
+    from .data import AugmentedBatches, DeviceDataset, PairFolder, synthetic_pairs
+
+    torch.manual_seed(args.seed)
+    if args.synthetic is not None:
+        H, W = args.synthetic_size
+        print(f"[train] --synthetic {args.synthetic}: training on SYNTHETIC frames (segmif_amd.data.synthetic_pairs, seed {args.seed}, "
+              f"{H} x {W}) - a run of the machinery, not of a data set; validation on {max(2, args.synthetic // 4)} more of them")
+        train_set = DeviceDataset.from_arrays(**synthetic_pairs(args.synthetic, H, W, args.seed))
+        val_set = DeviceDataset.from_arrays(**synthetic_pairs(max(2, args.synthetic // 4), H, W, args.seed + 1))
+    else:
+        if not args.name_lists:
+            ap.error("--root needs --name-lists")
+        train_set = DeviceDataset.from_folder(PairFolder(args.root, args.name_lists, args.split))
+        val_set = DeviceDataset.from_folder(PairFolder(args.root, args.name_lists, args.val_split))
+    os.makedirs(args.out, exist_ok=True)
+    seg_path, fus_path = os.path.join(args.out, SEG_CKPT), os.path.join(args.out, FUSION_CKPT)
+    batch = max(1, args.samples_per_gpu // 2)
+    seg, fus = Network3(args.backbone, 9, pretrained=args.pretrained or None).cuda().train(), Fusion_Network3_ac().cuda().train()
+    if not args.pretrained:
+        print("[train] no --pretrained backbone weights: the segmentation net starts from SEEDED RANDOM weights "
+              f"(torch.manual_seed({args.seed}))")
+    seg_initial = {k: v.clone() for k, v in seg.state_dict().items()}
+    crit = torch.nn.CrossEntropyLoss(ignore_index=255)
+    sched = dict(weight_decay=args.weight_decay, betas=args.betas, max_iter=args.max_iters, warmup_ratio=args.warmup_ratio, power=args.power)
+    loader_kw = dict(batch=batch, crop_size=args.crop_size, rescale_range=tuple(args.rescale_range), fliplr=True)
+    best, wrote_seg = None, False
+    for iter_ in range(1, args.rounds + 1):
+        # ---- fusion phase (train.py:266-413).  Its segmentation net is a freshly built one until round 3 (:307: the checkpoint is
+        # loaded only when iter_ > 2), then the best checkpoint so far.
+        print(f"[train] round {iter_}: fusion")
+        seg_state = {k: v.clone() for k, v in seg.state_dict().items()}
+        if iter_ <= 2:
+            seg.load_state_dict(seg_initial)
+        elif wrote_seg:
+            seg.load_state_dict(torch.load(seg_path, map_location="cuda"))
+        trainer = FusionTrainer(seg, fus, make_fusion_optimizer(fus, iter_, lr=args.lr, **sched), crit, iter_=iter_)
+        batches = AugmentedBatches(train_set, seed=args.seed + 2 * iter_, **loader_kw)
+        n_fus = args.fusion_iters if args.fusion_iters is not None else (6000 if iter_ == 1 else 4000)
+        for n in range(n_fus):
+            _, ir3, vis3, mask3, label = next(batches)
+            loss = trainer.step(ir3, vis3, mask3, label)
+            if (n + 1) % args.log_iters == 0 or n + 1 == n_fus:
+                print(f"[train] round {iter_} fusion iter {n + 1}/{n_fus}: loss {float(loss):.6f}")
+            if (n + 1) % 500 == 0:
+                torch.save(fus.state_dict(), fus_path)
+        torch.save(fus.state_dict(), fus_path)
+        fused_set = DeviceDataset(train_set.names, train_set.ir, _fused_frames(seg, fus, train_set, batch), train_set.mask, train_set.label)
+        # ---- segmentation phase (train.py:115-245) on the fused training frames, from the best checkpoint so far (:159-160)
+        print(f"[train] round {iter_}: segmentation")
+        seg.load_state_dict(torch.load(seg_path, map_location="cuda") if (wrote_seg and iter_ > 1) else seg_state)
+        if best is None:
+            best = _miou(seg, fus, val_set, batch)
+            print(f"[train] initial mIoU {best:.4f}")
+        opt = make_seg_optimizer(seg, iter_curr=(iter_ - 1) * 10000, lr=args.lr, warmup_iter=args.warmup_iter, **sched)
+        batches = AugmentedBatches(fused_set, seed=args.seed + 2 * iter_ + 1, photometric=(), **loader_kw)
+        n_seg = args.seg_iters if args.seg_iters is not None else 10000
+        for n in range(n_seg):
+            _, _, fused3, _, label = next(batches)
+            loss = seg_train_step(seg, opt, fused3, label, crit)
+            if (n + 1) % args.log_iters == 0 or n + 1 == n_seg:
+                print(f"[train] round {iter_} segmentation iter {n + 1}/{n_seg}: lr {opt.param_groups[0]['lr']:.3e} loss {float(loss):.6f}")
+            if (n + 1) % 1000 == 0 or n + 1 == n_seg:
+                miou = _miou(seg, fus, val_set, batch)
+                if miou > best:  # (train.py:237: only an improvement is written)
+                    torch.save(seg.state_dict(), seg_path)
+                    best, wrote_seg = miou, True
+                print(f"[train] round {iter_} segmentation iter {n + 1}: mIoU {miou:.4f} (best {best:.4f})")
+    if not wrote_seg:
+        # no validation ever beat the initial mIoU: the reference would leave no segmentation checkpoint; the last state is written
+        # here, after the last round, so that a run leaves both files and no round has loaded a state that was not an improvement
+        torch.save(seg.state_dict(), seg_path)
+        print(f"[train] no segmentation state improved on the initial mIoU {best:.4f}: {seg_path} holds the LAST state, not a best one")
+    print(f"[train] wrote {seg_path} and {fus_path}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
