@@ -12,7 +12,7 @@ import ctypes
 
 import torch
 
-from . import _lib, ops
+from . import _lib, modes, ops
 from .ops import ACT_GELU, ACT_NONE, ACT_PRELU, ACT_RELU, _req, _stream, rows_view
 
 
@@ -549,8 +549,6 @@ class SrAttentionFn(torch.autograd.Function):
     flash-style kernels of csrc/attention_bwd.hip (scores recomputed per tile in registers, nothing of size N x Nk in HBM;
     SEGMIF_ATTN_BWD=materialize restores round 4's); other head sizes - score recomputation with batched fp32-MFMA GEMMs +
     row-softmax kernels over materialised (B, heads, N, Nk) tensors."""
-    FUSED = __import__("os").environ.get("SEGMIF_ATTN_BWD", "fused") != "materialize"
-
     @staticmethod
     def forward(ctx, q, kv, heads, scale):
         ctx.heads, ctx.scale = heads, scale
@@ -564,7 +562,7 @@ class SrAttentionFn(torch.autograd.Function):
         heads, scale = ctx.heads, ctx.scale
         do = do.contiguous()
         B, N, C = q.shape
-        if SrAttentionFn.FUSED and C == heads * 64 and q.is_contiguous() and kv.is_contiguous() and out.is_contiguous() \
+        if modes.get("attn_bwd") == "fused" and C == heads * 64 and q.is_contiguous() and kv.is_contiguous() and out.is_contiguous() \
                 and ops.aligned16(q, kv, out, do):  # (r6, ADVICE r5: unaligned storage takes the materialising path below instead of EINVAL)
             dq, dkv = ops.sr_attention_bwd(q, kv, out, do, heads, scale)
             return dq, dkv, None, None

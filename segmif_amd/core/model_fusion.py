@@ -15,15 +15,10 @@ import torch
 import torch.nn as nn
 
 from .. import autograd as ag
-from .. import ops
+from .. import modes, ops
 from . import mix_transformer
 from ._util import PackedCache, init_reference_style, require_device, wants_grad
 from .segformer_head import SegFormerHead
-
-import os
-
-_DRDB_RES_PLANES = os.environ.get("SEGMIF_DRDB_RES", "planes") != "fp32"
-_CONV1_STENCIL = os.environ.get("SEGMIF_CONV1", "stencil") != "igemm"  # A/B switch (r6): conv1_ir / conv1_vis as a stencil kernel
 
 __all__ = ["WeTr", "RGB2YCrCb", "YCrCb2RGB", "DRDB", "CrossAttention", "CrossAttention2", "CrossPath",
            "FeatureFusionModule", "Fusion_Network3_ac", "Network3", "Mean", "fuse_to_rgb"]
@@ -704,11 +699,11 @@ class Fusion_Network3_ac(nn.Module):
         # (r4) on f16x3 planes a DRDB takes its residual from its own input chunks (hi + 2^-11 lo), so neither conv1 nor the
         # first interaction's CrossPath tails write an fp32 copy of the DRDB inputs: 20 GB of stores and as many of reads per
         # 64-pair step.  SEGMIF_DRDB_RES=fp32 keeps round 3's fp32 residual tensors (A/B switch; bf16 planes always do).
-        lean = guard is not None and _DRDB_RES_PLANES
+        lean = guard is not None and modes.get("drdb_res") == "planes"
         for x, conv, name in ((ir, self.conv1_ir, "conv1_ir"), (vis, self.conv1_vis, "conv1_vis")):
             pls.append(ops.Planes(B, H, W, DRDB.PLANES_CHUNKS, dev, guard))
             # conv1 writes its 64 channels split, as the DRDB's first four chunks (and as fp32 - the DRDB's residual input - unless lean)
-            if pls[-1].f16 and _CONV1_STENCIL and conv.weight.is_contiguous():
+            if pls[-1].f16 and modes.get("conv1") == "stencil" and conv.weight.is_contiguous():
                 # (r6) Cin = 1: a store-bound stencil, not a K = 9 scalar-gather GEMM (2.4 -> ~1 ms per 64-image launch)
                 xs.append(ops.conv3x3_c1(self._first_channel_nhwc(x), conv.weight, bias=conv.bias, act=PRELU, prelu=slope,
                                          planes=pls[-1], planes_only=lean))

@@ -6,14 +6,54 @@ dimension is dense (stride 1) and whose leading dimensions collapse to `rows` wi
 convs read from and write into concat buffers without copies.
 """
 import ctypes
-import os
-import threading
-import warnings
 
-import torch
+from . import modes as _modes  # (before torch: a misspelt SEGMIF_ variable then fails at once)
 
-from . import _lib
-from ._lib import ACT_GELU, ACT_NONE, ACT_PRELU, ACT_RELU  # noqa: F401
+import torch  # noqa: E402
+
+from . import _lib  # noqa: E402
+from ._lib import ACT_GELU, ACT_NONE, ACT_PRELU, ACT_RELU  # noqa: E402,F401
+from .guard import (Planes16Guard, active_guard, f16x3_enabled, finish_guarded, install_guard, range_fallbacks,  # noqa: E402,F401
+                    range_stats, run_guarded, run_unguarded)
+
+# The arithmetic-mode switches live in modes.py (one table: names, environment variables, values, what each selects).
+# NB `ops.modes` is that module's CONTEXT MANAGER (`with ops.modes(conv3x3="fp32", linear="fp32"): ...`), `segmif_amd.modes` the
+# module itself: `from .ops import modes` and `from . import modes` give different things.
+_mode, modes = _modes.get, _modes.modes
+
+
+def _switch(name):
+    """-> (getter, setter) of one switch of the table, documented by its entry."""
+    def getter():
+        return _modes.get(name)
+
+    def setter(mode):
+        return _modes.set(name, mode)
+    doc = next(m.doc for m in _modes.TABLE if m.name == name)
+    getter.__doc__, setter.__doc__ = doc, doc + "  Returns the previous value."
+    return getter, setter
+
+
+conv3x3_mode, set_conv3x3_mode = _switch("conv3x3")
+linear_mode, set_linear_mode = _switch("linear")
+crosspath_mode, set_crosspath_mode = _switch("crosspath")
+crosspath_arith, set_crosspath_arith = _switch("crosspath_arith")
+attention_mode, set_attention_mode = _switch("attention")
+mixffn_mode, set_mixffn_mode = _switch("mixffn")
+pairs_mode, set_pairs_mode = _switch("pairs")
+_, set_train_conv = _switch("train_conv")
+
+
+def train_conv_f16():
+    return _mode("train_conv") == "f16x3" and _mode("conv3x3") != "fp32"
+
+
+def lazy_seg_mode():
+    return _mode("lazy_seg") == "1"
+
+
+def set_lazy_seg_mode(on):
+    return _modes.set("lazy_seg", "1" if on else "0") == "1"
 
 
 def _stream():
@@ -84,70 +124,6 @@ class SplitWeight:
         self.data, self.N, self.cin, self.f16 = data, N, cin, f16  # f16: the f16x3 image (segmif_conv3x3_split16_pack)
 
 
-_CONV3X3_MODES = ("planes", "planes16", "bf16x6", "fp32")
-_conv3x3_mode = os.environ.get("SEGMIF_CONV3X3", "planes16")
-if _conv3x3_mode not in _CONV3X3_MODES:
-    raise RuntimeError(f"SEGMIF_CONV3X3 must be one of {_CONV3X3_MODES}, got {_conv3x3_mode!r}")
-
-
-_CROSSPATH_MODES = ("gram", "gemm")
-_crosspath_mode = os.environ.get("SEGMIF_CROSSPATH", "gram")
-if _crosspath_mode not in _CROSSPATH_MODES:
-    raise RuntimeError(f"SEGMIF_CROSSPATH must be one of {_CROSSPATH_MODES}, got {_crosspath_mode!r}")
-
-
-def crosspath_mode():
-    return _crosspath_mode
-
-
-# (r6) arithmetic of crosspath_tail's own contractions where it can be f16x3 (lazy segmentation feature, planes-only output, guarded
-# scope): "f16x3" (default) | "bf16x6" (A/B switch, SEGMIF_CROSSPATH_ARITH).  Round 4 had built the same for the kernel that still read
-# x_3 from HBM and measured nothing (HBM-bound then); the lazy tail is bound by its vector + matrix work.
-_crosspath_arith = os.environ.get("SEGMIF_CROSSPATH_ARITH", "f16x3")
-if _crosspath_arith not in ("f16x3", "bf16x6"):
-    raise RuntimeError(f"SEGMIF_CROSSPATH_ARITH must be f16x3 or bf16x6, got {_crosspath_arith!r}")
-
-
-def crosspath_arith():
-    return _crosspath_arith
-
-
-def set_crosspath_arith(mode):
-    global _crosspath_arith
-    if mode not in ("f16x3", "bf16x6"):
-        raise ValueError(mode)
-    prev, _crosspath_arith = _crosspath_arith, mode
-    return prev
-
-
-def set_crosspath_mode(mode):
-    """'gram' (default): CrossPath in inference on the Gram-matrix kernels of csrc/crosspath.hip; 'gemm': round 1's
-    channel_proj GEMMs + fused kv reductions + two-source end_proj GEMM."""
-    global _crosspath_mode
-    if mode not in _CROSSPATH_MODES:
-        raise ValueError(f"mode must be one of {_CROSSPATH_MODES}")
-    prev, _crosspath_mode = _crosspath_mode, mode
-    return prev
-
-
-def conv3x3_mode():
-    return _conv3x3_mode
-
-
-def set_conv3x3_mode(mode):
-    """'bf16x6': 3x3 stride-1 convs with Cin % 16 == 0 run on the bf16 matrix pipe with 3-way split
-    operands (fp32-class accuracy, 2.7x the fp32 MFMA rate); 'planes': the same, and the fusion net's DRDBs and closing
-    convs in inference keep their activations pre-split in a planes buffer (csrc/conv3x3_planes.hip); 'planes16' (default):
-    as 'planes' with half-precision pairs and three products per MAC (f16x3, the same error class at half the matrix
-    work; guarded by Planes16Guard: a forward whose planes leave the half's exponent range is repeated in 'planes');
-    'fp32': exact-fp32 MFMA everywhere.  Training always uses the bf16x6 / fp32 kernels."""
-    global _conv3x3_mode
-    if mode not in _CONV3X3_MODES:
-        raise ValueError(f"mode must be one of {_CONV3X3_MODES}")
-    prev, _conv3x3_mode = _conv3x3_mode, mode
-    return prev
-
-
 def pack_weight_split(w):
     """OIHW 3x3 weight -> SplitWeight (the geometry limits of tile 14 are checked at launch)."""
     N, cin = w.shape[0], w.shape[1]
@@ -177,25 +153,6 @@ def pack_weight_split16(w):
     return SplitWeight(out, N, cin, f16=True)
 
 
-# Arithmetic of the TRAINING path's 3x3 convs (forward + input gradients of the DRDBs): "f16x3" (default, r4) = half pairs x
-# three products with the input scaled into the half's range from device-side range slots; "bf16x6" = round 3's bf16 triples.
-_TRAIN_CONV = os.environ.get("SEGMIF_TRAIN_CONV", "f16x3")
-if _TRAIN_CONV not in ("f16x3", "bf16x6"):
-    raise RuntimeError(f"SEGMIF_TRAIN_CONV must be 'f16x3' or 'bf16x6', got {_TRAIN_CONV!r}")
-
-
-def train_conv_f16():
-    return _TRAIN_CONV == "f16x3" and _conv3x3_mode != "fp32"
-
-
-def set_train_conv(mode):
-    global _TRAIN_CONV
-    if mode not in ("f16x3", "bf16x6"):
-        raise ValueError("mode must be 'f16x3' or 'bf16x6'")
-    prev, _TRAIN_CONV = _TRAIN_CONV, mode
-    return prev
-
-
 RANGE_WORDS = 8  # words per range slot: producers spread their one-atomic-per-workgroup over them, consumers take the maximum
 
 
@@ -214,307 +171,10 @@ def amax_rows(x, slot):
 def pack_conv3x3(w):
     """Packing for a stride-1 'same' 3x3 conv (dilation 1 or 2): the split image when the mode and the
     shape allow it, the fp32 packing otherwise.  Cache entries must be keyed on conv3x3_mode()."""
-    if _conv3x3_mode in ("bf16x6", "planes", "planes16") and w.dim() == 4 and w.shape[2] == 3 and w.shape[3] == 3 and w.shape[1] % 16 == 0 \
+    if _mode("conv3x3") in ("bf16x6", "planes", "planes16") and w.dim() == 4 and w.shape[2] == 3 and w.shape[3] == 3 and w.shape[1] % 16 == 0 \
             and 16 <= w.shape[0] <= 256:
         return pack_weight_split(w)
     return pack_weight(w)
-
-
-class Planes16Guard:
-    """Range bookkeeping of the f16x3 path, PER IMAGE: every producer launch of half pairs folds max |x| of what it wrote
-    into its own row of slots, one slot per batch element (a device-side atomic max; a launch whose batch is not the
-    guard's reports to column 0 and stands for every image).  tripped() reads the rows back (one host sync) and says which
-    images left [2^-13, 65504) somewhere - the range in which a half pair carries an fp32 value to within one bit.  All-zero
-    tensors pass; inf and NaN read as overflow (the slots hold integer maxima of bit patterns: a NaN cannot be dropped).
-    One hole, by construction: the maxima are taken over the HIGH halves' patterns, so a tensor whose every |x| is
-    below 2^-25 (the half's smallest subnormal, rounded) reads 0 like an all-zero tensor and passes; its values are then carried
-    by the low halves alone down to 2^-36 and as zeros below - an ABSOLUTE error of at most 2^-25 |w| per product, i.e. far
-    below fp32's own resolution of anything it is added to, but not the "one bit of fp32" the in-range contract states."""
-    SLOTS = 4096  # (r5: 1024 -> 4096 rows - a pairs LayerNorm takes LN_SUB rows; 1 MB at 64 images, read back once per forward)
-    LO, HI = 2.0 ** -13, 65504.0
-    # (r5) conditioning bound.  crosspath_fold reports, per image and per INTERACTION (the fusion net runs its FeatureFusionModule
-    # twice, in series), kappa = how far a CrossPath context softmax moves per unit RELATIVE perturbation of its Gram matrix
-    # (csrc/crosspath.hip).  What the f16x3 convs leave on the features entering an interaction is ~COND_EPS relative; the first
-    # interaction turns it into COND_EPS kappa_1, which the second amplifies again: the estimate of what reaches the fused image is
-    #     est = COND_EPS (kappa_1 + kappa_2 + kappa_1 kappa_2),
-    # and an image with est > COND_BOUND is repeated with the 3x3 convs in exact fp32 (verdict()).  One large kappa alone is
-    # harmless (1e-7 x 2 000 = 2e-4); the inputs on which f16x3 really lost accuracy - over-exposed image-like pairs, 4.6e-3 against
-    # the exact-fp32 path's 1.6e-3 - have BOTH in the hundreds (tools/cond_probe.py: 300 x 366).  The estimate is an upper-ish one
-    # (the probe pattern is not the real error pattern): over 30 calibration pairs at 64 x 96 (profiles/r05_cond_calibration.txt)
-    # every pair whose f16x3 error exceeded 3 x the exact-fp32-conv result's AND 1e-4 sits at est >= 3.5e-3 (the one that breaks
-    # the 1e-3 tolerance at 8.4e-3), while 4 of the 8 pairs above 2e-3 lose nothing and are repeated needlessly (correct, slower);
-    # below the bound the largest f16x3 error is 1.2e-4 and equals the exact-fp32 path's.  At 480 x 640 (r05_cond_fullsize.txt:
-    # mit_b1 / mit_b3, inputs x1 and x4) the contexts are decided - est <= 1.8e-4, f16x3 and exact-fp32 convs agree to 7e-6 on
-    # every pair - and nothing is repeated.  The bench line reports the repeat rate (f16x3_cond_repeat_rate).
-    # (r6) The bound came down from 2e-3 to 2e-4 after a false-negative search at FULL size (tools/cond_search.py,
-    # profiles/r06_cond_search.txt: 224 pairs at 480 x 640 - the bench's generator and image-like inputs at exposures x1 .. x8, hash
-    # weights and per-layer log-uniform weight scales, every pair against the same pair on exact-fp32 MFMA kernels and, where the two
-    # differ by more than 1e-4, against a float64 evaluation of the CPU restatement).  Among the pairs the 2e-3 bound let through, ONE was outside the
-    # tolerance: U[0,1) inputs x 8, kappa = (0, 3 970), estimate 3.97e-4, f16x3 1.53e-3 from the truth where exact fp32 sits at
-    # 6.5e-6.  Over all passed pairs the distance d between the f16x3 and the exact-fp32 result is <= 3.9 x the estimate; at
-    # 2e-4 the largest d among passed pairs is 1.1e-4 (that pair: 1.1e-4 from the truth) and no pair breaks max(1e-3, 1.5 e32).
-    # Price: 12 of the 187 passed pairs of that (adversarial) search and 15 of the 512 pairs of the bench's eight ranks are
-    # repeated (rank 0, the one-GPU headline: none, its largest estimate is 7e-7); a repeat costs ~12 ms + 6.6 ms per pair.
-    COND_EPS = 1.0e-7
-    COND_BOUND = float(os.environ.get("SEGMIF_GUARD_COND_BOUND", "2e-4"))
-
-    def __init__(self, device, images=1):
-        if os.environ.get("SEGMIF_GUARD_PER_IMAGE") == "0":  # A/B switch: one slot per launch, whole-batch repeats (round 3)
-            images = 1
-        self.images = max(1, int(images))
-        # rows 0 .. SLOTS-1: range slots; rows SLOTS, SLOTS + 1: the conditioning words of the first / every later interaction
-        # (one per image; crosspath_fold raises them)
-        self.amax = torch.zeros((self.SLOTS + 2, self.images), device=device, dtype=torch.int32)
-        self.used = 0
-        self.shared = 0  # launches past SLOTS rows: they share the last row (overflow check exact, vanishing-tensor check pooled)
-        self.whole = set()  # rows written by a launch that did not index by image
-        self.interaction = 0  # FeatureFusionModule calls seen by this scope (next_interaction())
-
-    def slot(self, images=None):
-        """-> (device address of the next launch's row of range slots, amax_images for the kernel).  images: the batch the
-        launch will index its slots by; anything but the guard's own count makes it a whole-batch row.  Past SLOTS launches
-        the last row is shared: the overflow check stays exact (a maximum of maxima), only the vanishing-tensor check of those
-        launches is pooled."""
-        if self.used < self.SLOTS:
-            self.used += 1
-        else:
-            self.shared += 1  # (r6, ADVICE r5: counted and reported - range_stats()["slot_rows_shared"])
-            _note_shared_row()
-        row = self.used - 1
-        per_image = images is not None and images == self.images and self.images > 1
-        if not per_image and self.images > 1:
-            self.whole.add(row)
-        return self.amax.data_ptr() + 4 * self.images * row, (self.images if per_image else 1)
-
-    def slot_rows(self, images, n):
-        """-> (address of n CONSECUTIVE rows of range slots, amax_images, rows actually granted): for a launch that spreads its
-        reports (n a power of two).  Near the end of the table a single row is granted."""
-        if self.used + n > self.SLOTS:
-            ptr, nimg = self.slot(images)
-            return ptr, nimg, 1
-        ptr, nimg = self.slot(images)
-        first = self.used - 1
-        for _ in range(n - 1):
-            self.slot(images)
-        assert self.used - 1 == first + n - 1
-        return ptr, nimg, n
-
-    def next_interaction(self):
-        """Called by FeatureFusionModule at the start of each forward inside the scope: the folds that follow report to the
-        conditioning row of that interaction (first / later)."""
-        self.interaction += 1
-
-    def cond_slot(self, images):
-        """-> device address of the conditioning words for a launch over `images` images (segmif_crosspath_fold_f32's `cond`):
-        the row of the running interaction when the launch indexes the guard's batch, else None (a module run on its own with
-        a batch the scope does not know gets no conditioning check)."""
-        if images == self.images:
-            return self.amax.data_ptr() + 4 * self.images * (self.SLOTS + (1 if self.interaction > 1 else 0))
-        return None
-
-    def reset(self):
-        """Forget every launch (a recorded hipGraph re-fills the same rows on each replay)."""
-        self.used = 0
-        self.shared = 0
-        self.interaction = 0
-        self.whole.clear()
-        self.amax.zero_()
-
-    def _read(self):
-        """ONE device read-back: (range maxima of the used rows, conditioning words) as float32."""
-        host = torch.cat((self.amax[:self.used], self.amax[self.SLOTS:self.SLOTS + 2])).cpu().view(torch.float32)
-        return host[:self.used], host[self.used:self.used + 2]
-
-    def maxima(self):
-        return self._read()[0]
-
-    def kappa(self):
-        """-> float tensor (2, images): the largest softmax conditioning figure each image's CrossPath contexts reported in the
-        first interaction (row 0) and in the later one(s) (row 1)."""
-        return self._read()[1]
-
-    def cond_estimate(self, k=None):
-        """-> float tensor (images,): COND_EPS (k1 + k2 + k1 k2), the estimated relative error the f16x3 convs' rounding leaves on
-        the fused image after both interactions (NaN kappa: NaN)."""
-        k = self.kappa() if k is None else k
-        return self.COND_EPS * (k[0] + k[1] + k[0] * k[1])
-
-    def verdict(self):
-        """-> (tripped, saturated): bool tensors (images,).  tripped: some tensor of that image left the half's range (or held
-        inf / NaN) - repeat on bf16x6.  saturated: in range, but the CrossPath context softmaxes are ill-conditioned enough that
-        the f16x3 convs' operand rounding is estimated (cond_estimate) to reach COND_BOUND on the fused image, or their logits
-        are NaN - repeat with the 3x3 convs in exact fp32.  One read-back for both."""
-        m, k = self._read()
-        bad = ~((m == 0) | ((m >= self.LO) & (m < self.HI)))  # NaN fails every comparison: bad
-        out = bad.any(0) if bad.shape[0] else torch.zeros(self.images, dtype=torch.bool)
-        for row in self.whole:
-            if row < bad.shape[0] and bool(bad[row, 0]):
-                out[:] = True
-        sat = ~(self.cond_estimate(k) <= self.COND_BOUND)  # NaN: saturated
-        return out, sat & ~out
-
-    def tripped(self):
-        """-> bool tensor (images,): True where some tensor of that image left the half's range (or held inf / NaN)."""
-        return self.verdict()[0]
-
-    def saturated(self):
-        return self.verdict()[1]
-
-    def ok(self):
-        t, s = self.verdict()
-        return not bool(t.any() or s.any())
-
-
-class _Scope(threading.local):
-    """Per-thread state of the guarded scopes: two threads running forwards in one process must not share a guard."""
-    guard = None     # the Planes16Guard of the running guarded scope (run_guarded), or None
-    suppress = 0     # > 0 while a scope is being repeated on the bf16x6 kernels: nested scopes must not open a guard
-
-
-_scope = _Scope()
-_stats_lock = threading.Lock()
-_stats = {"scopes": 0, "fallbacks": 0, "images": 0, "images_repeated": 0, "images_repeated_fp32conv": 0, "streak": 0,
-          "warned": False, "slot_rows_shared": 0}
-
-
-def _note_shared_row():
-    with _stats_lock:
-        _stats["slot_rows_shared"] += 1
-
-
-def _count(images, repeated, exact=0):
-    """repeated: images computed again on bf16x6 (range); exact: images computed again with the 3x3 convs in fp32 (conditioning)."""
-    with _stats_lock:
-        _stats["scopes"] += 1
-        _stats["images"] += images
-        _stats["images_repeated"] += repeated
-        _stats["images_repeated_fp32conv"] += exact
-        if repeated:
-            _stats["fallbacks"] += 1
-            _stats["streak"] += 1
-            if _stats["streak"] >= 8 and not _stats["warned"]:
-                _stats["warned"] = True
-                warnings.warn("segmif_amd: the f16x3 range guard has tripped in 8 guarded forwards in a row - those images "
-                              "run twice (f16x3, then bf16x6).  Activations outside [2^-13, 65504): consider "
-                              "SEGMIF_CONV3X3=planes SEGMIF_LINEAR=bf16x6 for this model / data.", RuntimeWarning)
-        else:
-            _stats["streak"] = 0
-
-
-def active_guard():
-    return _scope.guard
-
-
-def range_fallbacks():
-    """Guarded scopes in which at least one image was repeated on the bf16x6 kernels."""
-    return _stats["fallbacks"]
-
-
-def range_stats():
-    """-> dict: guarded scopes, scopes with a repeat, images seen, images repeated (f16x3_trip_rate = repeated / seen)."""
-    with _stats_lock:
-        d = {k: _stats[k] for k in ("scopes", "fallbacks", "images", "images_repeated", "images_repeated_fp32conv", "slot_rows_shared")}
-    d["trip_rate"] = d["images_repeated"] / d["images"] if d["images"] else 0.0
-    d["cond_repeat_rate"] = d["images_repeated_fp32conv"] / d["images"] if d["images"] else 0.0
-    return d
-
-
-def f16x3_enabled():
-    return _conv3x3_mode == "planes16" or _linear_mode == "f16x3" or _attention_mode == "f16x3"
-
-
-def run_guarded(fn, device, enabled=None, images=1, redo=None):
-    """Run fn() with the f16x3 kernels available (enabled=None: if a mode asks for them): inside, active_guard() hands every
-    producer of half pairs its row of range slots, one slot per image.  One read-back at the end.  If images left the
-    half's exponent range: with redo given, `redo(out, idx)` recomputes just those batch elements (idx: LongTensor) on the
-    bf16x6 kernels and returns the patched result; without it (or when every image tripped) fn() runs again as a whole,
-    without a guard.  Nested calls join the outer scope (which does the checking); fn must be repeatable."""
-    if enabled is None:
-        enabled = f16x3_enabled()
-    if _scope.guard is not None or _scope.suppress or not enabled:
-        return fn()
-    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-        # (r6, ADVICE r5) a hipGraph capture cannot hold the scope's host read-back: a standalone call recorded by the CALLER's
-        # graph runs on the bf16x6 kernels (no range to guard, capturable); PairForward.capture installs a guard of its own
-        # and checks it after each replay instead
-        _scope.suppress += 1
-        try:
-            return fn()
-        finally:
-            _scope.suppress -= 1
-    _scope.guard = guard = Planes16Guard(device, images)
-    try:
-        out = fn()
-        bad, sat = guard.verdict()
-    finally:
-        _scope.guard = None
-    return finish_guarded(out, bad, sat, fn, device, redo)
-
-
-def _exact_repeat_modes():
-    """What a conditioning repeat switches to, -> the previous modes: the 3x3 convs in exact fp32 (round 5: the over-exposed
-    image-like pair, tools/stats_bisect.py) AND, (r6), CrossPath in its GEMM form.  tools/r6_fn_bisect.py on the pair the full-size
-    search found (U[0,1) x 8, kappa 3 970): with the Gram form the result is 1.5e-3 .. 1.6e-3 from the all-exact-fp32 one WHATEVER the
-    convs / Linears / attention run on (fp32 included), with the GEMM form 2.4e-5 (bf16x6 or fp32 convs alike).  K^T V = Wk G Wv^T
-    takes the Gram matrix's rounding (fp32 sums inside a 1024-pixel run) times the cancellation of Wk y and Wv y; the GEMM form sums
-    k v^T directly (fp32 over 32 rows, fp64 across) - slower (three 128-wide tensors per call), only for the flagged pairs."""
-    return set_conv3x3_mode("fp32"), set_crosspath_mode("gemm")
-
-
-def _restore_modes(prev):
-    set_conv3x3_mode(prev[0])
-    set_crosspath_mode(prev[1])
-
-
-def finish_guarded(out, bad, sat, fn, device, redo=None):
-    """The repeat half of a guarded scope, given its verdict (Planes16Guard.verdict()): images in `bad` left the half's range
-    and are computed again on the bf16x6 kernels; images in `sat` (r5) stayed in range but reported an ill-conditioned CrossPath
-    softmax and are computed again with the 3x3 convs in exact fp32 and (r6) CrossPath in GEMM form (_exact_repeat_modes).  With
-    `redo(out, idx)` only those images run again, else fn() as a whole."""
-    nbad, nsat, n = int(bad.sum()), int(sat.sum()), int(bad.numel())
-    _count(n, nbad, nsat)
-    if nbad == 0 and nsat == 0:
-        return out
-    _scope.suppress += 1
-    try:
-        if redo is None or nbad == n or nsat == n:
-            del out
-            if nsat:  # (a whole-batch repeat serves both kinds: exact convs + GEMM-form CrossPath, everything else on bf16x6)
-                prev = _exact_repeat_modes()
-                try:
-                    return fn()
-                finally:
-                    _restore_modes(prev)
-            return fn()
-        if nbad:
-            out = redo(out, bad.nonzero().flatten().to(device))
-        if nsat:
-            prev = _exact_repeat_modes()
-            try:
-                out = redo(out, sat.nonzero().flatten().to(device))
-            finally:
-                _restore_modes(prev)
-        return out
-    finally:
-        _scope.suppress -= 1
-
-
-def install_guard(guard):
-    """Low-level: make `guard` (or None) the active one WITHOUT run_guarded's read-back, returning the previous one - for a
-    caller that does the read-back itself later (pipeline.PairForward records a hipGraph this way and checks after replay)."""
-    prev, _scope.guard = _scope.guard, guard
-    return prev
-
-
-def run_unguarded(fn, images=1, repeated=None):
-    """fn() on the bf16x6 kernels, counted as a range fallback of `repeated` of `images` images (for a caller that does its
-    own guard handling, and for measurements of the bf16x6 path)."""
-    _count(images, images if repeated is None else repeated)
-    _scope.suppress += 1
-    try:
-        return fn()
-    finally:
-        _scope.suppress -= 1
 
 
 class Planes:
@@ -668,46 +328,9 @@ class GemmSplitWeight:
         self.data, self.N, self.K, self.half, self.pairs = data, N, K, half, pairs
 
 
-_LINEAR_MODES = ("f16x3", "bf16x6", "fp32")
-_linear_mode = os.environ.get("SEGMIF_LINEAR", "f16x3")
-if _linear_mode not in _LINEAR_MODES:
-    raise RuntimeError(f"SEGMIF_LINEAR must be one of {_LINEAR_MODES}, got {_linear_mode!r}")
 GEMM_SPLIT_MIN_ROWS = 2048  # below this the 128-row tiles leave the chip idle; the fp32 tiles with split-K win
-
-
-def linear_mode():
-    return _linear_mode
-
-
-def set_linear_mode(mode):
-    """'f16x3' (default): tall nn.Linear problems on the split-operand GEMM, with half pairs and three products per MAC
-    inside a guarded scope (run_guarded) and bf16 triples / six products outside one; 'bf16x6': always bf16 triples;
-    'fp32': the exact-fp32 MFMA tiles.  Weight caches are keyed on the mode."""
-    global _linear_mode
-    if mode not in _LINEAR_MODES:
-        raise ValueError(f"mode must be one of {_LINEAR_MODES}")
-    prev, _linear_mode = _linear_mode, mode
-    return prev
-
-
-# ---- (r5) PAIRS: activations pre-split by their producer, both GEMM operands by LDS-DMA (csrc/gemm_pairs.hip) ----------------
-_PAIRS = os.environ.get("SEGMIF_GEMM_PAIRS", "on")  # "off": round 4's gemm_split<f16x3> everywhere (A/B switch)
-if _PAIRS not in ("on", "off"):
-    raise RuntimeError(f"SEGMIF_GEMM_PAIRS must be 'on' or 'off', got {_PAIRS!r}")
 LN_SUB = 8             # rows of range slots a pairs LayerNorm spreads its reports over (csrc/rowops.hip, layernorm_pairs_kernel)
 PAIRS_MIN_ROWS = 8192  # below this a transformer block's GEMMs stay on round 4's kernels (fp32 tiles with split-K for the short ones)
-
-
-def pairs_mode():
-    return _PAIRS
-
-
-def set_pairs_mode(mode):
-    global _PAIRS
-    if mode not in ("on", "off"):
-        raise ValueError("mode must be 'on' or 'off'")
-    prev, _PAIRS = _PAIRS, mode
-    return prev
 
 
 class Pairs:
@@ -728,13 +351,13 @@ class Pairs:
 def pairs_block_ok(x):
     """True when a transformer block over tokens x (B, N, C) should run its Linears on gemm_pairs: inside a guarded f16x3 scope,
     C a multiple of 16 and at least 128 (a 128-column tile), enough rows to fill the chip."""
-    return (_PAIRS == "on" and _scope.guard is not None and _linear_mode == "f16x3" and x.dim() == 3 and x.is_contiguous()
+    return (_mode("pairs") == "on" and active_guard() is not None and _mode("linear") == "f16x3" and x.dim() == 3 and x.is_contiguous()
             and x.shape[2] >= 128 and x.shape[2] % 16 == 0 and x.shape[0] * x.shape[1] >= PAIRS_MIN_ROWS and x.data_ptr() % 16 == 0)
 
 
 def _pack_pairs(wc, N, K):
     """The two-plane weight image of gemm_pairs for a contiguous fp32 (N, K) matrix, or None when the kernel cannot take it."""
-    if _PAIRS != "on" or K % 16 or N % 4 or N < 128:
+    if _mode("pairs") != "on" or K % 16 or N % 4 or N < 128:
         return None
     lib = _lib.load()
     img = torch.empty((lib.segmif_gemm_pairs_weight_bytes(N, K),), device=wc.device, dtype=torch.uint8)
@@ -742,11 +365,15 @@ def _pack_pairs(wc, N, K):
     return img
 
 
-def _guard_slot(images):
-    guard = _scope.guard
+def _need_guard(why="PAIRS tensors exist inside a guarded f16x3 scope only (ops.run_guarded / install_guard)"):
+    guard = active_guard()
     if guard is None:
-        raise RuntimeError("PAIRS tensors exist inside a guarded f16x3 scope only (ops.run_guarded / install_guard)")
-    return guard.slot(images)
+        raise RuntimeError(why)
+    return guard
+
+
+def _guard_slot(images):
+    return _need_guard().slot(images)
 
 
 def pairs_from_f32(x):
@@ -773,9 +400,7 @@ def layernorm_pairs(x, gamma, beta, eps):
     out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
     if not aligned16(gamma, beta):
         gamma, beta = gamma.detach().clone(), beta.detach().clone()
-    guard = _scope.guard
-    if guard is None:
-        raise RuntimeError("PAIRS tensors exist inside a guarded f16x3 scope only (ops.run_guarded / install_guard)")
+    guard = _need_guard()
     # (the kernel's waves are short and many: its range reports are spread over LN_SUB consecutive rows of slots)
     amax, nimg, nsub = guard.slot_rows(x.shape[0] if x.dim() == 3 else None, LN_SUB)
     _lib.check(_lib.load().segmif_layernorm_pairs_f32(x.data_ptr(), _req(gamma).data_ptr(), _req(beta).data_ptr(), out.data_ptr(),
@@ -842,29 +467,33 @@ def linear_pairs(xp, packs, N, *, bias=None, act=ACT_NONE, res=None, out=None, p
     return out
 
 
+def _pack_gemm_split(wc, N, K, half):
+    """GemmSplitWeight of a contiguous fp32 (N, K) matrix: the bf16x6 image and, with half, the f16x3 and pairs images."""
+    lib = _lib.load()
+    out = torch.empty((lib.segmif_gemm_split_weight_bytes(N, K),), device=wc.device, dtype=torch.uint8)
+    _lib.check(lib.segmif_gemm_split_pack(wc.data_ptr(), N, K, K, out.data_ptr(), _stream()), "segmif_gemm_split_pack")
+    img16 = pimg = None
+    if half:
+        img16 = torch.empty((lib.segmif_gemm_split16_weight_bytes(N, K),), device=wc.device, dtype=torch.uint8)
+        _lib.check(lib.segmif_gemm_split16_pack(wc.data_ptr(), N, K, K, img16.data_ptr(), _stream()), "segmif_gemm_split16_pack")
+        pimg = _pack_pairs(wc, N, K)
+    return GemmSplitWeight(out, N, K, img16, pimg)
+
+
 def pack_linear(w, half=None):
     """(N, K) Linear weight -> (fp32 packing, GemmSplitWeight or None).  Cache entries must be keyed on linear_mode().
     half: also build the f16x3 image (default: when linear_mode() is 'f16x3'; training passes False - it re-packs per step
     and never runs under a range guard)."""
     packed = pack_weight(w)
     N, K = w.shape[0], w.shape[1]
-    if _linear_mode == "fp32" or w.dim() != 2 or K % 32 or N < 32:
+    if _mode("linear") == "fp32" or w.dim() != 2 or K % 32 or N < 32:
         return packed, None
-    lib = _lib.load()
-    wc = w.detach().contiguous()
-    out = torch.empty((lib.segmif_gemm_split_weight_bytes(N, K),), device=w.device, dtype=torch.uint8)
-    _lib.check(lib.segmif_gemm_split_pack(wc.data_ptr(), N, K, K, out.data_ptr(), _stream()), "segmif_gemm_split_pack")
-    img16 = pimg = None
-    if _linear_mode == "f16x3" if half is None else half:
-        img16 = torch.empty((lib.segmif_gemm_split16_weight_bytes(N, K),), device=w.device, dtype=torch.uint8)
-        _lib.check(lib.segmif_gemm_split16_pack(wc.data_ptr(), N, K, K, img16.data_ptr(), _stream()), "segmif_gemm_split16_pack")
-        pimg = _pack_pairs(wc, N, K)
-    return packed, GemmSplitWeight(out, N, K, img16, pimg)
+    return packed, _pack_gemm_split(w.detach().contiguous(), N, K, _mode("linear") == "f16x3" if half is None else half)
 
 
 def linear_wants_split(rows, N, K):
     """The size rule of linear_auto, for callers that would rather not build a split weight image they will not use."""
-    return _linear_mode != "fp32" and rows >= GEMM_SPLIT_MIN_ROWS and N >= 128 and N % 4 == 0 and K % 32 == 0
+    return _mode("linear") != "fp32" and rows >= GEMM_SPLIT_MIN_ROWS and N >= 128 and N % 4 == 0 and K % 32 == 0
 
 
 def _vec4(t):  # the split GEMM's 16-byte epilogue accesses
@@ -877,7 +506,7 @@ def _gemm_split(a_ptr, rows, K, lda, split, N, bias, act, res, out, images, patc
     orow, oc, ldo = rows_view(out, "out")
     if orow != rows or oc != N or (split.N, split.K) != (N, K):
         raise RuntimeError(f"split GEMM: shapes do not fit (rows {rows}/{orow}, N {N}/{oc}, weight {split.N}x{split.K})")
-    guard = _scope.guard
+    guard = active_guard()
     use16 = split.half is not None and guard is not None
     d = _lib.SegmifGemmSplit()
     d.a, d.w, d.out = a_ptr, (split.half if use16 else split.data).data_ptr(), out.data_ptr()
@@ -915,9 +544,6 @@ def linear_auto(x, packs, N, *, bias=None, act=ACT_NONE, res=None, out=None):
     return _gemm_split(x.data_ptr(), rows, K, lda, split, N, bias, act, res, out, images)
 
 
-_SR_CONV_IGEMM = os.environ.get("SEGMIF_SR_CONV") == "igemm"  # A/B switch: the round-3 path (fp32 implicit-GEMM tiles)
-
-
 def pack_sr_conv(w):
     """(N, C, k, k) weight of a conv the split GEMM can take in patch mode (Attention's spatial-reduction conv: kernel =
     stride; the overlapping patch embeds of stages 2-4) -> (fp32 packing for the igemm tiles, GemmSplitWeight over K = k * k * C
@@ -925,17 +551,9 @@ def pack_sr_conv(w):
     packed = pack_weight(w)
     N, C, k = w.shape[0], w.shape[1], w.shape[2]
     K = k * k * C
-    if _linear_mode == "fp32" or w.dim() != 4 or w.shape[3] != k or C % 32 or N < 32 or packed.shape[1] != K:
+    if _mode("linear") == "fp32" or w.dim() != 4 or w.shape[3] != k or C % 32 or N < 32 or packed.shape[1] != K:
         return packed, None
-    lib = _lib.load()
-    out = torch.empty((lib.segmif_gemm_split_weight_bytes(N, K),), device=w.device, dtype=torch.uint8)
-    _lib.check(lib.segmif_gemm_split_pack(packed.data_ptr(), N, K, K, out.data_ptr(), _stream()), "segmif_gemm_split_pack")
-    img16 = pimg = None
-    if _linear_mode == "f16x3":
-        img16 = torch.empty((lib.segmif_gemm_split16_weight_bytes(N, K),), device=w.device, dtype=torch.uint8)
-        _lib.check(lib.segmif_gemm_split16_pack(packed.data_ptr(), N, K, K, img16.data_ptr(), _stream()), "segmif_gemm_split16_pack")
-        pimg = _pack_pairs(packed, N, K)
-    return packed, GemmSplitWeight(out, N, K, img16, pimg)
+    return packed, _pack_gemm_split(packed, N, K, _mode("linear") == "f16x3")
 
 
 def patch_conv_auto(x, packs, N, k, stride, pad, *, bias=None):
@@ -947,7 +565,7 @@ def patch_conv_auto(x, packs, N, k, stride, pad, *, bias=None):
     OH, OW = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
     rows = B * OH * OW
     if split is None or rows < GEMM_SPLIT_MIN_ROWS or N < 128 or N % 4 or C % 32 or not x.is_contiguous() or x.data_ptr() % 16 \
-            or not _vec4(bias) or _SR_CONV_IGEMM:
+            or not _vec4(bias) or _mode("sr_conv") == "igemm":
         return conv2d(x, packed, N, k, stride=stride, pad=pad, bias=bias)
     out = torch.empty((B, OH, OW, N), device=x.device, dtype=torch.float32)
     return _gemm_split(x.data_ptr(), rows, k * k * C, C, split, N, bias, ACT_NONE, None, out, B, patch=(k, stride, pad, H, W))
@@ -958,27 +576,10 @@ def sr_conv_auto(x, packs, N, sr, *, bias=None):
     return patch_conv_auto(x, packs, N, sr, sr, 0, bias=bias)
 
 
-_MIXFFN = os.environ.get("SEGMIF_MIXFFN", "fused")  # "chain": round 3's LayerNorm -> GEMM -> dwconv+GELU -> GEMM everywhere (A/B switch)
-if _MIXFFN not in ("fused", "chain"):
-    raise RuntimeError(f"SEGMIF_MIXFFN must be 'fused' or 'chain', got {_MIXFFN!r}")
-
-
-def mixffn_mode():
-    return _MIXFFN
-
-
-def set_mixffn_mode(mode):
-    global _MIXFFN
-    if mode not in ("fused", "chain"):
-        raise ValueError("mode must be 'fused' or 'chain'")
-    prev, _MIXFFN = _MIXFFN, mode
-    return prev
-
-
 def mixffn_fusable(C, hidden):
     """The one-kernel Mix-FFN (csrc/mixffn.hip) exists for C = 64 | 128 with the 4x hidden width, on f16x3 operands: it runs
     inside a guarded scope only (the bf16x6 chain is what a tripped pair is repeated on)."""
-    return _MIXFFN == "fused" and C in (64, 128) and hidden == 4 * C and _linear_mode == "f16x3" and _scope.guard is not None
+    return _mode("mixffn") == "fused" and C in (64, 128) and hidden == 4 * C and _mode("linear") == "f16x3" and active_guard() is not None
 
 
 def pack_mixffn(w1, b1, dw9, dwb, w2):
@@ -1010,9 +611,7 @@ def mixffn_fused(x, ln, wimg, b2, H, W):
     _req(x, "x")
     if x.dim() != 3 or not x.is_contiguous() or x.shape[1] != H * W:
         raise RuntimeError("mixffn_fused expects contiguous (B, H*W, C) tokens")
-    guard = _scope.guard
-    if guard is None:
-        raise RuntimeError("mixffn_fused runs on f16x3 operands: call it inside ops.run_guarded (or install_guard)")
+    guard = _need_guard("mixffn_fused runs on f16x3 operands: call it inside ops.run_guarded (or install_guard)")
     B, _, C = x.shape
     lib = _lib.load()
     if wimg.dtype != torch.uint8 or wimg.numel() != lib.segmif_mixffn_weight_bytes(C):
@@ -1434,27 +1033,6 @@ def upsum_act(base, srcs, OH, OW, bias=None, act=ACT_NONE, out=None):
     return out
 
 
-_ATTENTION_MODES = ("f16x3", "bf16x6", "fp32")
-_attention_mode = os.environ.get("SEGMIF_ATTENTION", "f16x3")
-if _attention_mode not in _ATTENTION_MODES:
-    raise RuntimeError(f"SEGMIF_ATTENTION must be one of {_ATTENTION_MODES}, got {_attention_mode!r}")
-
-
-def attention_mode():
-    return _attention_mode
-
-
-def set_attention_mode(mode):
-    """'f16x3' (default): csrc/attention_split.hip on half pairs with three f16 MFMA products per MAC inside a guarded scope
-    (run_guarded), on bf16 triples / six products outside one; 'bf16x6': always bf16 triples (head_dim 64, fp32-class either
-    way); 'fp32': csrc/attention.hip (fp32 MFMA) everywhere.  head_dim 32 always runs the fp32 kernel."""
-    global _attention_mode
-    if mode not in _ATTENTION_MODES:
-        raise ValueError(f"mode must be one of {_ATTENTION_MODES}")
-    prev, _attention_mode = _attention_mode, mode
-    return prev
-
-
 def sr_attention(q, kv, heads, scale, pairs=False):
     """q: (B, N, C) contiguous; kv: (B, Nk, 2C) contiguous (k | v) -> (B, N, C).  pairs=True: return the result as ops.Pairs
     when the f16x3 kernel runs (inside a guarded scope, head_dim 64, N >= 1024), the fp32 tensor otherwise."""
@@ -1467,17 +1045,17 @@ def sr_attention(q, kv, heads, scale, pairs=False):
     out = torch.empty_like(q)
     kptr = kv.data_ptr()
     lib = _lib.load()
-    if hd == 64 and _attention_mode != "fp32" and N >= 1024:  # below that the K/V pack launch outweighs the matrix-pipe gain
+    if hd == 64 and _mode("attention") != "fp32" and N >= 1024:  # below that the K/V pack launch outweighs the matrix-pipe gain
         ws = torch.empty((lib.segmif_sr_attention_split_workspace(B, heads, Nk),), device=q.device, dtype=torch.uint8)
-        guard = _scope.guard
-        if _attention_mode == "f16x3" and guard is not None and pairs:
+        guard = active_guard()
+        if _mode("attention") == "f16x3" and guard is not None and pairs:
             amax, nimg = guard.slot(B)
             oamax, _ = guard.slot(B)
             _lib.check(lib.segmif_sr_attention_split16_pairs_f32(q.data_ptr(), kptr, kptr + 4 * C, out.data_ptr(), ws.data_ptr(), B,
                                                                  heads, N, Nk, hd, C, 2 * C, C, float(scale), amax, oamax, nimg,
                                                                  _stream()), "segmif_sr_attention_split16_pairs_f32")
             return Pairs(out)
-        if _attention_mode == "f16x3" and guard is not None:
+        if _mode("attention") == "f16x3" and guard is not None:
             amax, nimg = guard.slot(B)
             _lib.check(lib.segmif_sr_attention_split16_f32(q.data_ptr(), kptr, kptr + 4 * C, out.data_ptr(), ws.data_ptr(), B, heads,
                                                            N, Nk, hd, C, 2 * C, C, float(scale), amax, nimg, _stream()),
@@ -1575,21 +1153,6 @@ def linattn_fold_bwd(ktv, wend, dweff, dktv, dwend_part, wofs, kofs, scale, head
     return dktv, dwend_part
 
 
-_LAZY_SEG = os.environ.get("SEGMIF_LAZY_SEG", "1") != "0"
-
-
-def lazy_seg_mode():
-    return _LAZY_SEG
-
-
-def set_lazy_seg_mode(on):
-    """A/B switch (env SEGMIF_LAZY_SEG=0): Fusion_Network3_ac.forward_from_features hands CrossPath the LOW-resolution
-    segmentation feature and the kernels resize it as they read (on), or the feature is resized to H x W first (off)."""
-    global _LAZY_SEG
-    prev, _LAZY_SEG = _LAZY_SEG, bool(on)
-    return prev
-
-
 class LazySeg:
     """The segmentation feature CrossPath consumes, NOT yet resized: `low` = (B, ih, iw, 64) contiguous NHWC (conv3 / conv4 already
     applied), to be read as bilinear(low -> H x W) (align_corners = False; core/mix_transformer.py:364-373).  The Gram-form
@@ -1671,7 +1234,7 @@ def crosspath_fold(part, wkv, wend, weff, wofs, kofs, scale):
     if tuple(_req(wkv, "wkv").shape) != (128, 64) or not wkv.is_contiguous():
         raise RuntimeError("crosspath_fold expects the raw contiguous (128, 64) kv weight")
     Nout = wend.shape[0]
-    guard = _scope.guard
+    guard = active_guard()
     cond = guard.cond_slot(B) if guard is not None else None  # (r5) the softmax's conditioning figure, per image
     _lib.check(_lib.load().segmif_crosspath_fold_f32(part.data_ptr(), nblk, wkv.data_ptr(), _req(wend).data_ptr(),
                                                      _req(weff).data_ptr(), B, Nout, wend.stride(0), wofs, weff.stride(1), kofs,
@@ -1727,7 +1290,7 @@ def crosspath_tail(x3, xi, w3, b3, wi, bi, weff, bend, ln, out=None, planes=None
         if planes.f16:
             d.planes_f16 = 1
             d.planes_amax, d.planes_amax_images = planes.guard.slot(B)
-            if lazy and planes_only and _crosspath_arith == "f16x3":
+            if lazy and planes_only and _mode("crosspath_arith") == "f16x3":
                 # (r6) the kernel's own contractions on half pairs: its operands' range goes to a slot of its own
                 d.arith_f16 = 1
                 d.arith_amax, d.arith_amax_images = planes.guard.slot(B)

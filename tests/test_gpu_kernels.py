@@ -497,20 +497,18 @@ def test_sr_attention(ops, B, heads, N, Nk, hd, mode):
     kvh = kv.double().reshape(B, Nk, 2, heads, hd)
     k, v = kvh[:, :, 0].permute(0, 2, 1, 3), kvh[:, :, 1].permute(0, 2, 1, 3)
     ref = (torch.softmax(qh @ k.transpose(-2, -1) * scale, -1) @ v).transpose(1, 2).reshape(B, N, C)
-    prev = ops.attention_mode()
-    ops.set_attention_mode(mode)
     guard = ops.Planes16Guard("cuda", B) if mode == "f16x3" else None
     pg = ops.install_guard(guard)
     try:
-        y = ops.sr_attention(q.cuda(), kv.cuda(), heads, scale)
+        with ops.modes(attention=mode):
+            y = ops.sr_attention(q.cuda(), kv.cuda(), heads, scale)
         y32 = y
         if mode == "f16x3":
             ops.install_guard(None)
-            ops.set_attention_mode("fp32")
-            y32 = ops.sr_attention(q.cuda(), kv.cuda(), heads, scale)
+            with ops.modes(attention="fp32"):
+                y32 = ops.sr_attention(q.cuda(), kv.cuda(), heads, scale)
     finally:
         ops.install_guard(pg)
-        ops.set_attention_mode(prev)
     assert err(y, ref) < TOL
     if mode == "f16x3" and hd == 64 and N >= 1024:
         assert err(y, ref) <= 3.0 * err(y32, ref) + 1e-7, (err(y, ref), err(y32, ref))
@@ -531,17 +529,15 @@ def test_sr_attention_large_logits(ops, mode):
         kv[:, :32, :hd] *= 1.0e-3
         kv[:, 64:, hd:] *= 10.0 ** rnd(1, 36, 1, seed=30, lo=-3, hi=2)
     ref = torch.softmax(q.double() @ kv[..., :hd].double().transpose(-2, -1) * 0.125, -1) @ kv[..., hd:].double()
-    prev = ops.attention_mode()
-    ops.set_attention_mode(mode)
     pg = ops.install_guard(ops.Planes16Guard("cuda", B) if mode == "f16x3" else None)
     try:
-        y = ops.sr_attention(q.cuda(), kv.cuda(), heads, 0.125)
+        with ops.modes(attention=mode):
+            y = ops.sr_attention(q.cuda(), kv.cuda(), heads, 0.125)
         ops.install_guard(None)
-        ops.set_attention_mode("fp32")
-        y32 = ops.sr_attention(q.cuda(), kv.cuda(), heads, 0.125)
+        with ops.modes(attention="fp32"):
+            y32 = ops.sr_attention(q.cuda(), kv.cuda(), heads, 0.125)
     finally:
         ops.install_guard(pg)
-        ops.set_attention_mode(prev)
     assert err(y, ref) < TOL and err(y, ref) <= 3.0 * err(y32, ref) + 1e-7, (err(y, ref), err(y32, ref))
 
 

@@ -310,28 +310,24 @@ def test_fusion_net_on_f16x3_planes_vs_reference_and_fallback(ops, golden_dir):
     gp = _load(golden_dir, "pair_b1_64x96.npz")
     ir, vis, mask = (torch.from_numpy(gp[k]).cuda() for k in ("ir", "vis", "mask"))
     outs = {}
-    prev = ops.conv3x3_mode()
-    try:
-        with torch.no_grad():
-            out0, out1 = net.denoise_net.encoder.forward_fusion(mask)
-            for mode in ("planes16", "fp32"):
-                ops.set_conv3x3_mode(mode)
+    with torch.no_grad():
+        out0, out1 = net.denoise_net.encoder.forward_fusion(mask)
+        for mode in ("planes16", "fp32"):
+            with ops.modes(conv3x3=mode):
                 y = fus.DRDB1(torch.from_numpy(g["drdb_x"]).cuda())
                 assert _rel(y, g["drdb_y"]) < TIGHT, mode
                 yf = fus(ir, vis, out0, out1)
                 assert _rel(yf, gp["y_fused"]) < 5 * TIGHT, mode
                 outs[mode] = (y, yf)
-            assert fus.planes16_fallbacks == 0
-            assert _rel(outs["planes16"][0], outs["fp32"][0].cpu()) < 2e-6
-            # (r6: 7.1e-6 since the CrossPath tail and conv1 run on f16x3 operands under planes16 as well; < 5e-6 before)
-            assert _rel(outs["planes16"][1], outs["fp32"][1].cpu()) < 1.5e-5
-            ops.set_conv3x3_mode("planes16")
-            big = torch.from_numpy(g["drdb_x"]).cuda() * 1.0e6
+        assert fus.planes16_fallbacks == 0
+        assert _rel(outs["planes16"][0], outs["fp32"][0].cpu()) < 2e-6
+        # (r6: 7.1e-6 since the CrossPath tail and conv1 run on f16x3 operands under planes16 as well; < 5e-6 before)
+        assert _rel(outs["planes16"][1], outs["fp32"][1].cpu()) < 1.5e-5
+        big = torch.from_numpy(g["drdb_x"]).cuda() * 1.0e6
+        with ops.modes(conv3x3="planes16"):
             yb = fus.DRDB1(big)
-            ops.set_conv3x3_mode("fp32")
+        with ops.modes(conv3x3="fp32"):
             assert _rel(yb, fus.DRDB1(big).cpu()) < 2e-6
-    finally:
-        ops.set_conv3x3_mode(prev)
 
 
 def test_full_size_b3_pair_on_f16x3_planes_vs_reference_checksum(ops, golden_dir):
@@ -346,13 +342,9 @@ def test_full_size_b3_pair_on_f16x3_planes_vs_reference_checksum(ops, golden_dir
     ir = dw.det_input("b3_ir", (1, 1, H, W)).cuda()
     vis = dw.det_input("b3_vis", (1, 3, H, W)).cuda()
     mask = dw.det_input("b3_mask", (1, 1, H, W)).repeat(1, 3, 1, 1).cuda()
-    prev = ops.set_conv3x3_mode("planes16")
     before = ops.range_fallbacks()
-    try:
-        with torch.no_grad():
-            fused, labels = PairForward(net, fus)(ir, vis, mask)
-    finally:
-        ops.set_conv3x3_mode(prev)
+    with ops.modes(conv3x3="planes16"), torch.no_grad():
+        fused, labels = PairForward(net, fus)(ir, vis, mask)
     assert ops.range_fallbacks() == before
     got = fused.contiguous().reshape(-1)[torch.from_numpy(g["fused_idx"]).cuda()].cpu()
     scale = max(abs(g["fused_stats"][2]), abs(g["fused_stats"][3]))

@@ -178,16 +178,10 @@ def _check_against_oracle(ops, pipe, sd_seg, sd_fus, ir, vis, mask, name):
     e, e_ref = err(fused), err(ref["fused"])
     with torch.no_grad():
         e6 = err(ops.run_unguarded(lambda: pipe._eager_body(ir.cuda(), vis.cuda(), mask.cuda()), images=0, repeated=0)[0])
-        prev = (ops.set_conv3x3_mode("fp32"), ops.set_linear_mode("fp32"), ops.set_attention_mode("fp32"))
-        try:
+        with ops.modes(conv3x3="fp32", linear="fp32", attention="fp32"):
             e32 = err(pipe._eager_body(ir.cuda(), vis.cuda(), mask.cuda())[0])
-            prev_cp = ops.set_crosspath_mode("gemm")  # (r6) the second exact-fp32 formulation: what a conditioning repeat runs
-            try:
+            with ops.modes(crosspath="gemm"):  # (r6) the second exact-fp32 formulation: what a conditioning repeat runs
                 e32g = err(pipe._eager_body(ir.cuda(), vis.cuda(), mask.cuda())[0])
-            finally:
-                ops.set_crosspath_mode(prev_cp)
-        finally:
-            ops.set_conv3x3_mode(prev[0]), ops.set_linear_mode(prev[1]), ops.set_attention_mode(prev[2])
     # labels: exact wherever the truth's top-2 margin clears both the tolerance and the reference's own logit error
     lg64 = ref64["logits"]
     lg_scale = float(lg64.abs().max())
@@ -455,11 +449,8 @@ def test_mixffn_fused_inside_the_encoder(ops, nets, monkeypatch):
     ir, vis, mask = (t.cuda() for t in _inputs(2, 96, 128, 3))
     with torch.no_grad():
         f1, l1 = pipe.eager(ir, vis, mask)
-        prev = ops.set_mixffn_mode("chain")
-        try:
+        with ops.modes(mixffn="chain"):
             f0, l0 = pipe.eager(ir, vis, mask)
-        finally:
-            ops.set_mixffn_mode(prev)
     d = float((f1 - f0).abs().max())
     observed("r4_mixffn_pair_fused_vs_chain", {"max_abs_diff_fused_image": d, "labels_differ": int((l1 != l0).sum())})
     assert not torch.equal(f1, f0) and d < 1e-4

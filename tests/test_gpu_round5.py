@@ -209,17 +209,10 @@ def test_encoder_blocks_on_the_pairs_path(ops, monkeypatch):
     with torch.no_grad():
         with scope(ops, 4) as g_on:
             on = [f.clone() for f in enc.forward_features_nhwc(x)]
-        prev = ops.set_pairs_mode("off")
-        try:
-            with scope(ops, 4) as g_off:
-                off = [f.clone() for f in enc.forward_features_nhwc(x)]
-        finally:
-            ops.set_pairs_mode(prev)
-        prev = ops.set_linear_mode("fp32")
-        try:
+        with ops.modes(pairs="off"), scope(ops, 4) as g_off:
+            off = [f.clone() for f in enc.forward_features_nhwc(x)]
+        with ops.modes(linear="fp32"):
             exact = [f.clone() for f in enc.forward_features_nhwc(x)]
-        finally:
-            ops.set_linear_mode(prev)
     assert not g_on.tripped().any() and not g_off.tripped().any()
     assert g_on.used != g_off.used  # (different producers report: the pairs path is not a no-op)
     errs = {}
@@ -253,12 +246,8 @@ def test_mit_b3_pair_in_batch_on_the_pairs_path_vs_reference(ops, golden_dir):
 
     errs = {}
     for mode in ("on", "off"):
-        prev = ops.set_pairs_mode(mode)
-        try:
-            with torch.no_grad(), scope(ops, 8) as gd:
-                out0, out1 = enc.forward_fusion(mask)
-        finally:
-            ops.set_pairs_mode(prev)
+        with ops.modes(pairs=mode), torch.no_grad(), scope(ops, 8) as gd:
+            out0, out1 = enc.forward_fusion(mask)
         assert not gd.tripped().any()
         errs[mode] = {"out0": sample_err(out0[:1], "out0"), "out1": sample_err(out1[:1], "out1")}
     observed("pairs_path_mit_b3_features_vs_reference", errs)
@@ -330,16 +319,10 @@ def test_ill_conditioned_pair_is_repeated_with_exact_convs(ops):
             raw = pipe._eager_body(ir.cuda(), vis.cuda(), mask.cuda())[0]
         truth = so.pair_forward(sd64[0], sd64[1], ir.double(), vis.double(), mask.double(), "mit_b1", return_all=True)["fused"]
         ref32 = so.pair_forward(sd_seg, sd_fus, ir, vis, mask, "mit_b1", return_all=True)["fused"]  # the reference's fp32 CPU arithmetic
-        prev = (ops.set_conv3x3_mode("fp32"), ops.set_linear_mode("fp32"), ops.set_attention_mode("fp32"))
-        try:
+        with ops.modes(conv3x3="fp32", linear="fp32", attention="fp32"):
             f32 = pipe._eager_body(ir.cuda(), vis.cuda(), mask.cuda())[0]
-            prev_cp = ops.set_crosspath_mode("gemm")
-            try:
+            with ops.modes(crosspath="gemm"):
                 f32_gemm = pipe._eager_body(ir.cuda(), vis.cuda(), mask.cuda())[0]
-            finally:
-                ops.set_crosspath_mode(prev_cp)
-        finally:
-            ops.set_conv3x3_mode(prev[0]), ops.set_linear_mode(prev[1]), ops.set_attention_mode(prev[2])
     bad, sat = g.verdict()
     kap = g.kappa()
     assert not bad.any() and sat.any(), (kap, g.cond_estimate(kap), ops.Planes16Guard.COND_BOUND)
@@ -361,7 +344,7 @@ def test_ill_conditioned_pair_is_repeated_with_exact_convs(ops):
     # (r6) The yardstick is the scatter of float32 itself on this input: three float32 evaluations - the reference's CPU arithmetic
     # (the oracle on float32 weights), the repo's exact-fp32 MFMA kernels with CrossPath in Gram form and in GEMM form - land
     # 1.2e-3 .. 2.5e-3 from the float64 truth, each by its own summation order behind a softmax of condition ~ kappa.  The repeat
-    # (exact-fp32 convs + GEMM-form CrossPath since r6, see ops._exact_repeat_modes) has to sit inside that scatter: not above
+    # (exact-fp32 convs + GEMM-form CrossPath since r6, see guard.finish_guarded) has to sit inside that scatter: not above
     # 1.5 x the worst of the three, and strictly better than the f16x3 result it replaces.
     assert e <= max(TOL, 1.5 * max(e32, e32g, eref)), (e, e32, e32g, eref, e_raw)
     assert e < e_raw or e_raw < TOL, (e, e_raw)
@@ -384,8 +367,7 @@ def test_fused_attention_backward_vs_fp64_autograd(ops, B, N, heads, Nk):
     o.backward(do.double())
     errs = {}
     for mode in ("fused", "materialize"):
-        ag.SrAttentionFn.FUSED = mode == "fused"
-        try:
+        with ops.modes(attn_bwd=mode):
             qg, kvg = q.cuda().requires_grad_(True), kv.cuda().requires_grad_(True)
             out = ag.sr_attention(qg, kvg, heads, scale)
             out.backward(do.cuda())
@@ -393,8 +375,6 @@ def test_fused_attention_backward_vs_fp64_autograd(ops, B, N, heads, Nk):
             if mode == "fused":
                 again_q, again_kv = ops.sr_attention_bwd(qg.detach(), kvg.detach(), out.detach(), do.cuda(), heads, scale)
                 assert torch.equal(again_q, qg.grad) and torch.equal(again_kv, kvg.grad)  # deterministic
-        finally:
-            ag.SrAttentionFn.FUSED = True
         errs[mode] = {"dq": float((qg.grad.double().cpu() - qd.grad).abs().max() / qd.grad.abs().max()),
                       "dkv": float((kvg.grad.double().cpu() - kvd.grad).abs().max() / kvd.grad.abs().max()),
                       "out": float((out.double().cpu() - o.detach()).abs().max() / o.detach().abs().max())}
@@ -537,11 +517,8 @@ def test_pair_forward_with_and_without_the_resized_feature(ops):
     with torch.no_grad():
         feats = seg.denoise_net.encoder.forward_fusion_features(mask3)
         for on in (True, False):
-            prev = ops.set_lazy_seg_mode(on)
-            try:
+            with ops.modes(lazy_seg="1" if on else "0"):
                 outs[on] = fus.forward_from_features(ir, vis, *feats).clone()
-            finally:
-                ops.set_lazy_seg_mode(prev)
     e = float((outs[True] - outs[False]).abs().max() / outs[False].abs().max())
     observed("lazy_seg_pair_forward", e)
     assert e < 2e-5, e

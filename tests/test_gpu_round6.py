@@ -276,11 +276,8 @@ def test_standalone_eval_repeat_for_conditioning_really_runs_exact_convs(ops, mo
     with torch.no_grad():
         monkeypatch.setattr(ops.Planes16Guard, "COND_BOUND", 1e30)  # (small images: the real bound may well ask for the repeat)
         base = fus(ir, vis, o1, o2)
-        prev = (ops.set_conv3x3_mode("fp32"), ops.set_crosspath_mode("gemm"))  # (what a conditioning repeat switches to: ops._exact_repeat_modes)
-        try:
+        with ops.modes(conv3x3="fp32", crosspath="gemm"):  # (what a conditioning repeat switches to: guard.finish_guarded)
             exact = ops.run_unguarded(lambda: fus(ir, vis, o1, o2), images=0, repeated=0)
-        finally:
-            ops.set_conv3x3_mode(prev[0]), ops.set_crosspath_mode(prev[1])
         before = ops.range_stats()["images_repeated_fp32conv"]
         monkeypatch.setattr(ops.Planes16Guard, "COND_BOUND", -1.0)  # every image "ill-conditioned"
         forced = fus(ir, vis, o1, o2)
@@ -364,14 +361,10 @@ def test_crosspath_tail_f16x3_arithmetic_vs_fp64(ops, B, ih, iw, H, W):
     dec = lambda p: (lambda hv: hv[:, :16].double() + hv[:, 16:].double() * 2.0 ** -11)(p.view(torch.float16).view(-1, 32))
 
     def run(arith, x=xi):
-        prev = ops.set_crosspath_arith(arith)
-        try:
-            with scope(ops, B) as g:
-                pl = ops.Planes(B, H, W, 4, "cuda", g)
-                assert ops.crosspath_tail(low, x, None, None, wi, bi, weff, bend, ln, planes=pl, hw=(H, W), planes_only=True, lazy=True) is None
-            return pl, g
-        finally:
-            ops.set_crosspath_arith(prev)
+        with ops.modes(crosspath_arith=arith), scope(ops, B) as g:
+            pl = ops.Planes(B, H, W, 4, "cuda", g)
+            assert ops.crosspath_tail(low, x, None, None, wi, bi, weff, bend, ln, planes=pl, hw=(H, W), planes_only=True, lazy=True) is None
+        return pl, g
 
     p16_, g16 = run("f16x3")
     p6, g6 = run("bf16x6")
@@ -451,11 +444,8 @@ def test_false_negative_of_the_round5_bound_is_now_repeated(ops):
         s1 = ops.range_stats()
         with scope(ops, 1) as g:
             raw = pipe._eager_body(ir, vis, mask)[0]
-        prev = (ops.set_conv3x3_mode("fp32"), ops.set_linear_mode("fp32"), ops.set_attention_mode("fp32"), ops.set_crosspath_mode("gemm"))
-        try:
+        with ops.modes(conv3x3="fp32", linear="fp32", attention="fp32", crosspath="gemm"):
             f32 = ops.run_unguarded(lambda: pipe._eager_body(ir, vis, mask), images=0, repeated=0)[0]
-        finally:
-            ops.set_conv3x3_mode(prev[0]), ops.set_linear_mode(prev[1]), ops.set_attention_mode(prev[2]), ops.set_crosspath_mode(prev[3])
     est = float(g.cond_estimate()[0])
     d_raw, d_guarded = rel(raw, f32), rel(fused, f32)
     observed("r6_false_negative_pair", {"estimate": est, "f16x3_unrepeated_vs_fp32_mfma": d_raw, "guarded_vs_fp32_mfma": d_guarded})

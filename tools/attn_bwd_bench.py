@@ -9,7 +9,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from segmif_amd import autograd as ag  # noqa: E402
+from segmif_amd import autograd as ag, ops  # noqa: E402
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 tot = {"fused": 0.0, "materialize": 0.0}
@@ -20,19 +20,18 @@ for name, N, heads, blocks in (("stage1", 19200, 1, 3), ("stage2", 4800, 2, 4), 
     do = torch.randn(B, N, C, device="cuda")
     res = {}
     for mode in ("fused", "materialize", "fused", "materialize"):
-        ag.SrAttentionFn.FUSED = mode == "fused"
-        out = ag.sr_attention(q, kv, heads, 0.125)
-        out.backward(do, retain_graph=True)
-        torch.cuda.synchronize()
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        for _ in range(5):
-            q.grad = kv.grad = None
+        with ops.modes(attn_bwd=mode):
+            out = ag.sr_attention(q, kv, heads, 0.125)
             out.backward(do, retain_graph=True)
-        e.record()
-        torch.cuda.synchronize()
+            torch.cuda.synchronize()
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(5):
+                q.grad = kv.grad = None
+                out.backward(do, retain_graph=True)
+            e.record()
+            torch.cuda.synchronize()
         res[mode] = min(res.get(mode, 1e9), s.elapsed_time(e) / 5)
-    ag.SrAttentionFn.FUSED = True
     for m in tot:
         tot[m] += res[m] * blocks
     print(f"{name}: N {N:6d} heads {heads}: fused {res['fused']:.3f} ms, materialising {res['materialize']:.3f} ms per call (x {blocks} blocks)", flush=True)
