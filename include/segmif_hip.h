@@ -759,6 +759,48 @@ int segmif_laploss2_f32(const float* gen, const float* ir, const float* vis, flo
                         int planes, int H, int W, void* stream);
 int segmif_laploss2_bwd_f32(const float* sign3, float* grad, int planes, int H, int W, const float* upstream, void* stream);
 
+/* The other fusion objectives of core/loss.py (:386-397 new_loss_sobel, :423-457 Fusionloss / Fusionloss2, :479-505, :518-603) as one
+ * table-driven kernel pair (csrc/fusion_objective.hip).  gen, ir, vis: single-channel planes (planes, H, W); mask: (planes,
+ * mask_planes, H, W), mask_planes in 1..4.  Term k of a descriptor is
+ *     s_k = sum over pixels of rho( w * (L(gen) - t) )
+ *   op      L: identity, or Sobelxy = |gx| + |gy| (zero padding, core/loss.py:634-650)
+ *   target  t = L(a_ir ir + a_vis vis + a_mask mask_0) (LINEAR), or max(L(ir), L(vis)) (MAX: the a_* are not read)
+ *   weight  w = 1, mask_c or |1 - mask_c|; a weighted term sums over its first mask_channels (1..4, <= mask_planes) mask planes c,
+ *           as torch's broadcast of (B, 3, H, W) * (B, 1, H, W) does.  mask_0 is the plane a_mask reads.
+ *   rho     |.| or (.)^2
+ * ir / vis / mask may be NULL when no term reads them.
+ *   segmif_fusion_objective_f32      sums8[k] = s_k for k < n_terms (0 above); one launch, then a fixed-order sum: deterministic.
+ *                                    partial: 8 * segmif_fusion_objective_blocks(planes, H, W) doubles.
+ *   segmif_fusion_objective_bwd_f32  grad = sum_k coef8[k] ds_k/dgen, recomputed from the inputs (sign(0) = 0); coef8: 8 device
+ *                                    floats, which the caller forms from sums8 and the upstream gradient on the device.
+ * 16-byte row loads when W % 4 == 0 and the planes are 16-byte aligned, scalar ones otherwise.  A descriptor with n_terms
+ * outside 1..8, an unknown enum value or mask_channels outside 1..4 (or above mask_planes) returns SEGMIF_EINVAL; nothing is
+ * launched. */
+#define SEGMIF_OBJ_MAX_TERMS 8
+enum { SEGMIF_OBJ_IDENTITY = 0, SEGMIF_OBJ_SOBEL = 1 };
+enum { SEGMIF_OBJ_TARGET_LINEAR = 0, SEGMIF_OBJ_TARGET_MAX = 1 };
+enum { SEGMIF_OBJ_WEIGHT_ONE = 0, SEGMIF_OBJ_WEIGHT_MASK = 1, SEGMIF_OBJ_WEIGHT_INV_MASK = 2 };
+enum { SEGMIF_OBJ_RHO_ABS = 0, SEGMIF_OBJ_RHO_SQUARE = 1 };
+
+typedef struct {
+  int32_t op, target, weight, rho;
+  float a_ir, a_vis, a_mask;
+  int32_t mask_channels;
+} SegmifObjTerm;
+
+typedef struct {
+  int32_t n_terms;
+  SegmifObjTerm term[SEGMIF_OBJ_MAX_TERMS];
+} SegmifFusionObjective;
+
+int segmif_fusion_objective_blocks(int planes, int H, int W);
+int segmif_fusion_objective_f32(const SegmifFusionObjective* desc, const float* gen, const float* ir, const float* vis,
+                                const float* mask, int mask_planes, double* partial, double* sums8, int planes, int H, int W,
+                                void* stream);
+int segmif_fusion_objective_bwd_f32(const SegmifFusionObjective* desc, const float* gen, const float* ir, const float* vis,
+                                    const float* mask, int mask_planes, const float* coef8, float* grad, int planes, int H, int W,
+                                    void* stream);
+
 /* The fusion net's shared scalar PReLU (core/model_fusion.py:1038) on the training path, kept apart from the conv so
  * that the backward reads the branch off the pre-activation z (any slope, also <= 0): y = z > 0 ? z : a z;
  * dz = dy (z > 0 ? 1 : a), dslope[0] = sum over z <= 0 of dy z (fp64 two-pass).  16-byte path when n % 4 == 0 and the

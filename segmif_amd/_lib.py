@@ -91,6 +91,15 @@ class SegmifAugmentRec(ctypes.Structure):
                 ("taps_x", c_int32), ("taps_y", c_int32), ("reserved", c_int32 * 2)]
 
 
+class SegmifObjTerm(ctypes.Structure):
+    _fields_ = [("op", c_int32), ("target", c_int32), ("weight", c_int32), ("rho", c_int32),
+                ("a_ir", c_float), ("a_vis", c_float), ("a_mask", c_float), ("mask_channels", c_int32)]
+
+
+class SegmifFusionObjective(ctypes.Structure):
+    _fields_ = [("n_terms", c_int32), ("term", SegmifObjTerm * 8)]
+
+
 # name -> (restype, argtypes); must list every symbol include/segmif_hip.h declares
 SIGNATURES = {
     "segmif_abi_version": (c_int, []),
@@ -235,6 +244,11 @@ SIGNATURES = {
     "segmif_ssim_grad_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_float, c_float, c_void_p]),
     "segmif_sobel_l1_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "segmif_sobel_l1_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "segmif_fusion_objective_blocks": (c_int, [c_int, c_int, c_int]),
+    "segmif_fusion_objective_f32": (c_int, [POINTER(SegmifFusionObjective), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                            c_void_p, c_int, c_int, c_int, c_void_p]),
+    "segmif_fusion_objective_bwd_f32": (c_int, [POINTER(SegmifFusionObjective), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                                c_void_p, c_int, c_int, c_int, c_void_p]),
     "segmif_adamw_entry_bytes": (c_int, []),
     "segmif_adamw_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_float, c_float, c_float,
                                c_void_p]),

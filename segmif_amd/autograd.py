@@ -12,7 +12,7 @@ import ctypes
 
 import torch
 
-from . import _lib, modes, ops
+from . import _lib, losses, modes, ops
 from .ops import ACT_GELU, ACT_NONE, ACT_PRELU, ACT_RELU, _req, _stream, rows_view
 
 
@@ -1377,6 +1377,107 @@ class LapLoss2Fn(torch.autograd.Function):
         _lib.check(_lib.load().segmif_laploss2_bwd_f32(sign3.data_ptr(), grad.data_ptr(), planes, H, W, up.data_ptr(), _stream()),
                    "segmif_laploss2_bwd_f32")
         return grad, None, None
+
+
+class SsimFn(torch.autograd.Function):
+    """1 - SSIM(gen, mask) alone (core/loss.py:504): FusionLossGrad3Fn's kernels with the MSE term's coefficient at zero."""
+
+    @staticmethod
+    def forward(ctx, gen, mask):
+        lib = _lib.load()
+        g, m = gen.contiguous(), mask.contiguous()
+        B, C, H, W = g.shape
+        n = g.numel()
+        stack = torch.empty((5, n), device=g.device, dtype=torch.float32)
+        _lib.check(lib.segmif_ssim_prep_f32(g.data_ptr(), m.data_ptr(), stack.data_ptr(), n, _stream()), "segmif_ssim_prep_f32")
+        bl = _blur_planes(stack, 5 * B * C, H, W)
+        need = ctx.needs_input_grad[0]
+        der = torch.empty((3, n), device=g.device, dtype=torch.float32) if need else None
+        part = torch.empty((2 * lib.segmif_loss_blocks(n),), device=g.device, dtype=torch.float64)
+        sums = torch.empty((2,), device=g.device, dtype=torch.float64)
+        _lib.check(lib.segmif_ssim_map_f32(bl.data_ptr(), g.data_ptr(), m.data_ptr(), der.data_ptr() if need else None,
+                                           part.data_ptr(), sums.data_ptr(), n, _stream()), "segmif_ssim_map_f32")
+        ctx.save_for_backward(g, m, der)
+        ctx.geom = (B * C, H, W, n)
+        return (1.0 - sums[0] / n).float()
+
+    @staticmethod
+    def backward(ctx, dloss):
+        g, m, der = ctx.saved_tensors
+        planes, H, W, n = ctx.geom
+        bd = _blur_planes(der, 3 * planes, H, W)
+        grad = torch.empty_like(g)
+        up = dloss.reshape(1).float().contiguous()
+        _lib.check(_lib.load().segmif_ssim_grad_f32(bd.data_ptr(), g.data_ptr(), m.data_ptr(), grad.data_ptr(), n, up.data_ptr(),
+                                                    -1.0 / n, 0.0, _stream()), "segmif_ssim_grad_f32")
+        return grad, None
+
+
+_OBJ_CODES = {"identity": 0, "sobel": 1, "linear": 0, "max": 1, "one": 0, "mask": 1, "inv_mask": 2, "abs": 0, "square": 1}
+_obj_tables = {}
+
+
+def objective_descriptor(terms, mask_planes=1):
+    """The SegmifFusionObjective of a tuple of losses.ObjTerm; a weighted term sums over all mask_planes channels of the mask."""
+    d = _lib.SegmifFusionObjective()
+    d.n_terms = len(terms)
+    for k, t in enumerate(terms[:8]):
+        d.term[k] = _lib.SegmifObjTerm(_OBJ_CODES[t.op], _OBJ_CODES[t.target], _OBJ_CODES[t.weight], _OBJ_CODES[t.rho],
+                                       t.a_ir, t.a_vis, t.a_mask, mask_planes if t.weight != "one" else 1)
+    return d
+
+
+class FusionObjectiveFn(torch.autograd.Function):
+    """losses.fusion_objective on the device (csrc/fusion_objective.hip): one launch for the sums of all terms (+ the fixed-order
+    finish), combine() on their means, and one launch for grad = sum_k coef[k] ds_k/dgen with coef = upstream * dcombine/dmean_k /
+    count_k formed on the device (no host sync: new_loss_sobel's coefficients depend on the sums).  The backward recomputes from
+    the inputs; nothing per term is kept.  ir, vis and mask are data."""
+
+    @staticmethod
+    def forward(ctx, gen, terms, combine, ir, vis, mask):
+        lib = _lib.load()
+        need_ir, need_vis, need_mask = losses.objective_needs(terms)
+        g = gen.contiguous()
+        a = ir.detach().contiguous() if need_ir else None
+        b = vis.detach().contiguous() if need_vis else None
+        m = mask.detach().contiguous() if need_mask else None
+        B, C, H, W = g.shape
+        n, mp, k = g.numel(), (m.shape[1] if need_mask else 1), len(terms)
+        key = (terms, mp, n, g.device)
+        if key not in _obj_tables:  # the descriptor and 1 / (elements a term's mean runs over), once per table and size
+            inv = torch.tensor([1.0 / (n * (mp if t.weight != "one" else 1)) for t in terms], dtype=torch.float64, device=g.device)
+            _obj_tables[key] = (objective_descriptor(terms, mp), inv)
+        desc, inv = _obj_tables[key]
+        nblk = lib.segmif_fusion_objective_blocks(B * C, H, W)
+        part = torch.empty((8 * nblk,), device=g.device, dtype=torch.float64)
+        sums = torch.empty((8,), device=g.device, dtype=torch.float64)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        _lib.check(lib.segmif_fusion_objective_f32(ctypes.byref(desc), g.data_ptr(), ptr(a), ptr(b), ptr(m), mp, part.data_ptr(),
+                                                   sums.data_ptr(), B * C, H, W, _stream()), "segmif_fusion_objective_f32")
+        means = sums[:k] * inv
+        if ctx.needs_input_grad[0]:
+            with torch.enable_grad():
+                s = means.detach().requires_grad_(True)
+                loss = combine(s)
+                (dl,) = torch.autograd.grad(loss, s, allow_unused=True)
+            ctx.save_for_backward(g, a, b, m, (dl if dl is not None else torch.zeros_like(inv)) * inv)
+            ctx.geom = (desc, mp, B * C, H, W, k)
+        else:
+            loss = combine(means)
+        return loss.detach().float()
+
+    @staticmethod
+    def backward(ctx, dloss):
+        g, a, b, m, base = ctx.saved_tensors
+        desc, mp, planes, H, W, k = ctx.geom
+        coef = torch.zeros((8,), device=g.device, dtype=torch.float32)
+        coef[:k] = (dloss.double() * base).float()
+        grad = torch.empty_like(g)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        _lib.check(_lib.load().segmif_fusion_objective_bwd_f32(ctypes.byref(desc), g.data_ptr(), ptr(a), ptr(b), ptr(m), mp,
+                                                               coef.data_ptr(), grad.data_ptr(), planes, H, W, _stream()),
+                   "segmif_fusion_objective_bwd_f32")
+        return grad, None, None, None, None, None
 
 
 # functional front-ends ------------------------------------------------------------------------------

@@ -6,8 +6,12 @@ csrc/rowops.hip; autograd.FusionLossGrad3Fn / FusionLoss3Fn): SURVEY §8(f) N1. 
 (non-fp32, more than one channel, mismatched shapes) are REFUSED like everywhere else in the package - there is no torch /
 MIOpen fallback on the GPU.  The torch formulations below run on CPU tensors only: they are what the CPU tests pin against
 the reference (tests/golden/losses.npz).
+
+fusion_objective is the general form behind the remaining objectives of core/loss.py: a table of up to 8 terms
+mean rho(w (L(gen) - t)) and a function combining their means; one HIP kernel pair (csrc/fusion_objective.hip) serves every table.
 """
 import math
+from typing import NamedTuple
 
 import torch
 import torch.nn.functional as F
@@ -101,3 +105,102 @@ def lap_loss2(generate_img, ir, vis):
         d = [t - F.conv2d(t, w, padding=size // 2, groups=C) for t in (generate_img, ir, vis)]
         total = total + coef * F.l1_loss(d[0], torch.maximum(d[1], d[2]))
     return total
+
+
+def ssim_loss(generate_img, mask):
+    """1 - SSIM(fused, mask) alone (the last term of Fusionloss_grad2, core/loss.py:504)."""
+    if _hip_ok(generate_img, mask):
+        from . import autograd as ag
+        return ag.SsimFn.apply(generate_img, mask.detach())
+    return 1 - ssim(generate_img, mask)
+
+
+# ---- the table-driven objectives (csrc/fusion_objective.hip; core/loss.py:386-397, :423-457, :479-505, :518-603) ------------------
+OBJ_OPS, OBJ_TARGETS, OBJ_WEIGHTS, OBJ_RHOS = ("identity", "sobel"), ("linear", "max"), ("one", "mask", "inv_mask"), ("abs", "square")
+OBJ_MAX_TERMS = 8
+
+
+class ObjTerm(NamedTuple):
+    """mean over pixels (and, for a weighted term, mask channels) of rho(w * (L(gen) - t)):
+    op      L: "identity" | "sobel" (sobel_xy)
+    target  t: "linear" = L(a_ir ir + a_vis vis + a_mask mask[:, :1]) | "max" = max(L(ir), L(vis))
+    weight  w: "one" | "mask" | "inv_mask" = |1 - mask|, broadcast over every channel of the mask
+    rho     "abs" | "square" """
+    op: str = "identity"
+    target: str = "linear"
+    weight: str = "one"
+    rho: str = "abs"
+    a_ir: float = 0.0
+    a_vis: float = 0.0
+    a_mask: float = 0.0
+
+
+def objective_needs(terms):
+    """(ir, vis, mask): which of the data planes the terms read"""
+    ir = any(t.target == "max" or t.a_ir != 0 for t in terms)
+    vis = any(t.target == "max" or t.a_vis != 0 for t in terms)
+    mask = any(t.weight != "one" or (t.target == "linear" and t.a_mask != 0) for t in terms)
+    return ir, vis, mask
+
+
+def _check_terms(terms, ir, vis, mask):
+    if not 1 <= len(terms) <= OBJ_MAX_TERMS:
+        raise ValueError(f"fusion_objective takes 1..{OBJ_MAX_TERMS} terms, got {len(terms)}")
+    for t in terms:
+        if t.op not in OBJ_OPS or t.target not in OBJ_TARGETS or t.weight not in OBJ_WEIGHTS or t.rho not in OBJ_RHOS:
+            raise ValueError(f"fusion_objective: unknown entry in {t}")
+    for name, need, given in zip(("ir", "vis", "mask"), objective_needs(terms), (ir, vis, mask)):
+        if need and given is None:
+            raise ValueError(f"fusion_objective: a term reads {name}, which is None")
+
+
+def objective_means(terms, gen, ir=None, vis=None, mask=None):
+    """The terms' means as a 1-D tensor, written with torch ops in gen's dtype (float64-capable): what CPU tensors get, and what
+    the tests hold the HIP kernel against."""
+    out = []
+    for t in terms:
+        L = sobel_xy if t.op == "sobel" else (lambda z: z)
+        if t.target == "max":
+            tgt = torch.maximum(L(ir), L(vis))
+        else:
+            lin = torch.zeros_like(gen)
+            for a, src in ((t.a_ir, ir), (t.a_vis, vis), (t.a_mask, mask[:, :1] if mask is not None else None)):
+                if a != 0:
+                    lin = lin + a * src
+            tgt = L(lin)
+        e = L(gen) - tgt
+        if t.weight == "mask":
+            e = mask * e
+        elif t.weight == "inv_mask":
+            e = (1 - mask).abs() * e
+        out.append(e.abs().mean() if t.rho == "abs" else (e * e).mean())
+    return torch.stack(out)
+
+
+def _objective_hip_ok(terms, gen, ir, vis, mask):
+    need_ir, need_vis, need_mask = objective_needs(terms)
+    planes = [p for p, need in ((ir, need_ir), (vis, need_vis)) if need]
+    ts = [gen] + planes + ([mask] if need_mask else [])
+    if not any(t.is_cuda for t in ts):
+        return False
+    ok = _hip_ok(gen, *planes)  # (raises for what the kernels do not cover)
+    if need_mask and not (mask.is_cuda and mask.dtype == torch.float32 and mask.dim() == 4 and 1 <= mask.shape[1] <= 4
+                          and mask.shape[:1] + mask.shape[2:] == gen.shape[:1] + gen.shape[2:]):
+        raise RuntimeError("segmif_amd.losses: the fusion-objective kernel takes a float32 device mask of 1..4 channels at the fused "
+                           f"image's size, got {tuple(mask.shape)} {mask.dtype} {mask.device.type} for a fused image "
+                           f"{tuple(gen.shape)} (no torch fallback on the GPU)")
+    if not ok:  # only the mask is on the device
+        raise RuntimeError("segmif_amd.losses: the fusion-objective kernel takes device tensors only (no torch fallback on the GPU)")
+    return True
+
+
+def fusion_objective(terms, combine, gen, ir=None, vis=None, mask=None):
+    """combine(means) for the table `terms` (ObjTerm entries; means: their 1-D tensor) - the general form of the objectives of
+    core/loss.py.  gen, ir, vis: (B, 1, H, W); mask: (B, 1..4, H, W), its channel 0 is what a_mask reads.  On the GPU: one HIP
+    launch for all the sums and one for the gradient (autograd.FusionObjectiveFn); ir, vis and mask are data."""
+    terms = tuple(terms)
+    _check_terms(terms, ir, vis, mask)
+    if _objective_hip_ok(terms, gen, ir, vis, mask):
+        from . import autograd as ag
+        return ag.FusionObjectiveFn.apply(gen, terms, combine, ir, vis, mask)
+    return combine(objective_means(terms, gen, ir, vis, mask))

@@ -110,11 +110,16 @@ class FusionTrainer:
     backward also accumulates `.grad` on every segmentation-net parameter; nothing reads them (the seg phase's
     optimizer.zero_grad() at train.py:225 clears them, checkpoints are state_dicts).  False (default) back-propagates
     THROUGH the segmentation net without forming its weight gradients - same fusion-net update, ~1/5 less device
-    work per step; True reproduces the reference's side effect."""
+    work per step; True reproduces the reference's side effect.
+
+    fusion_loss: None (default) is the reference's schedule - Fusionloss3 in round 1, Fusionloss_grad3 as the intensity term
+    afterwards.  Otherwise a callable (ir, vis_ycrcb, fused, mask3) -> scalar, e.g. any 4-argument objective of core/loss.py or
+    make_fusion_loss(NAME), evaluated in their place; everything around it (the segmentation term, the weights) is unchanged."""
 
     def __init__(self, seg_net, fusion_net, optimizer, criterion, iter_=2, reducer=None, seg_weight_grads=False,
-                 report_lap=False):
+                 report_lap=False, fusion_loss=None):
         self.seg, self.fus, self.opt, self.crit = seg_net, fusion_net, optimizer, criterion
+        self.fusion_loss = fusion_loss  # None: the reference's schedule
         self.iter_ = iter_
         self.reducer = reducer
         self.seg_weight_grads = seg_weight_grads
@@ -151,7 +156,7 @@ class FusionTrainer:
             with torch.no_grad():
                 self.last_lap = losses.lap_loss2(fusion.detach(), ir, vis[:, 0:1])
         if self.iter_ > 1:
-            loss1 = losses.fusion_loss_grad3(fusion, mask3)
+            loss1 = losses.fusion_loss_grad3(fusion, mask3) if self.fusion_loss is None else self.fusion_loss(ir, vis, fusion, mask3)
             fused_rgb = YCrCb2RGB(vis, fusion)  # (train.py:362-365: fused_ycbcr = vis.clone(); fused_ycbcr[:, 0:1] = fusion)
             if self.seg_weight_grads:
                 loss2 = self.seg._loss(fused_rgb, labels, self.crit)
@@ -170,7 +175,7 @@ class FusionTrainer:
                     w0, w1 = float(bw[0]), float(bw[1])
             loss = w0 * loss1 * (0.4 / self.iter_) + w1 * loss2 * 0.8
         else:
-            loss = losses.fusion_loss3(fusion, mask3)
+            loss = losses.fusion_loss3(fusion, mask3) if self.fusion_loss is None else self.fusion_loss(ir, vis, fusion, mask3)
         loss.backward()
         if self.reducer is not None:
             self.reducer.finish()
@@ -203,6 +208,27 @@ def make_fusion_optimizer(fusion_net, iter_, lr=8e-5, weight_decay=0.01, betas=(
     return PolyWarmupAdamW(params=[{"params": list(fusion_net.parameters()), "lr": lr / iter_, "weight_decay": weight_decay}],
                            lr=3e-4 / iter_, weight_decay=weight_decay, betas=list(betas), warmup_iter=3e-5 / iter_, max_iter=max_iter,
                            warmup_ratio=warmup_ratio, power=power)
+
+
+def fusion_loss_names():
+    """the objectives of core/loss.py that --fusion-loss / make_fusion_loss build"""
+    from .core import loss
+    return sorted(n for n in loss.__all__ if n.startswith(("Fusionloss", "Total_fusion_loss", "new_loss_sobel")))
+
+
+def make_fusion_loss(name):
+    """core/loss.py's objective `name` as FusionTrainer's fusion_loss hook (ir, vis_ycrcb, fused, mask3) -> scalar: the classes
+    whose forward takes the mask third and the fused image last (Total_fusion_loss*, new_loss_sobel) are wrapped accordingly;
+    new_loss_sobel, which slices nothing itself, gets the Y plane."""
+    from .core import loss
+    if name not in fusion_loss_names():
+        raise ValueError(f"unknown fusion objective {name!r}; one of {', '.join(fusion_loss_names())}")
+    fn = getattr(loss, name)()
+    if name.startswith("Total_fusion_loss"):
+        return lambda ir, vis, fused, mask3: fn(ir, vis, mask3, fused)
+    if name == "new_loss_sobel":
+        return lambda ir, vis, fused, mask3: fn(ir[:, :1], vis[:, :1], mask3, fused)
+    return fn
 
 
 def _miou(seg, fus, val, batch):
@@ -260,6 +286,9 @@ def main(argv=None):
     ap.add_argument("--warmup-ratio", type=float, default=1e-6, help=ours.strip(" ()"))
     ap.add_argument("--power", type=float, default=1.0, help="polynomial decay" + ours)
     ap.add_argument("--max-iters", type=int, default=160000, help="horizon of both schedules" + ours)
+    ap.add_argument("--fusion-loss", metavar="NAME", help="train the fusion net on this objective of core/loss.py instead of the "
+                    "reference's schedule (Fusionloss3 in round 1, then Fusionloss_grad3 as the intensity term), which is the default. "
+                    "Any objective other than that schedule is this project's choice: the reference's train.py instantiates no other")
     ap.add_argument("--log-iters", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args(argv)
@@ -267,6 +296,8 @@ def main(argv=None):
         raise RuntimeError("segmif_amd.train needs the MI355X device (the HIP path has no CPU fallback)")
     if (args.synthetic is None) == (args.root is None):
         ap.error("give either --root DIR --name-lists DIR or --synthetic N")
+    if args.fusion_loss is not None and args.fusion_loss not in fusion_loss_names():
+        ap.error(f"--fusion-loss {args.fusion_loss}: one of {', '.join(fusion_loss_names())}")
     if args.backbone == "mit_b0":
         ap.error("--backbone mit_b0: Fusion_Network3_ac takes 64/128-channel segmentation features, mit_b0 gives 32/64")
     from .core import Fusion_Network3_ac, Network3
@@ -296,6 +327,9 @@ def main(argv=None):
     sched = dict(weight_decay=args.weight_decay, betas=args.betas, max_iter=args.max_iters, warmup_ratio=args.warmup_ratio, power=args.power)
     loader_kw = dict(batch=batch, crop_size=args.crop_size, rescale_range=tuple(args.rescale_range), fliplr=True)
     best, wrote_seg = None, False
+    fusion_loss = make_fusion_loss(args.fusion_loss) if args.fusion_loss is not None else None
+    if fusion_loss is not None:
+        print(f"[train] --fusion-loss {args.fusion_loss}: NOT the reference's schedule of objectives")
     for iter_ in range(1, args.rounds + 1):
         # ---- fusion phase (train.py:266-413).  Its segmentation net is a freshly built one until round 3 (:307: the checkpoint is
         # loaded only when iter_ > 2), then the best checkpoint so far.
@@ -305,7 +339,8 @@ def main(argv=None):
             seg.load_state_dict(seg_initial)
         elif wrote_seg:
             seg.load_state_dict(torch.load(seg_path, map_location="cuda"))
-        trainer = FusionTrainer(seg, fus, make_fusion_optimizer(fus, iter_, lr=args.lr, **sched), crit, iter_=iter_)
+        trainer = FusionTrainer(seg, fus, make_fusion_optimizer(fus, iter_, lr=args.lr, **sched), crit, iter_=iter_,
+                                fusion_loss=fusion_loss)
         batches = AugmentedBatches(train_set, seed=args.seed + 2 * iter_, **loader_kw)
         n_fus = args.fusion_iters if args.fusion_iters is not None else (6000 if iter_ == 1 else 4000)
         for n in range(n_fus):
