@@ -72,6 +72,8 @@ CONV_CASES = [
     (1, 19, 45, 96, 64, 3, 1, 2, 2, 0),  # dilated, odd width, two 32-channel output tiles, three input chunks (bf16x6 wgrad)
     (3, 40, 70, 160, 32, 3, 1, 2, 2, 1),  # DRDB Dcov4 geometry: several 8x32 tiles per strip, partial tiles on both edges
     (2, 23, 37, 64, 32, 3, 1, 1, 1, 2),  # conv21 geometry, ragged: bf16x6 weight gradient at dilation 1 (funnel-shifted middle tap)
+    (2, 19, 45, 64, 16, 3, 1, 2, 2, 1),  # dilated with N % 32 != 0: wgrad3x3_halo_kernel<2, false> (exact fp32, scalar dy loads)
+    (1, 11, 37, 32, 48, 3, 1, 1, 1, 0),  # N = 48: wgrad3x3_halo_kernel<1, false> with two output-channel tiles, the second partial
 ]
 
 
@@ -96,7 +98,9 @@ def test_conv_backward(ag, case):
         assert err(sg.grad, sr.grad) < 1e-4
 
 
-@pytest.mark.parametrize("rows,C", [(1003, 64), (517, 320), (40, 512), (9000, 128), (333, 32)])
+@pytest.mark.parametrize("rows,C", [(1003, 64), (517, 320), (40, 512), (9000, 128), (333, 32),
+                                    (700, 160), (300, 256),     # C in 132 .. 256: layernorm_bwd_kernel<64, 1>
+                                    (77, 768), (130, 1024)])    # C in 516 .. 1024: layernorm_bwd_kernel<64, 4>
 def test_layernorm_backward(ag, rows, C):
     x, gm, bt, g = rnd(rows, C, seed=9, lo=-3, hi=5), rnd(C, seed=10), rnd(C, seed=11), rnd(rows, C, seed=12)
     xr, gr, br = leaf(x, double=True), leaf(gm, double=True), leaf(bt, double=True)
@@ -472,8 +476,9 @@ def test_hip_gradients_match_reference_autograd_fixtures(ag, golden_dir):
     _golden_grad_check(fus, g, tol=2e-3, sd64=sd64)
 
 
-def test_batchnorm_relu_train_mode(ag):
-    rows, C = 5000, 256
+@pytest.mark.parametrize("rows,C", [(5000, 256), (1003, 768),  # the decoder's widths: four and twelve trips of the 64-column loop
+                                    (300, 36)])                 # the loop's `n < C` tail; ragged last row block in all three
+def test_batchnorm_relu_train_mode(ag, rows, C):
     x, gm, bt, g = rnd(rows, C, seed=60, lo=-2, hi=3), rnd(C, seed=61, lo=0.5, hi=1.5), rnd(C, seed=62), rnd(rows, C, seed=63)
     xr, gr, br = leaf(x, double=True), leaf(gm, double=True), leaf(bt, double=True)
     yr = F.relu(F.batch_norm(xr.t()[None], None, None, gr, br, True, 0.1, 1e-5))[0].t()

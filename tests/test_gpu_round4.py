@@ -497,7 +497,9 @@ def _rel(a, b):
 
 
 @pytest.mark.parametrize("C,with_branch,with_scale,with_ds", [(64, True, True, True), (320, True, False, True), (512, True, True, False),
-                                                              (128, False, False, True), (64, False, False, False)])
+                                                              (128, False, False, True), (64, False, False, False),
+                                                              (160, True, True, True),      # layernorm_bwd_kernel<64, 1>, residual form
+                                                              (1024, True, False, True)])   # layernorm_bwd_kernel<64, 4>, residual form
 def test_add_layernorm_node_vs_fp64_autograd(ops, C, with_branch, with_scale, with_ds):
     """ag.add_layernorm: (s, n) = (x + scale[b] * branch, LayerNorm(s)) forward and backward in one kernel each, against torch
     autograd in fp64 - with and without the branch, the per-sample factor (one sample dropped: factor 0), and a gradient

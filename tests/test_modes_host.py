@@ -223,3 +223,67 @@ def test_integration_md_names_no_unknown_variable():
         if row.startswith("|"):
             named.update(re.findall(r"SEGMIF_[A-Z0-9_]+", row.split("|")[1]))
     assert named and named <= {m.env for m in modes.TABLE} | c_side, named - {m.env for m in modes.TABLE} - c_side
+
+
+def c_side_switches():
+    """{name: [source lines that read it]} for every getenv("SEGMIF_...") in csrc/."""
+    csrc = os.path.join(ROOT, "segmif_amd", "csrc")
+    reads = {}
+    for f in sorted(os.listdir(csrc)):
+        for line in open(os.path.join(csrc, f), errors="replace").read().splitlines():
+            for name in re.findall(r'getenv\("(SEGMIF_[A-Z0-9_]+)"\)', line):
+                reads.setdefault(name, []).append(line)
+    return reads
+
+
+# switches read inside the library that tests/test_gpu_kernel_variants.py need not name, each with its reason
+VARIANTS_EXEMPT = {
+    "SEGMIF_WG3_DBG": "compiled out unless the library is built with -DWG3_DBG=1",
+}
+
+
+def variants_text():
+    return open(os.path.join(ROOT, "tests", "test_gpu_kernel_variants.py")).read()
+
+
+def test_every_library_side_switch_has_a_variants_row_and_a_document_row():
+    """A getenv("SEGMIF_X") added to csrc/ selects kernel code no in-process test can reach: it needs a row in VARIANTS of the
+    kernel-variants GPU test (read as text: this test runs without a device) or an exemption with its reason, and a row in
+    INTEGRATION.md section 4 either way."""
+    reads = c_side_switches()
+    assert len(reads) >= 8
+    table = variants_text()
+    table = table[table.index("def _rows():"):table.index("VARIANTS = _rows()")]
+    missing = [n for n in reads if f'"{n}"' not in table and n not in VARIANTS_EXEMPT]
+    assert not missing, f"no row in VARIANTS of tests/test_gpu_kernel_variants.py: {missing}"
+    assert set(VARIANTS_EXEMPT) <= set(reads), "an exemption for a switch that is no longer read"
+    assert not [n for n in VARIANTS_EXEMPT if f'"{n}"' in table], "exempt and in the table"
+    documented = set()
+    for row in section4().splitlines():
+        if row.startswith("|"):
+            documented.update(re.findall(r"SEGMIF_[A-Z0-9_]+", row.split("|")[1]))
+    assert not set(reads) - documented - set(VARIANTS_EXEMPT), set(reads) - documented
+
+
+def test_variants_rows_name_switches_and_values_the_library_reads():
+    """The other direction: every switch a VARIANTS row sets is read by a getenv() in csrc/, and a value that the library
+    compares as text stands on the line that reads it (strcmp(e, "direct"), e[0] == '0') - for the two switches whose effect cannot
+    be seen from outside the kernel (GEMM_EPI, GEMM_PAIRS_SADDR) this is the only check of the spelling."""
+    reads = c_side_switches()
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    try:
+        import test_gpu_kernel_variants as tv
+    finally:
+        sys.path.remove(os.path.join(ROOT, "tests"))
+    seen = set()
+    for group, env, case, must, must_not in tv.VARIANTS:
+        for name, value in env.items():
+            assert name in reads, name
+            lines = " ".join(reads[name])
+            assert "atoi(e)" in lines and value.isdigit() or f'"{value}"' in lines or f"e[0] == '{value}'" in lines, (name, value)
+            seen.add(name)
+        assert (group is None) == (case is None)
+    assert seen == set(reads) - set(VARIANTS_EXEMPT)
+    for group in ("A", "B"):
+        assert tv.group_env(group)  # (asserts one value per switch within a group)
+    assert not set(tv.group_env("A")) & {"SEGMIF_PLANES_SUB"} and not set(tv.group_env("B")) & {"SEGMIF_PLANES_LEAN"}  # they interact
