@@ -47,6 +47,7 @@
 
 #include "igemm_common.h"
 #include "split_ops.h"
+#include "weight_pack.h"
 #include "segmif_hip.h"
 
 #ifndef PLANES_DBG
@@ -971,62 +972,24 @@ __global__ void planes_zero_border_kernel(unsigned char* __restrict__ planes, in
   }
 }
 
-// fp32 [N][ldw] (k = tap * Cin + c, taps = 9 | 1) -> [chunk][tap][n][96 B]: plane-major, half-swapped rows
-__global__ void planes_pack_weight_kernel(const float* __restrict__ w, int N, int Cin, int taps, int ldw, long long total,
-                                          uint16_t* __restrict__ out) {
-  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  const int j = (int)(idx & 15);
-  long long t = idx >> 4;
-  const int n = (int)(t % N); t /= N;
-  const int tap = (int)(t % taps);
-  const int chunk = (int)(t / taps);
-  const float x = w[(long long)n * ldw + tap * Cin + chunk * 16 + sigma16(j)];
-  uint32_t p0, p1, p2;
-  bf3::split3(x, 0.f, p0, p1, p2);
-  const int f = (n >> 4) & 1;
-  const long long row = ((long long)chunk * taps + tap) * N + n;
-  uint16_t* dst = out + row * 48 + (((j >> 3) ^ f) * 8) + (j & 7);
-  dst[0] = (uint16_t)(p0 & 0xffffu);
-  dst[16] = (uint16_t)(p1 & 0xffffu);
-  dst[32] = (uint16_t)(p2 & 0xffffu);
-}
-
-// f16x3 weights.  Row scale: one wave per output row n finds max |w[n][.]| and stores 2^-e(n) with
-// 2^14 <= 2^e(n) max < 2^15 (e = 0 for an all-zero or vanishing row).
-__global__ void planes16_weight_scale_kernel(const float* __restrict__ w, int K, int ldw, float* __restrict__ inv_scale) {
-  const int n = blockIdx.x;
-  float mx = 0.f;
-  for (int k = threadIdx.x; k < K; k += 64) mx = fmaxf(mx, fabsf(w[(long long)n * ldw + k]));
-  mx = p16::wave_max(mx);
-  if (threadIdx.x == 0) {
-    int e = 0;
-    if (mx >= 1e-30f && mx <= 3e38f) e = 14 - (int)((__float_as_uint(mx) >> 23) - 127);
-    inv_scale[n] = ldexpf(1.f, -e);
+// The weight image (weight_pack.h): fp32 [N][ldw] (k = tap * Cin + c, taps = 9 | 1) -> [chunk][tap][n][96 B]: plane-major,
+// half-swapped rows.  bf16x6: the three bf16 planes; f16x3: W0 | Wl | W0s of the row scaled by 2^e(n), then N floats 2^-e(n).
+struct PlanesWeightLayout {
+  static constexpr int PLANES = 3;
+  int N, Cin, taps;
+  int npad() const { return N; }
+  long long elements() const { return (long long)N * Cin * taps; }
+  __device__ PackSlot slot(long long idx) const {
+    const int j = (int)(idx & 15);
+    long long t = idx >> 4;
+    const int n = (int)(t % N); t /= N;
+    const int tap = (int)(t % taps);
+    const int chunk = (int)(t / taps);
+    const int f = (n >> 4) & 1;
+    const long long d = (((long long)chunk * taps + tap) * N + n) * 48 + (((j >> 3) ^ f) * 8) + (j & 7);
+    return {n, tap * Cin + chunk * 16 + sigma16(j), {d, d + 16, d + 32}, -1};
   }
-}
-
-// fp32 [N][ldw] (k = tap * Cin + c) -> [chunk][tap][n][96 B]: planes W0 | Wl | W0s of the scaled row, half-swapped rows
-__global__ void planes16_pack_weight_kernel(const float* __restrict__ w, int N, int Cin, int taps, int ldw, long long total,
-                                            const float* __restrict__ inv_scale, uint16_t* __restrict__ out) {
-  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  const int j = (int)(idx & 15);
-  long long t = idx >> 4;
-  const int n = (int)(t % N); t /= N;
-  const int tap = (int)(t % taps);
-  const int chunk = (int)(t / taps);
-  const float x = w[(long long)n * ldw + tap * Cin + chunk * 16 + sigma16(j)] * (1.f / inv_scale[n]);  // exact: power of two
-  const _Float16 w0 = (_Float16)x;
-  const _Float16 wl = (_Float16)(x - (float)w0);
-  const _Float16 ws = (_Float16)((float)w0 * (1.f / LSCALE));
-  const int f = (n >> 4) & 1;
-  const long long row = ((long long)chunk * taps + tap) * N + n;
-  uint16_t* dst = out + row * 48 + (((j >> 3) ^ f) * 8) + (j & 7);
-  dst[0] = __builtin_bit_cast(uint16_t, w0);
-  dst[16] = __builtin_bit_cast(uint16_t, wl);
-  dst[32] = __builtin_bit_cast(uint16_t, ws);
-}
+};
 
 }  // namespace
 }  // namespace segmif
@@ -1120,11 +1083,8 @@ extern "C" int64_t segmif_planes_weight_bytes(int N, int Cin, int taps) {
 }
 
 extern "C" int segmif_planes_pack_weight(const float* packed, int N, int Cin, int taps, int ldw, void* out, void* stream) {
-  if (!packed || !out || segmif_planes_weight_bytes(N, Cin, taps) == 0 || ldw < taps * Cin) return SEGMIF_EINVAL;
-  const long long total = (long long)N * Cin * taps;
-  hipLaunchKernelGGL(planes_pack_weight_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     packed, N, Cin, taps, ldw, total, (uint16_t*)out);
-  return (int)hipGetLastError();
+  return pack_weight<Bf16x6>({packed, N, taps * Cin, ldw}, PlanesWeightLayout{N, Cin, taps}, segmif_planes_weight_bytes(N, Cin, taps), out,
+                             (hipStream_t)stream);
 }
 
 extern "C" int64_t segmif_planes16_weight_bytes(int N, int Cin, int taps) {
@@ -1133,14 +1093,8 @@ extern "C" int64_t segmif_planes16_weight_bytes(int N, int Cin, int taps) {
 }
 
 extern "C" int segmif_planes16_pack_weight(const float* packed, int N, int Cin, int taps, int ldw, void* out, void* stream) {
-  if (!packed || !out || segmif_planes_weight_bytes(N, Cin, taps) == 0 || ldw < taps * Cin) return SEGMIF_EINVAL;
-  const long long total = (long long)N * Cin * taps;
-  float* inv_scale = reinterpret_cast<float*>((unsigned char*)out + total * 6);
-  hipLaunchKernelGGL(planes16_weight_scale_kernel, dim3((unsigned)N), dim3(64), 0, (hipStream_t)stream, packed, taps * Cin, ldw,
-                     inv_scale);
-  hipLaunchKernelGGL(planes16_pack_weight_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     packed, N, Cin, taps, ldw, total, inv_scale, (uint16_t*)out);
-  return (int)hipGetLastError();
+  return pack_weight<F16x3>({packed, N, taps * Cin, ldw}, PlanesWeightLayout{N, Cin, taps}, segmif_planes16_weight_bytes(N, Cin, taps), out,
+                            (hipStream_t)stream);
 }
 
 static int conv3x3_planes_impl(const SegmifConvPlanes* d, bool f16, uint32_t* amax, int amax_images, void* stream);

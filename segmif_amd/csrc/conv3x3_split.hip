@@ -55,6 +55,7 @@
 
 #include "igemm_common.h"
 #include "split_ops.h"
+#include "weight_pack.h"
 #include "segmif_hip.h"
 
 #ifndef SPLIT_INTERLEAVE
@@ -404,64 +405,27 @@ int launch(const IgemmK& k, hipStream_t stream) {
   return (int)hipGetLastError();
 }
 
-// packed fp32 [N][ldw] (k = tap * Cin + c)  ->  [n-tile][chunk][tap][n][plane][16] bf16
-__global__ void split_pack_kernel(const float* __restrict__ w, int N, int Cin, int ldw, int NOUT, long long total,
-                                  uint16_t* __restrict__ out) {
-  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  const int nchunks = Cin / 16;
-  const int c16 = (int)(idx & 15);
-  long long t = idx >> 4;
-  const int n = (int)(t % NOUT); t /= NOUT;
-  const int tap = (int)(t % 9); t /= 9;
-  const int chunk = (int)(t % nchunks);
-  const int nt = (int)(t / nchunks);
-  const int gn = nt * NOUT + n;
-  const float x = gn < N ? w[(long long)gn * ldw + tap * Cin + chunk * 16 + c16] : 0.f;
-  uint32_t p0, p1, p2;
-  bf3::split3(x, 0.f, p0, p1, p2);
-  const long long row = (((long long)nt * nchunks + chunk) * 9 + tap) * NOUT + n;
-  out[row * 48 + c16] = (uint16_t)(p0 & 0xffffu);
-  out[row * 48 + 16 + c16] = (uint16_t)(p1 & 0xffffu);
-  out[row * 48 + 32 + c16] = (uint16_t)(p2 & 0xffffu);
-}
-
-// f16x3 weights: [n-tile][chunk][tap][n][W0 | Wl | 2^-11 W0][16] halves of the row scaled by 2^e(n), then one float per
-// padded output channel: 2^-e(n)  (2^14 <= 2^e(n) max|w[n][.]| < 2^15; e = 0 for an all-zero row)
-__global__ void split16_scale_kernel(const float* __restrict__ w, int N, int K, int ldw, int Npad, float* __restrict__ inv_scale) {
-  const int n = blockIdx.x;
-  float mx = 0.f;
-  if (n < N)
-    for (int k = threadIdx.x; k < K; k += 64) mx = fmaxf(mx, fabsf(w[(long long)n * ldw + k]));
-  mx = p16::wave_max(mx);
-  if (threadIdx.x == 0 && n < Npad) {
-    int e = 0;
-    if (mx >= 1e-30f && mx <= 3e38f) e = 14 - (int)((__float_as_uint(mx) >> 23) - 127);
-    inv_scale[n] = ldexpf(1.f, -e);
+// The weight image (weight_pack.h): packed fp32 [N][ldw] (k = tap * Cin + c) -> [n-tile][chunk][tap][n][plane][16] halfwords, rows
+// past N zero.  bf16x6: the three bf16 planes; f16x3: W0 | Wl | 2^-11 W0 of the row scaled by 2^e(n), then one float per padded
+// output channel: 2^-e(n).
+struct SplitLayout {
+  static constexpr int PLANES = 3;
+  int N, Cin, NOUT;
+  int npad() const { return (N + NOUT - 1) / NOUT * NOUT; }
+  long long elements() const { return (long long)npad() * 9 * Cin; }
+  __device__ PackSlot slot(long long idx) const {
+    const int nchunks = Cin / 16;
+    const int c16 = (int)(idx & 15);
+    long long t = idx >> 4;
+    const int n = (int)(t % NOUT); t /= NOUT;
+    const int tap = (int)(t % 9); t /= 9;
+    const int chunk = (int)(t % nchunks);
+    const int nt = (int)(t / nchunks);
+    const int gn = nt * NOUT + n;
+    const long long d = ((((long long)nt * nchunks + chunk) * 9 + tap) * NOUT + n) * 48 + c16;
+    return {gn < N ? gn : -1, tap * Cin + chunk * 16 + c16, {d, d + 16, d + 32}, -1};
   }
-}
-
-__global__ void split16_pack_kernel(const float* __restrict__ w, int N, int Cin, int ldw, int NOUT, long long total,
-                                    const float* __restrict__ inv_scale, uint16_t* __restrict__ out) {
-  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  const int nchunks = Cin / 16;
-  const int c16 = (int)(idx & 15);
-  long long t = idx >> 4;
-  const int n = (int)(t % NOUT); t /= NOUT;
-  const int tap = (int)(t % 9); t /= 9;
-  const int chunk = (int)(t % nchunks);
-  const int nt = (int)(t / nchunks);
-  const int gn = nt * NOUT + n;
-  const float x = gn < N ? w[(long long)gn * ldw + tap * Cin + chunk * 16 + c16] * (1.f / inv_scale[gn]) : 0.f;  // exact: power of two
-  const _Float16 w0 = (_Float16)x;
-  const _Float16 wl = (_Float16)(x - (float)w0);
-  const _Float16 ws = (_Float16)((float)w0 * (1.f / p16::LSCALE));
-  const long long row = (((long long)nt * nchunks + chunk) * 9 + tap) * NOUT + n;
-  out[row * 48 + c16] = __builtin_bit_cast(uint16_t, w0);
-  out[row * 48 + 16 + c16] = __builtin_bit_cast(uint16_t, wl);
-  out[row * 48 + 32 + c16] = __builtin_bit_cast(uint16_t, ws);
-}
+};
 
 // max |x| of a rows view (rows x C, pitch ld) folded into one range slot (IEEE bit pattern; a NaN stays on top)
 __global__ __launch_bounds__(256) void amax_rows_kernel(const float* __restrict__ x, long long rows, int c4n, int rb, int ld,
@@ -516,12 +480,8 @@ extern "C" int64_t segmif_conv3x3_split_weight_bytes(int N, int Cin) {
 }
 
 extern "C" int segmif_conv3x3_split_pack(const float* packed, int N, int Cin, int ldw, void* out, void* stream) {
-  if (!packed || !out || N <= 0 || Cin <= 0 || Cin % 16 || ldw < 9 * Cin) return SEGMIF_EINVAL;
-  const int nout = segmif::split_nout(N);
-  const long long total = (long long)((N + nout - 1) / nout) * nout * 9 * Cin;
-  hipLaunchKernelGGL(segmif::split_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     packed, N, Cin, ldw, nout, total, (uint16_t*)out);
-  return (int)hipGetLastError();
+  const segmif::SplitLayout lay{N, Cin, segmif::split_nout(N)};
+  return segmif::pack_weight<segmif::Bf16x6>({packed, N, 9 * Cin, ldw}, lay, segmif_conv3x3_split_weight_bytes(N, Cin), out, (hipStream_t)stream);
 }
 
 #if SPLIT_DBG & 32
@@ -538,16 +498,8 @@ extern "C" int64_t segmif_conv3x3_split16_weight_bytes(int N, int Cin) {
 }
 
 extern "C" int segmif_conv3x3_split16_pack(const float* packed, int N, int Cin, int ldw, void* out, void* stream) {
-  if (!packed || !out || N <= 0 || Cin <= 0 || Cin % 16 || ldw < 9 * Cin) return SEGMIF_EINVAL;
-  const int nout = segmif::split_nout(N);
-  const int npad = (N + nout - 1) / nout * nout;
-  const long long total = (long long)npad * 9 * Cin;
-  float* inv_scale = reinterpret_cast<float*>((unsigned char*)out + total * 6);
-  hipLaunchKernelGGL(segmif::split16_scale_kernel, dim3((unsigned)npad), dim3(64), 0, (hipStream_t)stream, packed, N, 9 * Cin, ldw, npad,
-                     inv_scale);
-  hipLaunchKernelGGL(segmif::split16_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     packed, N, Cin, ldw, nout, total, inv_scale, (uint16_t*)out);
-  return (int)hipGetLastError();
+  const segmif::SplitLayout lay{N, Cin, segmif::split_nout(N)};
+  return segmif::pack_weight<segmif::F16x3>({packed, N, 9 * Cin, ldw}, lay, segmif_conv3x3_split16_weight_bytes(N, Cin), out, (hipStream_t)stream);
 }
 
 extern "C" int segmif_amax_f32(const float* x, int64_t rows, int C, int ld, uint32_t* slots, int nslots, void* stream) {

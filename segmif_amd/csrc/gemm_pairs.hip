@@ -37,6 +37,7 @@
 #include "device_once.h"
 #include "igemm_common.h"
 #include "split_ops.h"
+#include "weight_pack.h"
 #include "segmif_hip.h"
 
 namespace segmif {
@@ -327,40 +328,26 @@ __global__ __launch_bounds__(WM * 128) __attribute__((amdgpu_waves_per_eu(WM == 
 #endif
 }
 
-// f16x3 row scale 2^-e(n): 2^14 <= 2^e max |w[n][.]| < 2^15 (1 for vanishing rows and for the padding rows)
-__global__ void gemm_pairs_scale_kernel(const float* __restrict__ w, int N, int K, int ldw, float* __restrict__ inv_scale) {
-  const int n = blockIdx.x;  // grid = padded N
-  float mx = 0.f;
-  if (n < N)
-    for (int k = threadIdx.x; k < K; k += 64) mx = fmaxf(mx, fabsf(w[(long long)n * ldw + k]));
-  mx = p16::wave_max(mx);
-  if (threadIdx.x == 0) {
-    int e = 0;
-    if (mx >= 1e-30f && mx <= 3e38f) e = 14 - (int)((__float_as_uint(mx) >> 23) - 127);
-    inv_scale[n] = ldexpf(1.f, -e);
+// The weight image (weight_pack.h): fp32 [N][ldw] -> [n-tile][k-step][128 rows][4 slots x 8 halves]: logical slots
+// W0[0..7] | W0[8..15] | Wl[0..7] | Wl[8..15] of the row scaled by 2^e(n) (Wl = W - W0), slot j stored at j ^ ((row >> 2) & 3); zero
+// filled past N / K; then one float 2^-e(n) per padded output column
+struct GemmPairsLayout {
+  static constexpr int PLANES = 2;
+  int N, K, nks;
+  int npad() const { return (N + PNT - 1) / PNT * PNT; }
+  long long elements() const { return (long long)npad() * nks * PBK; }
+  __device__ PackSlot slot(long long idx) const {
+    const int kk = (int)(idx & 15);
+    long long t = idx >> 4;
+    const int row = (int)(t & 127); t >>= 7;
+    const int ks = (int)(t % nks);
+    const int nt = (int)(t / nks);
+    const int n = nt * PNT + row, k = ks * PBK + kk;
+    const int sw = (row >> 2) & 3;
+    const long long r = (((long long)nt * nks + ks) * PNT + row) * (PROW / 2);
+    return {n < N && k < K ? n : -1, k, {r + ((kk >> 3) ^ sw) * 8 + (kk & 7), r + ((2 | (kk >> 3)) ^ sw) * 8 + (kk & 7), 0}, -1};
   }
-}
-
-// fp32 [N][ldw] -> [n-tile][k-step][128 rows][4 slots x 8 halves]: logical slots W0[0..7] | W0[8..15] | Wl[0..7] | Wl[8..15] of
-// the scaled row (Wl = W - W0), slot j stored at j ^ ((row >> 2) & 3); zero filled past N / K
-__global__ void gemm_pairs_pack_kernel(const float* __restrict__ w, int N, int K, int ldw, int nks, long long total,
-                                       const float* __restrict__ inv_scale, uint16_t* __restrict__ out) {
-  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  const int kk = (int)(idx & 15);
-  long long t = idx >> 4;
-  const int row = (int)(t & 127); t >>= 7;
-  const int ks = (int)(t % nks);
-  const int nt = (int)(t / nks);
-  const int n = nt * PNT + row, k = ks * PBK + kk;
-  const float x = (n < N && k < K) ? w[(long long)n * ldw + k] * (1.f / inv_scale[n]) : 0.f;  // exact: power of two
-  const _Float16 w0 = (_Float16)x;
-  const _Float16 wl = (_Float16)(x - (float)w0);
-  const int sw = (row >> 2) & 3;
-  uint16_t* dst = out + (((long long)nt * nks + ks) * PNT + row) * (PROW / 2);
-  dst[(((kk >> 3)) ^ sw) * 8 + (kk & 7)] = __builtin_bit_cast(uint16_t, w0);
-  dst[((2 | (kk >> 3)) ^ sw) * 8 + (kk & 7)] = __builtin_bit_cast(uint16_t, wl);
-}
+};
 
 // fp32 rows -> pairs rows (a producer for tensors whose own kernel has no pairs epilogue; tests).  One thread = 4 values.
 __global__ __launch_bounds__(256) void pairs_from_f32_kernel(const float* __restrict__ x, long long ldx, unsigned char* __restrict__ y,
@@ -426,14 +413,8 @@ extern "C" int64_t segmif_gemm_pairs_weight_bytes(int N, int K) {
 }
 
 extern "C" int segmif_gemm_pairs_pack(const float* w, int N, int K, int ldw, void* out, void* stream) {
-  if (!w || !out || segmif_gemm_pairs_weight_bytes(N, K) == 0 || ldw < K || ((uintptr_t)out & 15)) return SEGMIF_EINVAL;
-  const int nks = K / PBK, npad = (N + PNT - 1) / PNT * PNT;
-  const long long total = (long long)(npad / PNT) * nks * PNT * PBK;
-  float* inv_scale = reinterpret_cast<float*>((unsigned char*)out + (int64_t)(npad / PNT) * nks * PWSTEP);
-  hipLaunchKernelGGL(gemm_pairs_scale_kernel, dim3((unsigned)npad), dim3(64), 0, (hipStream_t)stream, w, N, K, ldw, inv_scale);
-  hipLaunchKernelGGL(gemm_pairs_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, N, K,
-                     ldw, nks, total, inv_scale, (uint16_t*)out);
-  return (int)hipGetLastError();
+  const GemmPairsLayout lay{N, K, K / PBK};
+  return pack_weight<F16x3>({w, N, K, ldw}, lay, segmif_gemm_pairs_weight_bytes(N, K), out, (hipStream_t)stream, 15);
 }
 
 extern "C" int segmif_pairs_from_f32(const float* x, int64_t ldx, void* y, int64_t ldy_bytes, int64_t rows, int C, uint32_t* amax,

@@ -25,6 +25,7 @@
 
 #include "igemm_common.h"
 #include "split_ops.h"
+#include "weight_pack.h"
 #include "segmif_hip.h"
 
 namespace segmif {
@@ -318,62 +319,25 @@ __global__ __launch_bounds__(256) void gemm_split_kernel(const GemmSplitK p) {
   else epilogue_r6(std::false_type{});
 }
 
-// fp32 [N][ldw] -> [n-tile][k-step][128 rows][K half][plane][16] bf16 with 208-byte rows, zero filled past N / K
-__global__ void gemm_split_pack_kernel(const float* __restrict__ w, int N, int K, int ldw, int nks, long long total,
-                                       uint16_t* __restrict__ out) {
-  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  const int kk = (int)(idx & 31);
-  long long t = idx >> 5;
-  const int row = (int)(t & 127); t >>= 7;
-  const int ks = (int)(t % nks);
-  const int nt = (int)(t / nks);
-  const int n = nt * GBN + row, k = ks * GBK + kk;
-  const float x = (n < N && k < K) ? w[(long long)n * ldw + k] : 0.f;
-  uint32_t p0, p1, p2;
-  bf3::split3(x, 0.f, p0, p1, p2);
-  uint16_t* dst = out + (((long long)nt * nks + ks) * GBM + row) * (GPITCH / 2) + (kk >> 4) * 48 + (kk & 15);
-  dst[0] = (uint16_t)(p0 & 0xffffu);
-  dst[16] = (uint16_t)(p1 & 0xffffu);
-  dst[32] = (uint16_t)(p2 & 0xffffu);
-  if (kk < 8) out[(((long long)nt * nks + ks) * GBM + row) * (GPITCH / 2) + 96 + kk] = 0;  // the 16 padding bytes
-}
-
-// f16x3 weights: row scale 2^-e(n) (2^14 <= 2^e max|w[n][.]| < 2^15; 1 for vanishing rows and for the padding rows)
-__global__ void gemm_split16_scale_kernel(const float* __restrict__ w, int N, int K, int ldw, float* __restrict__ inv_scale) {
-  const int n = blockIdx.x;  // grid = padded N
-  float mx = 0.f;
-  if (n < N)
-    for (int k = threadIdx.x; k < K; k += 64) mx = fmaxf(mx, fabsf(w[(long long)n * ldw + k]));
-  mx = p16::wave_max(mx);
-  if (threadIdx.x == 0) {
-    int e = 0;
-    if (mx >= 1e-30f && mx <= 3e38f) e = 14 - (int)((__float_as_uint(mx) >> 23) - 127);
-    inv_scale[n] = ldexpf(1.f, -e);
+// The weight image (weight_pack.h): fp32 [N][ldw] -> [n-tile][k-step][128 rows][K half][plane][16] halfwords with 208-byte rows, zero
+// filled past N / K.  bf16x6: the three bf16 planes; f16x3: W0 | W - W0 | 2^-11 W0 of the scaled row, then one float 2^-e(n) per
+// padded output column.
+struct GemmSplitLayout {
+  static constexpr int PLANES = 3;
+  int N, K, nks;
+  int npad() const { return (N + GBN - 1) / GBN * GBN; }
+  long long elements() const { return (long long)npad() * nks * GBK; }
+  __device__ PackSlot slot(long long idx) const {
+    const int kk = (int)(idx & 31);
+    long long t = idx >> 5;
+    const int row = (int)(t & 127); t >>= 7;
+    const int ks = (int)(t % nks);
+    const int nt = (int)(t / nks);
+    const int n = nt * GBN + row, k = ks * GBK + kk;
+    const long long r = (((long long)nt * nks + ks) * GBM + row) * (GPITCH / 2), d = r + (kk >> 4) * 48 + (kk & 15);
+    return {n < N && k < K ? n : -1, k, {d, d + 16, d + 32}, kk < 8 ? r + 96 + kk : -1};  // (kk < 8: the row's 16 padding bytes)
   }
-}
-
-// same image as gemm_split_pack_kernel with the planes W0 | W - W0 | 2^-11 W0 of the scaled row (halves)
-__global__ void gemm_split16_pack_kernel(const float* __restrict__ w, int N, int K, int ldw, int nks, long long total,
-                                         const float* __restrict__ inv_scale, uint16_t* __restrict__ out) {
-  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  const int kk = (int)(idx & 31);
-  long long t = idx >> 5;
-  const int row = (int)(t & 127); t >>= 7;
-  const int ks = (int)(t % nks);
-  const int nt = (int)(t / nks);
-  const int n = nt * GBN + row, k = ks * GBK + kk;
-  const float x = (n < N && k < K) ? w[(long long)n * ldw + k] * (1.f / inv_scale[n]) : 0.f;  // exact: power of two
-  const _Float16 w0 = (_Float16)x;
-  const _Float16 wl = (_Float16)(x - (float)w0);
-  const _Float16 ws = (_Float16)((float)w0 * (1.f / p16::LSCALE));
-  uint16_t* dst = out + (((long long)nt * nks + ks) * GBM + row) * (GPITCH / 2) + (kk >> 4) * 48 + (kk & 15);
-  dst[0] = __builtin_bit_cast(uint16_t, w0);
-  dst[16] = __builtin_bit_cast(uint16_t, wl);
-  dst[32] = __builtin_bit_cast(uint16_t, ws);
-  if (kk < 8) out[(((long long)nt * nks + ks) * GBM + row) * (GPITCH / 2) + 96 + kk] = 0;  // the 16 padding bytes
-}
+};
 
 }  // namespace
 }  // namespace segmif
@@ -392,12 +356,8 @@ extern "C" int64_t segmif_gemm_split_weight_bytes(int N, int K) {
 }
 
 extern "C" int segmif_gemm_split_pack(const float* w, int N, int K, int ldw, void* out, void* stream) {
-  if (!w || !out || segmif_gemm_split_weight_bytes(N, K) == 0 || ldw < K) return SEGMIF_EINVAL;
-  const int nks = K / GBK;
-  const long long total = (long long)((N + GBN - 1) / GBN) * nks * GBM * GBK;
-  hipLaunchKernelGGL(gemm_split_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, N, K,
-                     ldw, nks, total, (uint16_t*)out);
-  return (int)hipGetLastError();
+  const GemmSplitLayout lay{N, K, K / GBK};
+  return pack_weight<Bf16x6>({w, N, K, ldw}, lay, segmif_gemm_split_weight_bytes(N, K), out, (hipStream_t)stream);
 }
 
 extern "C" int64_t segmif_gemm_split16_weight_bytes(int N, int K) {
@@ -406,14 +366,8 @@ extern "C" int64_t segmif_gemm_split16_weight_bytes(int N, int K) {
 }
 
 extern "C" int segmif_gemm_split16_pack(const float* w, int N, int K, int ldw, void* out, void* stream) {
-  if (!w || !out || segmif_gemm_split_weight_bytes(N, K) == 0 || ldw < K) return SEGMIF_EINVAL;
-  const int nks = K / GBK, npad = (N + GBN - 1) / GBN * GBN;
-  const long long total = (long long)(npad / GBN) * nks * GBM * GBK;
-  float* inv_scale = reinterpret_cast<float*>((unsigned char*)out + segmif_gemm_split_weight_bytes(N, K));
-  hipLaunchKernelGGL(gemm_split16_scale_kernel, dim3((unsigned)npad), dim3(64), 0, (hipStream_t)stream, w, N, K, ldw, inv_scale);
-  hipLaunchKernelGGL(gemm_split16_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, N, K,
-                     ldw, nks, total, inv_scale, (uint16_t*)out);
-  return (int)hipGetLastError();
+  const GemmSplitLayout lay{N, K, K / GBK};
+  return pack_weight<F16x3>({w, N, K, ldw}, lay, segmif_gemm_split16_weight_bytes(N, K), out, (hipStream_t)stream);
 }
 
 static int gemm_split_impl(const SegmifGemmSplit* d, bool f16, uint32_t* amax, int amax_images, void* stream);

@@ -28,6 +28,7 @@
 
 #include "igemm_common.h"
 #include "split_ops.h"
+#include "weight_pack.h"
 #include "segmif_hip.h"
 
 #ifndef MF_DBG
@@ -370,58 +371,35 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
   if (p.amax_g) p16::fold_pat(p.amax_g, slot, slot, amx_g);
 }
 
-// row scale 2^-e(n) of an (N, K) weight: 2^14 <= 2^e max |w[n][.]| < 2^15 (1 for a vanishing row) -> dst[n * stride_hi + ...]
-__global__ void mixffn_scale_kernel(const float* __restrict__ w, int K, float* __restrict__ dst, int group, long long group_stride) {
-  const int n = blockIdx.x;  // written to dst[(n / group) * group_stride + n % group]
-  float mx = 0.f;
-  for (int k = threadIdx.x; k < K; k += 64) mx = fmaxf(mx, fabsf(w[(long long)n * K + k]));
-  mx = p16::wave_max(mx);
-  if (threadIdx.x == 0) {
-    int e = 0;
-    if (mx >= 1e-30f && mx <= 3e38f) e = 14 - (int)((__float_as_uint(mx) >> 23) - 127);
-    dst[(long long)(n / group) * group_stride + n % group] = ldexpf(1.f, -e);
+// The two weight images inside a chunk (weight_pack.h), f16x3: planes W0 | Wl | W0s of the scaled row.
+// fc1 (HID, C) -> chunk n >> 5, row n & 31: position (s, h, e) <- channel C/2 h + 8 s + e; its row scales live in the chunk's floats
+template <int C>
+struct MfFc1Layout {
+  using G = MfGeom<C>;
+  static constexpr int PLANES = 3;
+  int npad() const { return G::HID; }
+  long long elements() const { return (long long)G::HID * C; }
+  __device__ PackSlot slot(long long idx) const {
+    const int n = (int)(idx / C), pos = (int)(idx - (long long)n * C);
+    const int s = pos >> 4, hh = (pos >> 3) & 1, e = pos & 7;
+    const long long r = ((long long)(n >> 5) * G::CHB + (n & 31) * G::P1) / 2;
+    return {n, (C / 2) * hh + 8 * s + e, {r + pos, r + C + pos, r + 2 * C + pos}, pos < 8 ? r + 3 * C + pos : -1};  // (the 16 padding bytes)
   }
-}
-
-__device__ __forceinline__ void mf_put3(unsigned char* row, int plane_bytes, int pos, float x) {
-  const _Float16 w0 = (_Float16)x;
-  const _Float16 wl = (_Float16)(x - (float)w0);
-  const _Float16 ws = (_Float16)((float)w0 * (1.f / p16::LSCALE));
-  reinterpret_cast<_Float16*>(row)[pos] = w0;
-  reinterpret_cast<_Float16*>(row + plane_bytes)[pos] = wl;
-  reinterpret_cast<_Float16*>(row + 2 * plane_bytes)[pos] = ws;
-}
-
-// fc1 (HID, C) -> chunk (n >> 5), row n & 31: planes W0 | Wl | W0s of the scaled row, position (s, h, e) <- channel C/2 h + 8 s + e
+};
+// fc2 (C, HID) -> chunk j = k >> 5, row n: position (s, h, e) <- hidden channel 32 j + 16 s + 8 h + e; row scales behind the chunks
 template <int C>
-__global__ void mixffn_pack1_kernel(const float* __restrict__ w1, unsigned char* __restrict__ out) {
+struct MfFc2Layout {
   using G = MfGeom<C>;
-  const int idx = blockIdx.x * 256 + threadIdx.x;  // one thread per (n, position)
-  if (idx >= G::HID * C) return;
-  const int n = idx / C, pos = idx - n * C;
-  const int s = pos >> 4, hh = (pos >> 3) & 1, e = pos & 7;
-  const int c = (C / 2) * hh + 8 * s + e;
-  unsigned char* chunk = out + (long long)(n >> 5) * G::CHB;
-  const float inv = reinterpret_cast<const float*>(chunk + G::O_F)[G::F_S1 + (n & 31)];
-  const float x = w1[(long long)n * C + c] * (1.f / inv);  // exact: power of two
-  unsigned char* row = chunk + (n & 31) * G::P1;
-  mf_put3(row, 2 * C, pos, x);
-  if (pos < 8) reinterpret_cast<uint16_t*>(row + 6 * C)[pos] = 0;  // the 16 padding bytes
-}
-
-// fc2 (C, HID) -> chunk j = k >> 5, row n: position (s, h, e) <- hidden channel 32 j + 16 s + 8 h + e
-template <int C>
-__global__ void mixffn_pack2_kernel(const float* __restrict__ w2, const float* __restrict__ s2, unsigned char* __restrict__ out) {
-  using G = MfGeom<C>;
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= C * G::HID) return;
-  const int n = idx / G::HID, k = idx - n * G::HID;
-  const int j = k >> 5, pos = k & 31;
-  const float x = w2[(long long)n * G::HID + k] * (1.f / s2[n]);
-  unsigned char* row = out + (long long)j * G::CHB + G::W1B + n * G::P2;
-  mf_put3(row, 64, pos, x);
-  if (pos < 8) reinterpret_cast<uint16_t*>(row + 192)[pos] = 0;
-}
+  static constexpr int PLANES = 3;
+  int npad() const { return C; }
+  long long elements() const { return (long long)C * G::HID; }
+  __device__ PackSlot slot(long long idx) const {
+    const int n = (int)(idx / G::HID), k = (int)(idx - (long long)n * G::HID);
+    const int j = k >> 5, pos = k & 31;
+    const long long r = ((long long)j * G::CHB + G::W1B + n * G::P2) / 2;
+    return {n, k, {r + pos, r + 32 + pos, r + 64 + pos}, pos < 8 ? r + 96 + pos : -1};
+  }
+};
 
 // per-chunk floats: depthwise taps [9][32] (from the [9][HID] packing), depthwise bias, fc1 bias
 template <int C>
@@ -446,12 +424,10 @@ template <int C>
 int pack(const float* w1, const float* b1, const float* dw9, const float* dwb, const float* w2, void* out, hipStream_t s) {
   using G = MfGeom<C>;
   unsigned char* o = (unsigned char*)out;
-  float* s2 = reinterpret_cast<float*>(o + (long long)G::NCH * G::CHB);
-  float* s1_first = reinterpret_cast<float*>(o + G::O_F) + G::F_S1;  // fc1 row scales live inside the chunks
-  hipLaunchKernelGGL(mixffn_scale_kernel, dim3(G::HID), dim3(64), 0, s, w1, C, s1_first, 32, (long long)(G::CHB / 4));
-  hipLaunchKernelGGL(mixffn_scale_kernel, dim3(C), dim3(64), 0, s, w2, G::HID, s2, C, 0ll);
-  hipLaunchKernelGGL(mixffn_pack1_kernel<C>, dim3((G::HID * C + 255) / 256), dim3(256), 0, s, w1, o);
-  hipLaunchKernelGGL(mixffn_pack2_kernel<C>, dim3((C * G::HID + 255) / 256), dim3(256), 0, s, w2, s2, o);
+  const RowScales s1{reinterpret_cast<float*>(o + G::O_F) + G::F_S1, 5, G::CHB / 4};  // fc1 row scales live inside the chunks: 32 per chunk
+  int e = pack_weight<F16x3>({w1, G::HID, C, C}, MfFc1Layout<C>{}, image_bytes<C>(), out, s, 15, s1);
+  if (e == 0) e = pack_weight<F16x3>({w2, C, G::HID, G::HID}, MfFc2Layout<C>{}, image_bytes<C>(), out, s, 15);  // scales: the last C floats
+  if (e != 0) return e;
   hipLaunchKernelGGL(mixffn_pack_consts_kernel<C>, dim3((G::NCH * 11 * 32 + 255) / 256), dim3(256), 0, s, dw9, dwb, b1, o);
   return (int)hipGetLastError();
 }
