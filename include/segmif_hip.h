@@ -801,6 +801,51 @@ int segmif_fusion_objective_bwd_f32(const SegmifFusionObjective* desc, const flo
                                     const float* mask, int mask_planes, const float* coef8, float* grad, int planes, int H, int W,
                                     void* stream);
 
+/* The segmentation objectives of core/loss.py (:342-383 OhemCELoss, SoftmaxFocalLoss, NormalLoss) and torch's class-weighted /
+ * label-smoothed cross entropy as one kernel pair (csrc/seg_objective.hip) over NHWC logits (rows x C, pitch ld >= C, C <= 32) and
+ * int64 labels.  With p = softmax(x), y the label, w = class_weight (C device floats; NULL: all 1) and q = 1 - p_y, formed as
+ * sum_{c != y} e_c / sum_c e_c (the subtraction cancels as p_y -> 1), the per-pixel loss is
+ *   gamma == 0   l = (1 - eps) (-w_y log p_y) + (eps / C) sum_c (-w_c log p_c)      torch's F.cross_entropy(weight, label_smoothing)
+ *   gamma > 0    l = -w_y q^gamma log p_y  (eps must be 0)                           SoftmaxFocalLoss
+ *                dl/dx_c = w_y (delta_cy - p_c) q^gamma (gamma p_y log(p_y) / q - 1), log(p_y) / q = log1p(-q) / q with the limit
+ *                -1 at q = 0: finite for gamma < 1
+ * A pixel whose label equals ignore_index or lies outside [0, C) is ignored: l = 0 and gradient 0 (segmif_softmax_ce_f32's rule).
+ * Reductions:
+ *   SEGMIF_SEG_MEAN_VALID  sum l / sum_valid w_y   nn.CrossEntropyLoss / nn.NLLLoss 'mean'; NaN when no pixel is valid, as torch
+ *   SEGMIF_SEG_MEAN_ALL    sum l / rows            NormalLoss: torch.mean of reduction='none', ignored zeros count
+ *   SEGMIF_SEG_OHEM        OhemCELoss.forward without the sort; ohem_t = -log(thresh) in float32 as the reference forms it.
+ *                          n_gt = #{l > ohem_t}; n_gt >= ohem_n_min: the mean of {l > ohem_t}; otherwise the mean of the ohem_n_min
+ *                          largest l over ALL rows (ignored pixels' zeros included, as the reference sorts the whole view(-1)) =
+ *                          (sum_{l > kappa} l + (n_min - #{l > kappa}) kappa) / n_min, kappa the n_min-th largest l, found by an
+ *                          exact radix select on the device (integer atomics only).
+ * Ties at kappa: pixels with l == kappa share the n_min - #{l > kappa} remaining slots equally (a fractional weight; 1 when the
+ * value is unique; of no effect at kappa = 0, where ignored pixels have gradient 0).  The VALUE is the reference's exactly; the
+ * GRADIENT differs from the reference's arbitrary sort order only when two valid pixels have bit-equal losses.
+ *   segmif_seg_objective_workspace_bytes  bytes of `workspace` (0: rows < 1 or an unknown reduction)
+ *   segmif_seg_objective_f32      record4 = {loss, 1 / denominator, kappa (ohem_t on the threshold branch), tie weight} (device
+ *                                 floats).  For OHEM the workspace keeps the per-pixel l: hand the same workspace to the backward.
+ *   segmif_seg_objective_bwd_f32  dlogits (pitch ldd >= C) = upstream[0] * d loss / d logits, recomputed from the logits, already
+ *                                 scaled; upstream and record4 are read on the device.  workspace may be NULL unless OHEM.
+ * No host synchronisation, no floating-point atomics, fixed-order sums: bit-identical from run to run, capturable in a hipGraph;
+ * every launch is issued whichever OHEM branch the data takes.  16-byte loads when ld == C and the base is 16-byte aligned,
+ * scalar ones otherwise.  SEGMIF_EINVAL before any launch: C < 1 or C > 32, ld < C, gamma < 0, eps outside [0, 1), gamma > 0 with
+ * eps > 0, an unknown reduction, OHEM with n_min < 1, n_min > rows or ohem_t not finite. */
+enum { SEGMIF_SEG_MEAN_VALID = 0, SEGMIF_SEG_MEAN_ALL = 1, SEGMIF_SEG_OHEM = 2 };
+
+typedef struct {
+  float gamma, label_smoothing, ohem_t;
+  int32_t reduction, ignore_index;
+  int32_t reserved;
+  int64_t ohem_n_min;
+} SegmifSegObjective;
+
+int64_t segmif_seg_objective_workspace_bytes(int64_t rows, int reduction);
+int segmif_seg_objective_f32(const SegmifSegObjective* desc, const float* logits, const int64_t* labels, const float* class_weight,
+                             void* workspace, float* record4, int64_t rows, int C, int ld, void* stream);
+int segmif_seg_objective_bwd_f32(const SegmifSegObjective* desc, const float* logits, const int64_t* labels,
+                                 const float* class_weight, const void* workspace, const float* record4, const float* upstream,
+                                 float* dlogits, int64_t rows, int C, int ld, int ldd, void* stream);
+
 /* The fusion net's shared scalar PReLU (core/model_fusion.py:1038) on the training path, kept apart from the conv so
  * that the backward reads the branch off the pre-activation z (any slope, also <= 0): y = z > 0 ? z : a z;
  * dz = dy (z > 0 ? 1 : a), dslope[0] = sum over z <= 0 of dy z (fp64 two-pass).  16-byte path when n % 4 == 0 and the

@@ -100,6 +100,11 @@ class SegmifFusionObjective(ctypes.Structure):
     _fields_ = [("n_terms", c_int32), ("term", SegmifObjTerm * 8)]
 
 
+class SegmifSegObjective(ctypes.Structure):
+    _fields_ = [("gamma", c_float), ("label_smoothing", c_float), ("ohem_t", c_float), ("reduction", c_int32),
+                ("ignore_index", c_int32), ("reserved", c_int32), ("ohem_n_min", c_int64)]
+
+
 # name -> (restype, argtypes); must list every symbol include/segmif_hip.h declares
 SIGNATURES = {
     "segmif_abi_version": (c_int, []),
@@ -249,6 +254,11 @@ SIGNATURES = {
                                             c_void_p, c_int, c_int, c_int, c_void_p]),
     "segmif_fusion_objective_bwd_f32": (c_int, [POINTER(SegmifFusionObjective), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                                 c_void_p, c_int, c_int, c_int, c_void_p]),
+    "segmif_seg_objective_workspace_bytes": (c_int64, [c_int64, c_int]),
+    "segmif_seg_objective_f32": (c_int, [POINTER(SegmifSegObjective), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int,
+                                         c_int, c_void_p]),
+    "segmif_seg_objective_bwd_f32": (c_int, [POINTER(SegmifSegObjective), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "segmif_adamw_entry_bytes": (c_int, []),
     "segmif_adamw_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_float, c_float, c_float,
                                c_void_p]),

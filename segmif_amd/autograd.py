@@ -1480,6 +1480,111 @@ class FusionObjectiveFn(torch.autograd.Function):
         return grad, None, None, None, None, None
 
 
+_SEG_REDUCTIONS = {"mean": 0, "mean_all": 1, "ohem": 2}
+
+
+def seg_objective_descriptor(gamma=0.0, label_smoothing=0.0, ignore_index=255, reduction="mean", ohem_t=0.0, ohem_n_min=0):
+    """The SegmifSegObjective of losses.SegObjective's settings (ohem_t = -log(thresh))."""
+    d = _lib.SegmifSegObjective()
+    d.gamma, d.label_smoothing, d.ohem_t = gamma, label_smoothing, ohem_t
+    d.reduction, d.ignore_index, d.ohem_n_min = _SEG_REDUCTIONS[reduction], ignore_index, ohem_n_min
+    return d
+
+
+class SegObjectiveFn(torch.autograd.Function):
+    """losses.SegObjective on the device (csrc/seg_objective.hip).  Forward: the per-pixel losses, their reduction (for OHEM the
+    radix select of the n_min-th largest) and a 4-float device record {loss, 1 / denominator, kappa, tie weight}.  Backward: one
+    launch that recomputes the softmax and writes dlogits already scaled by the record and the upstream gradient - nothing
+    full-size is kept from the forward except, for OHEM, the per-pixel losses the selection was made on.  No host sync."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight, desc):
+        rows, C, ld = rows_view(logits, "logits")
+        lib = _lib.load()
+        nbytes = lib.segmif_seg_objective_workspace_bytes(rows, desc.reduction)
+        if nbytes <= 0:
+            raise RuntimeError(f"segmif_seg_objective_workspace_bytes refused rows = {rows}, reduction = {desc.reduction}")
+        ws = torch.empty((nbytes,), device=logits.device, dtype=torch.uint8)
+        rec = torch.empty((4,), device=logits.device, dtype=torch.float32)
+        _lib.check(lib.segmif_seg_objective_f32(ctypes.byref(desc), logits.data_ptr(), labels.data_ptr(),
+                                                weight.data_ptr() if weight is not None else None, ws.data_ptr(), rec.data_ptr(),
+                                                rows, C, ld, _stream()), "segmif_seg_objective_f32")
+        ctx.save_for_backward(logits, labels, weight, ws if desc.reduction == _SEG_REDUCTIONS["ohem"] else None, rec)
+        ctx.desc = desc
+        return rec[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, labels, weight, ws, rec = ctx.saved_tensors
+        rows, C, ld = rows_view(logits, "logits")
+        up = g.reshape(1).float().contiguous()
+        dlog = torch.empty(logits.shape, device=logits.device, dtype=torch.float32)
+        _lib.check(_lib.load().segmif_seg_objective_bwd_f32(ctypes.byref(ctx.desc), logits.data_ptr(), labels.data_ptr(),
+                                                            weight.data_ptr() if weight is not None else None,
+                                                            ws.data_ptr() if ws is not None else None, rec.data_ptr(), up.data_ptr(),
+                                                            dlog.data_ptr(), rows, C, ld, C, _stream()),
+                   "segmif_seg_objective_bwd_f32")
+        return dlog, None, None, None
+
+
+class NchwToNhwcFn(torch.autograd.Function):
+    """contiguous (B, C, H, W) -> contiguous (B, H, W, C) and back for the gradient: the two layout kernels"""
+
+    @staticmethod
+    def forward(ctx, x):
+        B, C, H, W = x.shape
+        out = torch.empty((B, H, W, C), device=x.device, dtype=torch.float32)
+        _lib.check(_lib.load().segmif_nchw_to_nhwc_f32(x.data_ptr(), out.data_ptr(), B, C, H * W, C, _stream()),
+                   "segmif_nchw_to_nhwc_f32")
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.to_nchw_contiguous(dy.contiguous())
+
+
+def nhwc_rows_of(logits):
+    """Logical (B, C, H, W) float32 device logits -> their (B, H, W, C) rows: a view when the memory is channels-last (ops.as_nchw's
+    result, also of a channel slice), one layout kernel when it is contiguous NCHW; autograd returns the gradient in the input's
+    layout either way."""
+    _req(logits, "logits")
+    if logits.dim() != 4:
+        raise RuntimeError(f"logits must be (B, C, H, W), got {tuple(logits.shape)}")
+    p = logits.permute(0, 2, 3, 1)
+    if p.stride(-1) == 1 or p.shape[-1] == 1:
+        try:
+            rows_view(p, "logits")
+            return p
+        except RuntimeError:
+            pass
+    if logits.is_contiguous():
+        return NchwToNhwcFn.apply(logits)
+    raise RuntimeError(f"logits must be contiguous or channels-last in memory, got strides {logits.stride()} for {tuple(logits.shape)}")
+
+
+def seg_objective(logits_nhwc, labels, gamma=0.0, label_smoothing=0.0, weight=None, ignore_index=255, reduction="mean", ohem_t=0.0,
+                  ohem_n_min=0):
+    """losses.SegObjective's value for NHWC logits (..., C) - a rows view, C <= 32 - and labels with one entry per row (any integer
+    type; converted to int64 on the device).  weight: (C,) float32 device class weights or None.  ohem_t = -log(thresh)."""
+    rows, C, _ = rows_view(logits_nhwc, "logits")
+    if C > 32:
+        raise RuntimeError(f"the segmentation-objective kernel holds a row of at most 32 classes in registers, got {C}")
+    if not isinstance(labels, torch.Tensor) or not labels.is_cuda or labels.is_floating_point():
+        raise RuntimeError("segmif_amd: labels must be an integer tensor on the MI355X device (the HIP path has no CPU fallback)")
+    if labels.numel() != rows:
+        raise RuntimeError(f"labels hold {labels.numel()} entries for {rows} rows of logits")
+    labels = labels.detach().long().contiguous()
+    if weight is not None:
+        weight = _req(weight, "class weights").detach().contiguous()
+        if weight.numel() != C:
+            raise RuntimeError(f"{weight.numel()} class weights for {C} classes")
+    if reduction == "ohem" and not 1 <= ohem_n_min <= rows:
+        raise ValueError(f"ohem_n_min = {ohem_n_min} outside 1..{rows} (the pixels of this batch); the reference's sort would index "
+                         "out of range")
+    desc = seg_objective_descriptor(gamma, label_smoothing, ignore_index, reduction, ohem_t, ohem_n_min)
+    return SegObjectiveFn.apply(logits_nhwc, labels, weight, desc)
+
+
 # functional front-ends ------------------------------------------------------------------------------
 def _color3(x, mode, ysrc=None, nout=3):
     """segmif_color3_f32 on a contiguous (B, 3, H, W) fp32 device tensor (ysrc: (B, 1, H, W))."""

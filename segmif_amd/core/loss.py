@@ -9,8 +9,11 @@ reference adds them.  Constructor and forward signatures, argument orders and th
 argument defaults to None and a call without tensors raises NotImplementedError (device tensors the kernels do not cover raise
 RuntimeError, as everywhere in the package).
 
-Left out: IQALoss (:605-633; needs core/Entropy.py), the detection losses and OhemCELoss, SoftmaxFocalLoss and NormalLoss (:1-383): the
-fusion trainer has no use for them.
+OhemCELoss, SoftmaxFocalLoss and NormalLoss (:342-383) are the segmentation phase's: each holds a losses.SegObjective, whose forward
+and backward are one HIP kernel pair (csrc/seg_objective.hip) - OHEM without the sort and without its host synchronisation, so it runs
+inside GraphedSegTrainStep.  They take device tensors only.
+
+Left out: IQALoss (:605-633; needs core/Entropy.py) and the detection losses (:1-340).
 """
 import torch
 import torch.nn as nn
@@ -21,7 +24,7 @@ from .model_fusion import RGB2YCrCb  # noqa: F401
 
 __all__ = ["Sobelxy", "Fusionloss3", "Fusionloss_grad3", "LapLoss2", "RGB2YCrCb", "Total_fusion_loss", "Total_fusion_loss2",
            "Fusionloss", "Fusionloss_add", "Fusionloss2", "Fusionloss4", "Fusionloss6", "Fusionloss_grad", "Fusionloss_grad2",
-           "Total_fusion_loss3", "new_loss_sobel"]
+           "Total_fusion_loss3", "new_loss_sobel", "OhemCELoss", "SoftmaxFocalLoss", "NormalLoss"]
 
 
 class Sobelxy(nn.Module):
@@ -235,3 +238,30 @@ class Total_fusion_loss3(_Total):
     def __init__(self):
         super().__init__()
         self.fl = Fusionloss()
+
+
+# ---- the segmentation objectives (core/loss.py:342-383) ------------------------------------------------------------------------------
+class OhemCELoss(losses.SegObjectiveLoss):
+    """core/loss.py:342-358: per-pixel CE; the mean of the losses above -log(thresh) when at least n_min of them are, else the mean
+    of the n_min largest (ignored pixels' zeros included).  self.thresh is -log(thresh) in float32, as in the reference."""
+
+    def __init__(self, thresh, n_min, ignore_lb=255, *args, **kwargs):
+        super().__init__(losses.SegObjective(ignore_index=ignore_lb, reduction="ohem", ohem_thresh=thresh, ohem_n_min=n_min))
+        self.thresh, self.n_min, self.ignore_lb = self.objective.ohem_t, self.objective.ohem_n_min, ignore_lb
+
+
+class SoftmaxFocalLoss(losses.SegObjectiveLoss):
+    """core/loss.py:361-373: NLLLoss(ignore_lb) of (1 - softmax)^gamma * log_softmax, mean over the valid pixels."""
+
+    def __init__(self, gamma, ignore_lb=255, *args, **kwargs):
+        if not gamma > 0:
+            raise ValueError(f"SoftmaxFocalLoss: gamma must be > 0 (gamma = 0 is cross entropy: NormalLoss or nn.CrossEntropyLoss), got {gamma}")
+        super().__init__(losses.SegObjective(gamma=gamma, ignore_index=ignore_lb))
+        self.gamma = gamma
+
+
+class NormalLoss(losses.SegObjectiveLoss):
+    """core/loss.py:375-383: torch.mean of CrossEntropyLoss(ignore_lb, reduction='none') - ignored pixels count in the mean."""
+
+    def __init__(self, ignore_lb=255, *args, **kwargs):
+        super().__init__(losses.SegObjective(ignore_index=ignore_lb, reduction="mean_all"))

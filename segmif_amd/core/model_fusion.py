@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 
 from .. import autograd as ag
-from .. import modes, ops
+from .. import losses, modes, ops
 from . import mix_transformer
 from ._util import PackedCache, init_reference_style, require_device, wants_grad
 from .segformer_head import SegFormerHead
@@ -758,7 +758,8 @@ class Fusion_Network3_ac(nn.Module):
 def seg_criterion_loss(seg, label, criterion):
     """criterion(bilinear-up(seg -> label size), label) for NHWC logits `seg` (ref :1095-1096, :241-244).  With the criterion
     train.py builds - nn.CrossEntropyLoss(ignore_index=...), mean reduction, no class weights - the whole chain (x4 bilinear,
-    softmax-CE with ignore_index, their backward) runs in two HIP kernels.  Any other criterion is the CALLER's code: it receives
+    softmax-CE with ignore_index, their backward) runs in two HIP kernels.  A losses.SegObjective, or one of core/loss.py's OhemCELoss /
+    SoftmaxFocalLoss / NormalLoss, which hold one, gets the bilinear kernel's NHWC output directly.  Any other criterion is the CALLER's code: it receives
     the up-sampled logits as an NCHW view of the HIP bilinear kernel's output (with its HIP backward) - (r6) no F.interpolate, no
     aten op of this package's own on the way."""
     H, W = label.shape[1:]
@@ -768,6 +769,8 @@ def seg_criterion_loss(seg, label, criterion):
     if isinstance(criterion, nn.CrossEntropyLoss) and criterion.weight is None and criterion.reduction == "mean" \
             and getattr(criterion, "label_smoothing", 0.0) == 0.0 and seg.shape[-1] <= 32:
         return ag.softmax_ce(up, label.type(torch.long), criterion.ignore_index)
+    if isinstance(criterion, (losses.SegObjective, losses.SegObjectiveLoss)):  # OHEM / focal / weighted CE: csrc/seg_objective.hip
+        return criterion.forward_nhwc(up, label)
     return criterion(ops.as_nchw(up), label.type(torch.long))
 
 

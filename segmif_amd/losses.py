@@ -9,11 +9,16 @@ the reference (tests/golden/losses.npz).
 
 fusion_objective is the general form behind the remaining objectives of core/loss.py: a table of up to 8 terms
 mean rho(w (L(gen) - t)) and a function combining their means; one HIP kernel pair (csrc/fusion_objective.hip) serves every table.
+
+SegObjective is the segmentation phase's counterpart: cross entropy with class weights / label smoothing, the focal loss, and the
+three reductions (mean over valid pixels, mean over all pixels, OHEM) of core/loss.py:342-383 on one HIP kernel pair
+(csrc/seg_objective.hip).  Device float32 logits only: there is no torch formulation of it in the package.
 """
 import math
 from typing import NamedTuple
 
 import torch
+import torch.nn as nn
 import torch.nn.functional as F
 
 
@@ -204,3 +209,94 @@ def fusion_objective(terms, combine, gen, ir=None, vis=None, mask=None):
         from . import autograd as ag
         return ag.FusionObjectiveFn.apply(gen, terms, combine, ir, vis, mask)
     return combine(objective_means(terms, gen, ir, vis, mask))
+
+
+# ---- the segmentation objectives (csrc/seg_objective.hip; core/loss.py:342-383) ------------------------------------------------------
+SEG_REDUCTIONS = ("mean", "mean_all", "ohem")
+
+
+class SegObjective(nn.Module):
+    """Per-pixel loss l over softmax(logits) and its reduction, forward and backward in csrc/seg_objective.hip:
+        gamma == 0   cross entropy with class weights `weight` and label smoothing, torch's F.cross_entropy definition
+        gamma > 0    the focal loss -w_y (1 - p_y)^gamma log p_y of SoftmaxFocalLoss (no label smoothing)
+        reduction    "mean": sum l / sum of w_y over valid pixels (nn.CrossEntropyLoss / nn.NLLLoss) | "mean_all": sum l / pixels
+                     (NormalLoss) | "ohem": OhemCELoss - the mean of the l above -log(ohem_thresh) when there are at least
+                     ohem_n_min of them, else the mean of the ohem_n_min largest l (ignored pixels' zeros among them).
+    ohem_thresh is a probability, as in the reference.  Pixels labelled ignore_index (or outside [0, C)) have l = 0 and no gradient.
+    No host synchronisation: it runs inside GraphedSegTrainStep's capture.  weight is a buffer (it moves with .cuda())."""
+
+    def __init__(self, gamma=0.0, label_smoothing=0.0, weight=None, ignore_index=255, reduction="mean", ohem_thresh=None,
+                 ohem_n_min=None):
+        super().__init__()
+        gamma, label_smoothing = float(gamma), float(label_smoothing)
+        if not (math.isfinite(gamma) and gamma >= 0.0):
+            raise ValueError(f"SegObjective: gamma must be finite and >= 0, got {gamma}")
+        if not 0.0 <= label_smoothing < 1.0:
+            raise ValueError(f"SegObjective: label_smoothing must lie in [0, 1), got {label_smoothing}")
+        if gamma > 0.0 and label_smoothing > 0.0:
+            raise ValueError("SegObjective: the focal loss (gamma > 0) takes no label smoothing")
+        if reduction not in SEG_REDUCTIONS:
+            raise ValueError(f"SegObjective: reduction must be one of {', '.join(SEG_REDUCTIONS)}, got {reduction!r}")
+        self.ohem_t, self.ohem_n_min = 0.0, 0
+        if reduction == "ohem":
+            if ohem_thresh is None or ohem_n_min is None:
+                raise ValueError("SegObjective: reduction 'ohem' needs ohem_thresh and ohem_n_min")
+            # -log(thresh) in float32, as OhemCELoss.__init__ forms it
+            t = float(-torch.log(torch.tensor(float(ohem_thresh), dtype=torch.float)))
+            if not math.isfinite(t):
+                raise ValueError(f"SegObjective: -log(ohem_thresh) must be finite, got ohem_thresh = {ohem_thresh}")
+            if int(ohem_n_min) != ohem_n_min or int(ohem_n_min) < 1:
+                raise ValueError(f"SegObjective: ohem_n_min must be an integer >= 1, got {ohem_n_min}")
+            self.ohem_t, self.ohem_n_min = t, int(ohem_n_min)
+        elif ohem_thresh is not None or ohem_n_min is not None:
+            raise ValueError("SegObjective: ohem_thresh / ohem_n_min belong to reduction 'ohem'")
+        if weight is not None:
+            weight = torch.as_tensor(weight, dtype=torch.float32).detach().clone()
+            if weight.dim() != 1 or not 1 <= weight.numel() <= 32:
+                raise ValueError(f"SegObjective: weight must hold one value per class (1..32), got shape {tuple(weight.shape)}")
+            if not bool(torch.isfinite(weight).all()) or bool((weight < 0).any()):
+                raise ValueError("SegObjective: class weights must be finite and >= 0")
+        self.register_buffer("weight", weight)
+        self.gamma, self.label_smoothing, self.ignore_index, self.reduction = gamma, label_smoothing, int(ignore_index), reduction
+
+    @classmethod
+    def from_criterion(cls, criterion):
+        """The SegObjective that computes what an nn.CrossEntropyLoss (mean reduction) does: the explicit opt-in for torch's class,
+        which seg_criterion_loss otherwise leaves to torch's kernels when it carries weights or smoothing."""
+        if not isinstance(criterion, nn.CrossEntropyLoss):
+            raise TypeError(f"SegObjective.from_criterion takes an nn.CrossEntropyLoss, got {type(criterion).__name__}")
+        if criterion.reduction != "mean":
+            raise ValueError(f"SegObjective.from_criterion: reduction {criterion.reduction!r} has no counterpart (mean only)")
+        return cls(label_smoothing=getattr(criterion, "label_smoothing", 0.0), weight=criterion.weight,
+                   ignore_index=criterion.ignore_index)
+
+    def extra_repr(self):
+        s = f"gamma={self.gamma}, label_smoothing={self.label_smoothing}, ignore_index={self.ignore_index}, reduction={self.reduction!r}"
+        return s + (f", ohem_t={self.ohem_t:.6f}, ohem_n_min={self.ohem_n_min}" if self.reduction == "ohem" else "")
+
+    def forward_nhwc(self, logits_nhwc, labels):
+        """logits_nhwc: (..., C) float32 device rows (a channel slice of a wider buffer is fine); labels: one per row"""
+        from . import autograd as ag
+        return ag.seg_objective(logits_nhwc, labels, gamma=self.gamma, label_smoothing=self.label_smoothing, weight=self.weight,
+                                ignore_index=self.ignore_index, reduction=self.reduction, ohem_t=self.ohem_t,
+                                ohem_n_min=self.ohem_n_min)
+
+    def forward(self, logits, labels):
+        """logits: logical (B, C, H, W), contiguous or channels-last in memory (what ops.as_nchw returns); the gradient comes back
+        in the same layout."""
+        from . import autograd as ag
+        return self.forward_nhwc(ag.nhwc_rows_of(logits), labels)
+
+
+class SegObjectiveLoss(nn.Module):
+    """Base of the reference-named segmentation losses of core/loss.py: holds a SegObjective and calls it."""
+
+    def __init__(self, objective):
+        super().__init__()
+        self.objective = objective
+
+    def forward(self, logits, labels):
+        return self.objective(logits, labels)
+
+    def forward_nhwc(self, logits_nhwc, labels):
+        return self.objective.forward_nhwc(logits_nhwc, labels)

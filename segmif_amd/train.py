@@ -12,7 +12,8 @@ feed train.py:369-374's dynamic weights are averaged too so every rank applies i
     python -m segmif_amd.train --synthetic N ...
 
 runs the whole schedule of train.py:424-434 - seven rounds of a fusion phase then a segmentation phase - on batches that
-segmif_amd.data makes on the device (main() below; one process, one GPU).
+segmif_amd.data makes on the device (main() below; one process, one GPU).  --seg-loss picks the segmentation phase's objective
+(make_seg_loss): the reference's CE by default, or OHEM / focal / NormalLoss / class-weighted CE on csrc/seg_objective.hip.
 """
 import argparse
 import os
@@ -231,6 +232,46 @@ def make_fusion_loss(name):
     return fn
 
 
+SEG_LOSSES = ("ce", "ohem", "focal", "normal", "weighted")
+
+
+def seg_loss_names():
+    """what --seg-loss / make_seg_loss build"""
+    return list(SEG_LOSSES)
+
+
+def make_seg_loss(name, ignore_index=255, ohem_thresh=0.7, ohem_n_min=None, focal_gamma=2.0, label_smoothing=0.0, class_weights=None):
+    """The segmentation phase's criterion `name` for seg_train_step / GraphedSegTrainStep:
+        ce        nn.CrossEntropyLoss(ignore_index) - the reference's (train.py:156), on the softmax-CE kernel it always had; with
+                  label_smoothing > 0 a losses.SegObjective
+        ohem      core.OhemCELoss(ohem_thresh, ohem_n_min)      focal   core.SoftmaxFocalLoss(focal_gamma)
+        normal    core.NormalLoss()                             weighted  losses.SegObjective(weight=class_weights, label_smoothing)
+    Everything but plain `ce` runs on csrc/seg_objective.hip.  Move the result to the device (.cuda()): the class weights are a
+    buffer.  Settings a choice does not read are refused, not ignored."""
+    from .core import loss
+    if name not in SEG_LOSSES:
+        raise ValueError(f"unknown segmentation objective {name!r}; one of {', '.join(SEG_LOSSES)}")
+    if class_weights is not None and name != "weighted":
+        raise ValueError(f"class weights belong to the 'weighted' objective, not {name!r}")
+    if label_smoothing and name not in ("ce", "weighted"):
+        raise ValueError(f"label smoothing belongs to 'ce' and 'weighted', not {name!r}")
+    if name == "ce":
+        if not label_smoothing:
+            return torch.nn.CrossEntropyLoss(ignore_index=ignore_index)
+        return losses.SegObjective(label_smoothing=label_smoothing, ignore_index=ignore_index)
+    if name == "ohem":
+        if ohem_n_min is None:
+            raise ValueError("'ohem' needs ohem_n_min (the reference has no default for it)")
+        return loss.OhemCELoss(ohem_thresh, ohem_n_min, ignore_index)
+    if name == "focal":
+        return loss.SoftmaxFocalLoss(focal_gamma, ignore_index)
+    if name == "normal":
+        return loss.NormalLoss(ignore_index)
+    if class_weights is None:
+        raise ValueError("'weighted' needs class_weights")
+    return losses.SegObjective(label_smoothing=label_smoothing, weight=class_weights, ignore_index=ignore_index)
+
+
 def _miou(seg, fus, val, batch):
     """mIoU of the pair forward (fusion net -> segmentation net) over a DeviceDataset, through segmif_amd.evaluate.Evaluator"""
     from .evaluate import Evaluator
@@ -289,9 +330,38 @@ def main(argv=None):
     ap.add_argument("--fusion-loss", metavar="NAME", help="train the fusion net on this objective of core/loss.py instead of the "
                     "reference's schedule (Fusionloss3 in round 1, then Fusionloss_grad3 as the intensity term), which is the default. "
                     "Any objective other than that schedule is this project's choice: the reference's train.py instantiates no other")
+    ap.add_argument("--seg-loss", choices=SEG_LOSSES, default="ce", help="objective of the SEGMENTATION phase (the segmentation term "
+                    "inside the fusion phase keeps plain CE).  ce, the default, is the reference's nn.CrossEntropyLoss(ignore_index=255); "
+                    "ohem / focal / normal are core/loss.py's OhemCELoss / SoftmaxFocalLoss / NormalLoss, weighted is CE with "
+                    "--seg-class-weights: none of those is the reference's objective, its train.py instantiates CE only")
+    ap.add_argument("--ohem-thresh", type=float, default=0.7, help="--seg-loss ohem: probability threshold (losses above -log of it are hard)")
+    ap.add_argument("--ohem-n-min", type=int, help="--seg-loss ohem: least number of pixels averaged; default batch * crop^2 // 16" + ours)
+    ap.add_argument("--focal-gamma", type=float, default=2.0, help="--seg-loss focal: exponent of (1 - p)")
+    ap.add_argument("--label-smoothing", type=float, default=0.0, help="--seg-loss ce / weighted: label smoothing in [0, 1); above 0 it is "
+                    "not the reference's objective")
+    ap.add_argument("--seg-class-weights", type=float, nargs="+", metavar="W", help="--seg-loss weighted: one weight >= 0 per class (9)")
     ap.add_argument("--log-iters", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args(argv)
+    n_class = 9
+    if args.seg_class_weights is not None and args.seg_loss != "weighted":
+        ap.error(f"--seg-class-weights belongs to --seg-loss weighted, not {args.seg_loss}")
+    if args.seg_loss == "weighted" and (args.seg_class_weights is None or len(args.seg_class_weights) != n_class
+                                        or min(args.seg_class_weights) < 0):
+        ap.error(f"--seg-loss weighted needs --seg-class-weights with {n_class} values >= 0")
+    if not 0.0 <= args.label_smoothing < 1.0:
+        ap.error(f"--label-smoothing {args.label_smoothing}: must lie in [0, 1)")
+    if args.label_smoothing and args.seg_loss not in ("ce", "weighted"):
+        ap.error(f"--label-smoothing belongs to --seg-loss ce / weighted, not {args.seg_loss}")
+    if args.seg_loss == "ohem" and not 0.0 < args.ohem_thresh <= 1.0:
+        ap.error(f"--ohem-thresh {args.ohem_thresh}: a probability in (0, 1]")
+    if args.seg_loss == "focal" and not args.focal_gamma > 0:
+        ap.error(f"--focal-gamma {args.focal_gamma}: must be > 0")
+    seg_pixels = max(1, args.samples_per_gpu // 2) * args.crop_size ** 2
+    if args.ohem_n_min is None:
+        args.ohem_n_min = max(1, seg_pixels // 16)
+    if args.seg_loss == "ohem" and not 1 <= args.ohem_n_min <= seg_pixels:
+        ap.error(f"--ohem-n-min {args.ohem_n_min}: outside 1..{seg_pixels}, the pixels of a segmentation batch")
     if not torch.cuda.is_available():
         raise RuntimeError("segmif_amd.train needs the MI355X device (the HIP path has no CPU fallback)")
     if (args.synthetic is None) == (args.root is None):
@@ -324,6 +394,12 @@ def main(argv=None):
               f"(torch.manual_seed({args.seed}))")
     seg_initial = {k: v.clone() for k, v in seg.state_dict().items()}
     crit = torch.nn.CrossEntropyLoss(ignore_index=255)
+    seg_crit = make_seg_loss(args.seg_loss, ohem_thresh=args.ohem_thresh, ohem_n_min=args.ohem_n_min if args.seg_loss == "ohem" else None,
+                             focal_gamma=args.focal_gamma, label_smoothing=args.label_smoothing,
+                             class_weights=args.seg_class_weights).cuda()
+    if args.seg_loss != "ce" or args.label_smoothing:
+        print(f"[train] --seg-loss {args.seg_loss}" + (f" --label-smoothing {args.label_smoothing}" if args.label_smoothing else "")
+              + ": NOT the reference's segmentation objective (segmentation phase only; the fusion phase's segmentation term keeps CE)")
     sched = dict(weight_decay=args.weight_decay, betas=args.betas, max_iter=args.max_iters, warmup_ratio=args.warmup_ratio, power=args.power)
     loader_kw = dict(batch=batch, crop_size=args.crop_size, rescale_range=tuple(args.rescale_range), fliplr=True)
     best, wrote_seg = None, False
@@ -363,7 +439,7 @@ def main(argv=None):
         n_seg = args.seg_iters if args.seg_iters is not None else 10000
         for n in range(n_seg):
             _, _, fused3, _, label = next(batches)
-            loss = seg_train_step(seg, opt, fused3, label, crit)
+            loss = seg_train_step(seg, opt, fused3, label, seg_crit)
             if (n + 1) % args.log_iters == 0 or n + 1 == n_seg:
                 print(f"[train] round {iter_} segmentation iter {n + 1}/{n_seg}: lr {opt.param_groups[0]['lr']:.3e} loss {float(loss):.6f}")
             if (n + 1) % 1000 == 0 or n + 1 == n_seg:
