@@ -608,6 +608,21 @@ int segmif_dequantize_u8(const uint8_t* in_nhwc, float* out_nchw, int B, int C, 
 int64_t segmif_fusion_stats_workspace_bytes(int B, int H, int W);
 int segmif_fusion_stats_u8(const uint8_t* fused_rgb, const uint8_t* vis_rgb, const uint8_t* ir, int64_t* joint_fa, int64_t* joint_fv,
                            int64_t* sums, double* ag, void* workspace, int B, int H, int W, int accumulate, void* stream);
+/* Local-window fusion scores of the same three planes (f = L(fused), v = L(vis), a = ir), PER IMAGE, all fp64:
+ *   qabf[b][0..1]            Xydeas-Petrovic (L = 1): sum (Q_AF gA + Q_VF gV) and sum (gA + gV) over the pixels; 3 x 3 Sobel as
+ *                            true convolutions with zero padding, the gS / gF comparison decided on the integers sx^2 + sy^2
+ *   ssim[b][0..1]            sum over the H W pixels of the SSIM map of (f, a) and of (f, v): 11 x 11 Gaussian, sigma 1.5, zero
+ *                            padding of 5, images taken as x / 255, C1 = 0.01^2, C2 = 0.03^2 (pytorch_ssim.ssim's map)
+ *   vif[b][src][scale][0..1] pixel-domain VIF, sigma_nsq = 2, src 0 = a, 1 = v as the reference image and f as the distorted
+ *                            one, scale 0 .. 3 with N = 17, 9, 5, 3 ("valid" Gaussians of sd = N / 5, decimation by 2):
+ *                            sum log10(1 + g^2 s1 / (sv + 2)) and sum log10(1 + s1 / 2)
+ * Every output is overwritten.  Sums are combined in a fixed order without floating-point atomics: bitwise reproducible and
+ * batch independent.  workspace: segmif_structural_stats_workspace_bytes(B, H, W) bytes of 8-byte aligned scratch (0 = invalid
+ * sizes).  H, W >= 41 (the fourth VIF scale), 1 <= B <= 65535, H W <= 2^30; a null pointer or an invalid size returns
+ * SEGMIF_EINVAL before any launch; nothing allocates or synchronises, so the call can be captured in a graph. */
+int64_t segmif_structural_stats_workspace_bytes(int B, int H, int W);
+int segmif_structural_stats_u8(const uint8_t* fused_rgb, const uint8_t* vis_rgb, const uint8_t* ir, double* qabf, double* ssim,
+                               double* vif, void* workspace, int B, int H, int W, void* stream);
 /* out[i] = palette[labels[i]] for labels int32 (n), palette uint8 (K, 3), 1 <= K <= 256; a label outside 0 .. K-1 gives
  * (0, 0, 0) (util/util.py:21-29 leaves unmatched pixels zero) */
 int segmif_palette_u8(const int32_t* labels, const uint8_t* palette, uint8_t* out, int64_t n, int K, void* stream);

@@ -177,6 +177,8 @@ SIGNATURES = {
     "segmif_dequantize_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p]),
     "segmif_fusion_stats_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "segmif_fusion_stats_u8": (c_int, [c_void_p] * 8 + [c_int, c_int, c_int, c_int, c_void_p]),
+    "segmif_structural_stats_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "segmif_structural_stats_u8": (c_int, [c_void_p] * 7 + [c_int, c_int, c_int, c_void_p]),
     "segmif_palette_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "segmif_augment_record_bytes": (c_int, []),
     "segmif_augment_pick_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),

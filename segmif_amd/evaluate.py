@@ -2,10 +2,11 @@
 (test_fusion.py:83-126 followed by test_segmentation.py:160-195 and util/util.py:8-29, in memory and on the device).
 
     python -m segmif_amd.evaluate --ir DIR --vis DIR --mask DIR [--label DIR] --out DIR [--backbone mit_b3]
-        [--seg-ckpt F] [--fusion-ckpt F] [--batch N] [--json F]
+        [--seg-ckpt F] [--fusion-ckpt F] [--batch N] [--json F] [--structural-scores]
 
 reads the sorted file names of --vis (TaskFusion_dataset2.py:40-48) from every folder (.npy always, .png when PIL imports),
-and writes OUT/Fused/NAME, OUT/Seg/NAME (palette rendering) and a JSON of the results.
+and writes OUT/Fused/NAME, OUT/Seg/NAME (palette rendering) and a JSON of the results.  --structural-scores adds Qabf, SSIM and
+VIF (utils/fusion_metrics.structural_scores; images of at least 41 x 41) to the JSON and to the summary line.
 """
 import argparse
 import json
@@ -17,7 +18,8 @@ import torch
 
 from . import _lib
 from .pipeline import PairForward
-from .utils.fusion_metrics import MFNET_PALETTE, SCORE_NAMES, colorize, fusion_scores, fusion_stats
+from .utils.fusion_metrics import (MFNET_PALETTE, SCORE_NAMES, STRUCTURAL_SCORE_NAMES, colorize, fusion_scores, fusion_stats,
+                                   structural_scores, structural_stats)
 from .utils.metrics import _dev, _stream, compute_results, confusion_matrix
 
 
@@ -36,15 +38,18 @@ def _nanmean(x):
 
 class Evaluator:
     """Accumulates the evaluation of (infrared, visible, mask) uint8 batches through PairForward(uint8_roundtrip=True,
-    return_u8=True): the min-max rescale of the fused image is per call = per batch, as the reference's is."""
+    return_u8=True): the min-max rescale of the fused image is per call = per batch, as the reference's is.  structural=True also
+    gathers Qabf, SSIM and VIF (STRUCTURAL_SCORE_NAMES) of every pair."""
 
-    def __init__(self, seg_net, fusion_net, n_class=9, graph=False):
+    def __init__(self, seg_net, fusion_net, n_class=9, graph=False, structural=False):
         self.pair = PairForward(seg_net, fusion_net, uint8_roundtrip=True, return_u8=True)
         self.n_class = n_class
         self.graph = graph
         self._graph_shape = None
         self._conf = None
         self._scores = []
+        self.structural = structural
+        self._structural = []
 
     def update(self, ir_u8, vis_u8, mask_u8, label=None):
         """ir_u8 (B, H, W), vis_u8 (B, H, W, 3), mask_u8 (B, H, W) uint8 and optionally label (B, H, W) int64, all on the device
@@ -69,6 +74,8 @@ class Evaluator:
             else:
                 _, labels, fused_u8 = self.pair.eager(ir, vis, mask3)
             self._scores.append(fusion_stats(fused_u8, vis_u8, ir_u8))
+            if self.structural:
+                self._structural.append(structural_stats(fused_u8, vis_u8, ir_u8))
             if label is not None:
                 self._conf = confusion_matrix(labels, _dev(label, "label", torch.int64), self.n_class, out=self._conf)
         return fused_u8, labels
@@ -76,10 +83,15 @@ class Evaluator:
     def results(self):
         """-> dict: every score of SCORE_NAMES as a per-image float64 array, 'mean' (name -> NaN-ignoring mean over the images)
         and, when labels were given, 'precision' / 'recall' / 'iou' per class (compute_results) and 'mIoU' =
-        mean(nan_to_num(iou)), the figure test_segmentation.py prints for data that lack a class."""
+        mean(nan_to_num(iou)), the figure test_segmentation.py prints for data that lack a class.  With structural=True the
+        scores of STRUCTURAL_SCORE_NAMES are added in the same two places."""
         per = [fusion_scores(s) for s in self._scores]
-        out = {k: np.concatenate([p[k] for p in per]) if per else np.zeros(0) for k in SCORE_NAMES}
-        out["mean"] = {k: _nanmean(out[k]) for k in SCORE_NAMES}
+        names = SCORE_NAMES
+        if self.structural:
+            per = [dict(p, **structural_scores(s)) for p, s in zip(per, self._structural)]
+            names = SCORE_NAMES + STRUCTURAL_SCORE_NAMES
+        out = {k: np.concatenate([p[k] for p in per]) if per else np.zeros(0) for k in names}
+        out["mean"] = {k: _nanmean(out[k]) for k in names}
         if self._conf is not None:
             precision, recall, iou = compute_results(self._conf)
             out.update(precision=precision, recall=recall, iou=iou, mIoU=float(np.mean(np.nan_to_num(iou))))
@@ -125,6 +137,8 @@ def main(argv=None):
     ap.add_argument("--fusion-ckpt")
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--json")
+    ap.add_argument("--structural-scores", action="store_true",
+                    help="also report Qabf, SSIM and VIF (one more device pass per batch; images of at least 41 x 41)")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError("segmif_amd.evaluate needs the MI355X device (the HIP path has no CPU fallback)")
@@ -138,7 +152,7 @@ def main(argv=None):
         else:
             print(f"[evaluate] no checkpoint for the {what} network: running on SEEDED RANDOM weights (torch.manual_seed(0))")
     seg, fus = seg.cuda().eval(), fus.cuda().eval()
-    ev = Evaluator(seg, fus)
+    ev = Evaluator(seg, fus, structural=args.structural_scores)
     names = _names(args.vis)
     if not names:
         raise RuntimeError(f"no .npy / .png files in {args.vis}")
@@ -165,7 +179,7 @@ def main(argv=None):
     path = args.json or os.path.join(args.out, "results.json")
     with open(path, "w") as f:
         json.dump(doc, f, indent=1)
-    print("[evaluate] " + "  ".join(f"{k} {res['mean'][k]:.4f}" for k in SCORE_NAMES) + (f"  mIoU {res['mIoU']:.4f}" if "mIoU" in res else ""))
+    print("[evaluate] " + "  ".join(f"{k} {res['mean'][k]:.4f}" for k in res["mean"]) + (f"  mIoU {res['mIoU']:.4f}" if "mIoU" in res else ""))
     print(f"[evaluate] wrote {path}")
     return 0
 
