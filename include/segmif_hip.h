@@ -585,6 +585,23 @@ int segmif_argmax_nhwc_i32(const float* x, int32_t* labels, int64_t rows, int C,
 /* (r6) test_segmentation.py:169-174 in one pass: labels = argmax_c bilinear(x -> OH x OW) for NHWC logits x (B, IH, IW, C), pixel pitch
  * ldx (align_corners = False, segmif_bilinear_nhwc_f32's arithmetic; ties -> lowest index): the resized logits are never written. */
 int segmif_bilinear_argmax_i32(const float* x, int32_t* labels, int B, int IH, int IW, int OH, int OW, int C, int ldx, void* stream);
+/* Multi-scale + flip inference (the protocol SegFormer's tables are quoted under; the reference evaluates one view only,
+ * test_segmentation.py:169-174), combined in one pass (csrc/tta.hip).  A view is the NHWC logits (B, ih, iw, C), pixel pitch
+ * ldx >= C, of one forward on a resized and, with flip != 0, mirrored input. */
+typedef struct { const float* x; int ih, iw, ldx, flip; } SegmifTtaView;
+/* For every output pixel and every view v of the HOST table `views`, in table order: r_v = bilinear(view v -> OH x OW)
+ * (align_corners = False, segmif_bilinear_nhwc_f32's arithmetic) sampled at column ox, or OW - 1 - ox when the view is mirrored
+ * (= flip(interpolate(x))); p_v = softmax_c(r_v) (max-subtracted, expf); mean = (sum_v p_v) / n_views;
+ * labels = argmax_c mean (ties -> lowest index).  probs_or_null, when given, receives mean as (B, OH, OW, C); nothing else of
+ * that size is read or written.  One thread owns a pixel and sums in table order: no atomics, bitwise reproducible,
+ * independent of B.  The table travels in the kernel arguments (no device allocation, no copy).  1 <= n_views <= 16,
+ * 1 <= C <= 32, ldx >= C, OH and B <= 65535; anything else is SEGMIF_EINVAL. */
+int segmif_tta_vote_f32(const SegmifTtaView* views, int n_views, int32_t* labels, float* probs_or_null, int B, int OH, int OW, int C,
+                        void* stream);
+/* y = flip?(interpolate(x, (OH, OW), bilinear, align_corners = False)) for `planes` = B * C contiguous (IH, IW) planes (NCHW):
+ * a view's network input in one pass (resize, then torch.flip, would be two).  The same coordinate arithmetic; a mirrored
+ * output column ox holds the resize's column OW - 1 - ox.  OH and planes <= 65535. */
+int segmif_resize_flip_nchw_f32(const float* x, float* y, int planes, int IH, int IW, int OH, int OW, int flip, void* stream);
 /* conf[t*K + p] += #{i : label[i] == t, pred[i] == p}, both inside [0, K) (K <= 32) — the accumulation of
  * test_segmentation.py:176-177 (sklearn confusion_matrix with labels=[0..K-1]: rows = ground truth,
  * columns = prediction, samples outside the label set ignored); conf is NOT cleared */

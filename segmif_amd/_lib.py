@@ -105,6 +105,10 @@ class SegmifSegObjective(ctypes.Structure):
                 ("ignore_index", c_int32), ("reserved", c_int32), ("ohem_n_min", c_int64)]
 
 
+class SegmifTtaView(ctypes.Structure):
+    _fields_ = [("x", c_void_p), ("ih", c_int32), ("iw", c_int32), ("ldx", c_int32), ("flip", c_int32)]
+
+
 # name -> (restype, argtypes); must list every symbol include/segmif_hip.h declares
 SIGNATURES = {
     "segmif_abi_version": (c_int, []),
@@ -277,6 +281,8 @@ SIGNATURES = {
                                         c_int, c_int, c_void_p]),
     "segmif_argmax_nhwc_i32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "segmif_bilinear_argmax_i32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "segmif_tta_vote_f32": (c_int, [POINTER(SegmifTtaView), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "segmif_resize_flip_nchw_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
 }
 
 _lib = None

@@ -16,6 +16,7 @@ import torch.nn as nn
 
 from .. import autograd as ag
 from .. import losses, modes, ops
+from ..tta import TTA
 from . import mix_transformer
 from ._util import PackedCache, init_reference_style, require_device, wants_grad
 from .segformer_head import SegFormerHead
@@ -815,6 +816,26 @@ class Network3(nn.Module):
         seg = self._segment_nhwc(fused)
         H, W = size if size is not None else fused.shape[2:]
         return ops.bilinear_argmax(seg, H, W)  # (r6: one pass - the resized logits, 708 MB per 64 images, are never written)
+
+    def predict_labels_tta(self, fused, size=None, tta=TTA(), return_probs=False, segment=None):
+        """Multi-scale + flip inference: one forward per view of tta.plan(H, W) - the input resized (and mirrored) by
+        ops.resize_flip_nchw, the (scale 1, not mirrored) view being `fused` itself - and one ops.tta_vote over the V
+        quarter-resolution logit maps: probabilities averaged after resizing to `size`, the flip undone after the softmax.
+        -> int32 labels (B, H, W), or (labels, probs (B, H, W, C)) with return_probs.  segment: what maps a view's
+        (B, 3, h, w) input to its NHWC logits (default self._segment_nhwc; a test may pass a cheap stand-in).  A plan that
+        is the single plain view is predict_labels.  Inference only: raises under grad."""
+        if torch.is_grad_enabled():
+            raise RuntimeError("predict_labels_tta is inference only: call it inside torch.no_grad()")
+        require_device(fused, "Network3 input")
+        H, W = fused.shape[2:]
+        plan = tta.plan(H, W)
+        if plan == [(H, W, False)] and not return_probs and segment is None:
+            return self.predict_labels(fused, size)
+        segment = self._segment_nhwc if segment is None else segment
+        fused = fused.contiguous()
+        views = [segment(fused if (h, w, f) == (H, W, False) else ops.resize_flip_nchw(fused, h, w, f)) for h, w, f in plan]
+        OH, OW = size if size is not None else (H, W)
+        return ops.tta_vote(views, [f for _, _, f in plan], OH, OW, want_probs=return_probs)
 
     def _loss(self, fused_seg1, label, criterion):
         """CE(bilinear-up(seg_map), label) (ref :1090-1097): seg_criterion_loss below."""

@@ -3,10 +3,13 @@
 
     python -m segmif_amd.evaluate --ir DIR --vis DIR --mask DIR [--label DIR] --out DIR [--backbone mit_b3]
         [--seg-ckpt F] [--fusion-ckpt F] [--batch N] [--json F] [--structural-scores]
+        [--ms-scales S [S ...]] [--flip] [--size-divisor N]
 
 reads the sorted file names of --vis (TaskFusion_dataset2.py:40-48) from every folder (.npy always, .png when PIL imports),
 and writes OUT/Fused/NAME, OUT/Seg/NAME (palette rendering) and a JSON of the results.  --structural-scores adds Qabf, SSIM and
-VIF (utils/fusion_metrics.structural_scores; images of at least 41 x 41) to the JSON and to the summary line.
+VIF (utils/fusion_metrics.structural_scores; images of at least 41 x 41) to the JSON and to the summary line.  --ms-scales and
+--flip (alone: scales 1.0) take the labels, and so the mIoU, from multi-scale + flip inference (segmif_amd.tta; the JSON then
+names the views under "tta"); the fused images and their scores do not change.
 """
 import argparse
 import json
@@ -18,6 +21,7 @@ import torch
 
 from . import _lib
 from .pipeline import PairForward
+from .tta import TTA
 from .utils.fusion_metrics import (MFNET_PALETTE, SCORE_NAMES, STRUCTURAL_SCORE_NAMES, colorize, fusion_scores, fusion_stats,
                                    structural_scores, structural_stats)
 from .utils.metrics import _dev, _stream, compute_results, confusion_matrix
@@ -39,10 +43,15 @@ def _nanmean(x):
 class Evaluator:
     """Accumulates the evaluation of (infrared, visible, mask) uint8 batches through PairForward(uint8_roundtrip=True,
     return_u8=True): the min-max rescale of the fused image is per call = per batch, as the reference's is.  structural=True also
-    gathers Qabf, SSIM and VIF (STRUCTURAL_SCORE_NAMES) of every pair."""
+    gathers Qabf, SSIM and VIF (STRUCTURAL_SCORE_NAMES) of every pair.  tta: a segmif_amd.tta.TTA - the labels (and the mIoU)
+    come from multi-scale + flip inference (PairForward(tta=)); not with graph=True."""
 
-    def __init__(self, seg_net, fusion_net, n_class=9, graph=False, structural=False):
-        self.pair = PairForward(seg_net, fusion_net, uint8_roundtrip=True, return_u8=True)
+    def __init__(self, seg_net, fusion_net, n_class=9, graph=False, structural=False, tta=None):
+        if tta is not None and graph:
+            raise NotImplementedError("Evaluator: graph=True cannot capture the multi-size forward (tta=)")
+        self.pair = PairForward(seg_net, fusion_net, uint8_roundtrip=True, return_u8=True, tta=tta)
+        self.tta = tta
+        self._frame = None
         self.n_class = n_class
         self.graph = graph
         self._graph_shape = None
@@ -73,6 +82,7 @@ class Evaluator:
                 fused_u8, labels = fused_u8.clone(), labels.clone()  # (the graph's output buffers are overwritten by the next replay)
             else:
                 _, labels, fused_u8 = self.pair.eager(ir, vis, mask3)
+            self._frame = tuple(vis.shape[2:])
             self._scores.append(fusion_stats(fused_u8, vis_u8, ir_u8))
             if self.structural:
                 self._structural.append(structural_stats(fused_u8, vis_u8, ir_u8))
@@ -96,6 +106,19 @@ class Evaluator:
             precision, recall, iou = compute_results(self._conf)
             out.update(precision=precision, recall=recall, iou=iou, mIoU=float(np.mean(np.nan_to_num(iou))))
         return out
+
+    def document(self, names, seeded_weights, res=None):
+        """What the command line writes as JSON: the names, which networks ran on seeded weights, results() (or `res`, if the
+        caller has them) with arrays as lists and - only with tta - its settings and the views of the last batch's frame size
+        under "tta"."""
+        doc = {"names": list(names), "seeded_weights": list(seeded_weights)}
+        for k, v in (self.results() if res is None else res).items():
+            doc[k] = v.tolist() if isinstance(v, np.ndarray) else v
+        if self.tta is not None:
+            if self._frame is None:
+                raise RuntimeError("Evaluator.document: no batch has been evaluated, the views have no size yet")
+            doc["tta"] = self.tta.describe(*self._frame)
+        return doc
 
 
 def _read(path):
@@ -125,7 +148,8 @@ def _load_weights(net, path):
     net.load_state_dict(sd.get("state_dict", sd) if isinstance(sd, dict) else sd)
 
 
-def main(argv=None):
+def parse_args(argv=None):
+    """-> (args, tta): the parsed command line and the TTA it asks for (None without --ms-scales / --flip)."""
     ap = argparse.ArgumentParser(prog="python -m segmif_amd.evaluate", description=__doc__.split("\n\n")[0])
     ap.add_argument("--ir", required=True)
     ap.add_argument("--vis", required=True)
@@ -139,7 +163,23 @@ def main(argv=None):
     ap.add_argument("--json")
     ap.add_argument("--structural-scores", action="store_true",
                     help="also report Qabf, SSIM and VIF (one more device pass per batch; images of at least 41 x 41)")
+    ap.add_argument("--ms-scales", type=float, nargs="+", metavar="S",
+                    help="multi-scale inference: one forward per scale of the frame (SegFormer's protocol: 0.5 0.75 1.0 1.25 1.5 1.75)")
+    ap.add_argument("--flip", action="store_true", help="also vote every scale's mirrored view (alone: scale 1.0)")
+    ap.add_argument("--size-divisor", type=int, default=8, metavar="N", help="view sizes are rounded up to a multiple of N (default 8)")
     args = ap.parse_args(argv)
+    tta = None
+    if args.ms_scales is not None or args.flip:
+        tta = TTA(tuple(args.ms_scales) if args.ms_scales is not None else (1.0,), args.flip, args.size_divisor)
+        try:
+            tta.plan(8, 8)  # (the settings' own checks: scales > 0, divisor >= 1, at most 16 views)
+        except ValueError as e:
+            ap.error(str(e))
+    return args, tta
+
+
+def main(argv=None):
+    args, tta = parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError("segmif_amd.evaluate needs the MI355X device (the HIP path has no CPU fallback)")
     from .core import Fusion_Network3_ac, Network3
@@ -152,7 +192,7 @@ def main(argv=None):
         else:
             print(f"[evaluate] no checkpoint for the {what} network: running on SEEDED RANDOM weights (torch.manual_seed(0))")
     seg, fus = seg.cuda().eval(), fus.cuda().eval()
-    ev = Evaluator(seg, fus, structural=args.structural_scores)
+    ev = Evaluator(seg, fus, structural=args.structural_scores, tta=tta)
     names = _names(args.vis)
     if not names:
         raise RuntimeError(f"no .npy / .png files in {args.vis}")
@@ -173,9 +213,7 @@ def main(argv=None):
             _write(os.path.join(args.out, "Seg", n), seg_h[k])
             print(f"[evaluate] {n}")
     res = ev.results()
-    doc = {"names": names, "seeded_weights": [w for w, c in (("seg", args.seg_ckpt), ("fusion", args.fusion_ckpt)) if not c]}
-    for k, v in res.items():
-        doc[k] = v.tolist() if isinstance(v, np.ndarray) else v
+    doc = ev.document(names, [w for w, c in (("seg", args.seg_ckpt), ("fusion", args.fusion_ckpt)) if not c], res)
     path = args.json or os.path.join(args.out, "results.json")
     with open(path, "w") as f:
         json.dump(doc, f, indent=1)

@@ -1370,6 +1370,48 @@ def bilinear_argmax(x, OH, OW):
     return labels
 
 
+def tta_vote(views, flips, OH, OW, want_probs=False):
+    """Multi-scale + flip vote (csrc/tta.hip): views - up to 16 NHWC logit maps (B, ih, iw, C) rows views, C <= 32, as
+    bilinear_argmax takes them; flips - one flag per view (the view's input was mirrored).  Every view is resized to OH x OW
+    (bilinear_argmax's arithmetic, a mirrored one read at the mirrored column), soft-maxed and averaged in list order ->
+    int32 labels (B, OH, OW) = argmax of the mean, or (labels, probs (B, OH, OW, C)) with want_probs.  Neither the resized
+    logits nor, unless asked for, the probabilities are ever formed."""
+    views, flips = list(views), list(flips)
+    if not 1 <= len(views) <= 16 or len(flips) != len(views):
+        raise RuntimeError(f"tta_vote takes 1..16 views and one flip flag per view, got {len(views)} and {len(flips)}")
+    if views[0].dim() != 4:
+        raise RuntimeError("tta_vote expects (B, H, W, C) views")
+    B, C = views[0].shape[0], views[0].shape[3]
+    tab = (_lib.SegmifTtaView * len(views))()
+    nbytes = 4.0 * B * OH * OW * (1 + (C if want_probs else 0))
+    for i, (x, f) in enumerate(zip(views, flips)):
+        if x.dim() != 4 or x.shape[0] != B or x.shape[3] != C or x.device != views[0].device:
+            raise RuntimeError(f"tta_vote: view {i} is {tuple(x.shape)}, expected ({B}, ih, iw, {C}) on one device")
+        _, _, ldx = rows_view(x, f"views[{i}]")
+        tab[i].x, tab[i].ih, tab[i].iw, tab[i].ldx, tab[i].flip = x.data_ptr(), x.shape[1], x.shape[2], ldx, int(bool(f))
+        nbytes += 4.0 * x.numel()
+    labels = torch.empty((B, OH, OW), device=views[0].device, dtype=torch.int32)
+    probs = torch.empty((B, OH, OW, C), device=views[0].device, dtype=torch.float32) if want_probs else None
+    _side("bilinear", lambda: _lib.check(_lib.load().segmif_tta_vote_f32(
+        tab, len(views), labels.data_ptr(), probs.data_ptr() if want_probs else None, B, OH, OW, C, _stream()),
+        "segmif_tta_vote_f32"), nbytes)
+    return (labels, probs) if want_probs else labels
+
+
+def resize_flip_nchw(x, OH, OW, flip):
+    """x (B, C, IH, IW) contiguous NCHW -> flip?(F.interpolate(x, (OH, OW), mode='bilinear', align_corners=False)) in one pass
+    (flip mirrors the width): the network input of one multi-scale view."""
+    _req(x, "x")
+    if x.dim() != 4 or not x.is_contiguous():
+        raise RuntimeError("resize_flip_nchw expects a contiguous (B, C, H, W) tensor")
+    B, C, IH, IW = x.shape
+    out = torch.empty((B, C, OH, OW), device=x.device, dtype=torch.float32)
+    _side("bilinear", lambda: _lib.check(_lib.load().segmif_resize_flip_nchw_f32(
+        x.data_ptr(), out.data_ptr(), B * C, IH, IW, OH, OW, int(bool(flip)), _stream()), "segmif_resize_flip_nchw_f32"),
+        4.0 * B * C * (IH * IW + OH * OW))
+    return out
+
+
 def pointwise2(a, b, mode, out=None):
     """(r6) y = a + b (mode 0), silu(a) + silu(b) (mode 1), silu(a) (mode 2; b None) over rows views of equal shape."""
     rows, C, lda = rows_view(a, "a")

@@ -10,7 +10,7 @@ from .utils.metrics import dequantize_fused, quantize_fused
 
 
 class PairForward:
-    def __init__(self, seg_net, fusion_net, commute_resize=True, uint8_roundtrip=False, return_u8=False):
+    def __init__(self, seg_net, fusion_net, commute_resize=True, uint8_roundtrip=False, return_u8=False, tta=None):
         """uint8_roundtrip: the reference's scripted flow hands the fused image from test_fusion.py to
         test_segmentation.py through uint8 PNG files (uint8(255 x), global min-max rescale over the batch, uint8 -
         test_fusion.py:112-120; read back as float32 / 255 - TaskFusion_dataset2.py:84-88).  True reproduces that
@@ -18,7 +18,10 @@ class PairForward:
         and the returned `fused` is that de-quantised image.  False (default) keeps the fp32 image.
         return_u8 (needs uint8_roundtrip): every call returns a third value, the (B, H, W, 3) uint8 image quantize_fused
         produced inside the body - the PNG pixels themselves (quantising the returned float again would truncate:
-        uint8(255 (u / 255)) is not u for every u, and the min-max rescale would run twice)."""
+        uint8(255 (u / 255)) is not u for every u, and the min-max rescale would run twice).
+        tta: a segmif_amd.tta.TTA - the labels are the multi-scale + flip vote Network3.predict_labels_tta forms from the
+        same fused image (`fused` and the uint8 image are unchanged); eager only, capture() refuses."""
+        self.tta = tta
         if return_u8 and not uint8_roundtrip:
             raise ValueError("return_u8=True needs uint8_roundtrip=True (there is no uint8 image otherwise)")
         self.return_u8 = return_u8
@@ -59,12 +62,17 @@ class PairForward:
         if self.uint8_roundtrip:
             u8 = quantize_fused(fused)
             fused = dequantize_fused(u8)
-        labels = self.seg.predict_labels(fused, vis.shape[2:])
+        if self.tta is not None:  # (the range guard's redo runs this body again for the flagged pairs: every view's forward too)
+            labels = self.seg.predict_labels_tta(fused, vis.shape[2:], self.tta)
+        else:
+            labels = self.seg.predict_labels(fused, vis.shape[2:])
         return (fused, labels, u8) if self.return_u8 else (fused, labels)
 
     def capture(self, ir, vis, mask3, warmup=2):
         """Capture one step on static copies of the inputs; later calls to replay() copy new inputs
         into the static buffers and launch the graph."""
+        if self.tta is not None:
+            raise NotImplementedError("graph capture of the multi-size forward (tta=) is not implemented: use eager()")
         if ops.launch_timer_active():
             raise RuntimeError("disable the launch timer before graph capture")
         self._static = [t.clone() for t in (ir, vis, mask3)]
