@@ -899,6 +899,49 @@ int segmif_adamw_f32(const void* table, const int32_t* chunk_entry, const int64_
                      int chunk_elems, float beta1, float beta2, float eps, float bias_corr1, float bias_corr2_sqrt,
                      void* stream);
 
+/* The guarded step (csrc/grad_guard.hip): gradient norm, clipping and skip-on-non-finite decided on the device, over the SAME
+ * table and chunk arrays as segmif_adamw_f32 (chunk_elems a multiple of 4; the chunks of an entry are neighbours, in offset order).
+ * Neither the reference nor its optimizer has any of this.  Nothing allocates or synchronises; no floating-point atomics: every
+ * sum has one fixed order (lanes, waves, chunks of an entry, entries of the table), so the record is bitwise reproducible.
+ *   record     one SegmifGradGuardRecord on the device, zeroed once by the caller; the counters run on from call to call
+ *   per_entry  nentries SegmifGradEntryStat, rewritten by every call
+ *   entry_slot / param_count (both or neither): entry i of the table is parameter entry_slot[i] of a persistent per-parameter
+ *              array; a skipped step adds 1 to `skipped` of every parameter in the table, a parameter whose gradient held a
+ *              non-finite element adds 1 to its `offended`. */
+typedef struct {
+  double sumsq;               /* sum of g^2 over the FINITE elements of every gradient (squares exact in double) */
+  float norm;                 /* (float)sqrt(sumsq) */
+  float coef;                 /* min(1, max_norm / (norm + 1e-6)): torch.nn.utils.clip_grad_norm_; 1 for max_norm = +inf */
+  uint32_t nonfinite;         /* inf / NaN elements met (not part of sumsq) */
+  uint32_t skip_now;          /* nonfinite != 0 && skip_nonfinite: the guarded update and the scale leave everything untouched */
+  uint32_t attempts, applied, skipped, clipped; /* running: calls; calls not skipped; skipped; applied with coef < 1 */
+  uint32_t consecutive_skips; /* skipped calls since the last applied one */
+  uint32_t reserved;
+} SegmifGradGuardRecord;
+typedef struct { double sumsq; uint32_t nonfinite, reserved; } SegmifGradEntryStat;
+typedef struct { uint32_t skipped, offended; } SegmifGradParamCount;
+int segmif_grad_guard_record_bytes(void);
+int segmif_grad_entry_stat_bytes(void);
+int segmif_grad_param_count_bytes(void);
+/* bytes of `workspace` for a table of nchunks chunks (8-byte aligned; 0: nchunks < 1) */
+int64_t segmif_grad_norm_workspace_bytes(int nchunks);
+/* Two launches: one block per chunk (partials into the workspace), then one block that fills per_entry and the record.
+ * max_norm > 0 (+inf: never clip). */
+int segmif_grad_norm_f32(const void* table, int nentries, const int32_t* chunk_entry, const int64_t* chunk_off, int nchunks,
+                         int chunk_elems, void* workspace, SegmifGradEntryStat* per_entry, SegmifGradGuardRecord* record,
+                         const int32_t* entry_slot, SegmifGradParamCount* param_count, float max_norm, int skip_nonfinite,
+                         void* stream);
+/* segmif_adamw_f32's arithmetic on g * record->coef (exact for coef == 1); with record->skip_now set no block touches p, m or v.
+ * chunk_entry / chunk_off / nchunks may address a sub-range of the table's chunks (one hyper-parameter group).  `step` is the
+ * group's count of ATTEMPTED steps; the kernel takes t = step - param_count[slot].skipped, the applied steps, and forms
+ * 1 - beta1^t and sqrt(1 - beta2^t) in double on the device. */
+int segmif_adamw_guarded_f32(const void* table, const int32_t* chunk_entry, const int64_t* chunk_off, int nchunks, int chunk_elems,
+                             double beta1, double beta2, float eps, int step, const SegmifGradGuardRecord* record,
+                             const int32_t* entry_slot, const SegmifGradParamCount* param_count, void* stream);
+/* g *= record->coef in place for every gradient of the table; nothing when record->skip_now is set (or coef == 1). */
+int segmif_grad_scale_f32(const void* table, const int32_t* chunk_entry, const int64_t* chunk_off, int nchunks, int chunk_elems,
+                          const SegmifGradGuardRecord* record, void* stream);
+
 /*
  * Mix-FFN of a MiT block as ONE kernel (csrc/mixffn.hip), C = 64 | 128 (stages 1-2 of mit_b1 .. b5):
  *     out = x + fc2(GELU(dwconv3x3(fc1(LayerNorm(x)))))     core/mix_transformer.py:46-53, :376-387, :152-155

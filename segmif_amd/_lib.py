@@ -105,6 +105,21 @@ class SegmifSegObjective(ctypes.Structure):
                 ("ignore_index", c_int32), ("reserved", c_int32), ("ohem_n_min", c_int64)]
 
 
+class SegmifGradGuardRecord(ctypes.Structure):
+    _fields_ = [("sumsq", c_double), ("norm", c_float), ("coef", c_float), ("nonfinite", ctypes.c_uint32),
+                ("skip_now", ctypes.c_uint32), ("attempts", ctypes.c_uint32), ("applied", ctypes.c_uint32),
+                ("skipped", ctypes.c_uint32), ("clipped", ctypes.c_uint32), ("consecutive_skips", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class SegmifGradEntryStat(ctypes.Structure):
+    _fields_ = [("sumsq", c_double), ("nonfinite", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class SegmifGradParamCount(ctypes.Structure):
+    _fields_ = [("skipped", ctypes.c_uint32), ("offended", ctypes.c_uint32)]
+
+
 class SegmifTtaView(ctypes.Structure):
     _fields_ = [("x", c_void_p), ("ih", c_int32), ("iw", c_int32), ("ldx", c_int32), ("flip", c_int32)]
 
@@ -268,6 +283,15 @@ SIGNATURES = {
     "segmif_adamw_entry_bytes": (c_int, []),
     "segmif_adamw_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_float, c_float, c_float,
                                c_void_p]),
+    "segmif_grad_guard_record_bytes": (c_int, []),
+    "segmif_grad_entry_stat_bytes": (c_int, []),
+    "segmif_grad_param_count_bytes": (c_int, []),
+    "segmif_grad_norm_workspace_bytes": (c_int64, [c_int]),
+    "segmif_grad_norm_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_float, c_int, c_void_p]),
+    "segmif_adamw_guarded_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_float, c_int, c_void_p,
+                                       c_void_p, c_void_p, c_void_p]),
+    "segmif_grad_scale_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "segmif_seg_normalize_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "segmif_nchw_to_nhwc_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p]),
     "segmif_nhwc_to_nchw_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p]),

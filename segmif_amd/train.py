@@ -16,6 +16,7 @@ segmif_amd.data makes on the device (main() below; one process, one GPU).  --seg
 (make_seg_loss): the reference's CE by default, or OHEM / focal / NormalLoss / class-weighted CE on csrc/seg_objective.hip.
 """
 import argparse
+import math
 import os
 import sys
 
@@ -115,7 +116,11 @@ class FusionTrainer:
 
     fusion_loss: None (default) is the reference's schedule - Fusionloss3 in round 1, Fusionloss_grad3 as the intensity term
     afterwards.  Otherwise a callable (ir, vis_ycrcb, fused, mask3) -> scalar, e.g. any 4-argument objective of core/loss.py or
-    make_fusion_loss(NAME), evaluated in their place; everything around it (the segmentation term, the weights) is unchanged."""
+    make_fusion_loss(NAME), evaluated in their place; everything around it (the segmentation term, the weights) is unchanged.
+
+    An optimizer built with skip_nonfinite (utils/optimizer.FusedAdamW's guard; this project's addition) changes one thing here: a
+    step whose loss1 or loss2 is not finite is not appended to `history`, so the dynamic weights of the following steps are not
+    formed from it.  Under a reducer the gradients are reduced before optimizer.step(), so every rank takes the same decision."""
 
     def __init__(self, seg_net, fusion_net, optimizer, criterion, iter_=2, reducer=None, seg_weight_grads=False,
                  report_lap=False, fusion_loss=None):
@@ -167,8 +172,9 @@ class FusionTrainer:
             w0 = w1 = 1.0
             n = len(self.history)
             if sync_loss_history:  # the reference's .item() host syncs (train.py:370-371, 377-378)
-                self.history.append((allreduce_scalar_mean(float(loss1.detach())),
-                                     allreduce_scalar_mean(float(loss2.detach()))))
+                pair = (allreduce_scalar_mean(float(loss1.detach())), allreduce_scalar_mean(float(loss2.detach())))
+                if not getattr(self.opt, "skip_nonfinite", False) or (math.isfinite(pair[0]) and math.isfinite(pair[1])):
+                    self.history.append(pair)
                 if n > 10:
                     r = torch.tensor([self.history[n - 1][0] / self.history[n - 2][0],
                                       self.history[n - 1][1] / self.history[n - 2][1]])
@@ -190,25 +196,26 @@ SEG_CKPT, FUSION_CKPT = "model-fusion_add_final2.pth", "modelfusion-final2.pth" 
 
 
 def make_seg_optimizer(seg_net, iter_curr=0, lr=8e-5, weight_decay=0.01, betas=(0.9, 0.999), warmup_iter=3000, max_iter=160000,
-                       warmup_ratio=1e-6, power=1.0):
-    """train.py:173-200: [encoder non-norm | encoder norm, no decay | decoder + classifier at 10 x lr]"""
+                       warmup_ratio=1e-6, power=1.0, max_grad_norm=None, skip_nonfinite=False):
+    """train.py:173-200: [encoder non-norm | encoder norm, no decay | decoder + classifier at 10 x lr].  max_grad_norm /
+    skip_nonfinite: the optimizer's guard (utils/optimizer.FusedAdamW), off by default; not the reference's."""
     from .utils.optimizer import PolyWarmupAdamW_seg
     g = seg_net.denoise_net.get_param_groups()
     return PolyWarmupAdamW_seg(
         params=[{"params": g[0], "lr": lr, "weight_decay": weight_decay}, {"params": g[1], "lr": lr, "weight_decay": 0.0},
                 {"params": g[2], "lr": lr * 10, "weight_decay": weight_decay}],
         lr=lr, weight_decay=weight_decay, betas=list(betas), iter_curr=iter_curr, warmup_iter=warmup_iter, max_iter=max_iter,
-        warmup_ratio=warmup_ratio, power=power)
+        warmup_ratio=warmup_ratio, power=power, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
 
 
 def make_fusion_optimizer(fusion_net, iter_, lr=8e-5, weight_decay=0.01, betas=(0.9, 0.999), max_iter=160000, warmup_ratio=1e-6,
-                          power=1.0):
+                          power=1.0, max_grad_norm=None, skip_nonfinite=False):
     """train.py:316-332: one group at lr / iter_; the default 3e-4 / iter_ and warmup_iter = 3e-5 / iter_ are constants of the
     reference's code (the warm-up branch is never taken)"""
     from .utils.optimizer import PolyWarmupAdamW
     return PolyWarmupAdamW(params=[{"params": list(fusion_net.parameters()), "lr": lr / iter_, "weight_decay": weight_decay}],
                            lr=3e-4 / iter_, weight_decay=weight_decay, betas=list(betas), warmup_iter=3e-5 / iter_, max_iter=max_iter,
-                           warmup_ratio=warmup_ratio, power=power)
+                           warmup_ratio=warmup_ratio, power=power, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
 
 
 def fusion_loss_names():
@@ -270,6 +277,42 @@ def make_seg_loss(name, ignore_index=255, ohem_thresh=0.7, ohem_n_min=None, foca
     if class_weights is None:
         raise ValueError("'weighted' needs class_weights")
     return losses.SegObjective(label_smoothing=label_smoothing, weight=class_weights, ignore_index=ignore_index)
+
+
+class _GuardLog:
+    """What a log line adds when the optimizer is guarded: ONE grad_stats() readback per line (never per step) - the last step's
+    gradient norm, the steps clipped and skipped since the previous line, the parameters that carried non-finite gradients - and
+    the stop after more than `max_consecutive` skipped steps in a row (the weights are frozen: running on helps nobody)."""
+
+    def __init__(self, optimizer, modules, max_consecutive):
+        self.opt, self.max_consecutive = optimizer, max_consecutive
+        self.names = {id(p): n for prefix, m in modules for n, p in m.named_parameters(prefix=prefix)}
+        self.clipped = self.skipped = 0
+        self.offended, self.stop = {}, None
+
+    def line(self):
+        st = self.opt.grad_stats()
+        text = f" gnorm {st['norm']:.4e} clipped {st['clipped'] - self.clipped} skipped {st['skipped'] - self.skipped}"
+        worst = sorted(((e["offended_steps"] - self.offended.get(id(e["param"]), 0), e["nonfinite"],
+                         self.names.get(id(e["param"]), "?")) for e in st["per_param"]), reverse=True)
+        worst = [w for w in worst if w[0] > 0]
+        if st["skipped"] > self.skipped and worst:
+            text += " non-finite gradients in " + ", ".join(f"{n} ({k} steps)" for k, _, n in worst[:3])
+            if len(worst) > 3:
+                text += f" and {len(worst) - 3} more"
+        self.clipped, self.skipped = st["clipped"], st["skipped"]
+        self.offended = {id(e["param"]): e["offended_steps"] for e in st["per_param"]}
+        self.stop = None
+        if st["consecutive_skips"] > self.max_consecutive:
+            now = [self.names.get(id(e["param"]), "?") for e in st["per_param"] if e["nonfinite"]]
+            self.stop = (f"[train] {st['consecutive_skips']} steps in a row were skipped for non-finite gradients "
+                         f"(--max-consecutive-skips {self.max_consecutive}): the weights no longer change.  Parameters with "
+                         f"non-finite gradients in the last step: {', '.join(now[:8])}" + (f" and {len(now) - 8} more" if len(now) > 8 else ""))
+        return text
+
+    def check(self):
+        if self.stop:
+            raise SystemExit(self.stop)
 
 
 def _miou(seg, fus, val, batch):
@@ -340,6 +383,13 @@ def main(argv=None):
     ap.add_argument("--label-smoothing", type=float, default=0.0, help="--seg-loss ce / weighted: label smoothing in [0, 1); above 0 it is "
                     "not the reference's objective")
     ap.add_argument("--seg-class-weights", type=float, nargs="+", metavar="W", help="--seg-loss weighted: one weight >= 0 per class (9)")
+    ap.add_argument("--clip-grad-norm", type=float, metavar="X", help="clip the global gradient norm of every step of both phases to "
+                    "X > 0 (torch.nn.utils.clip_grad_norm_'s rule, on the device); off by default.  This project's addition: the "
+                    "reference's train.py does not clip")
+    ap.add_argument("--skip-nonfinite", action="store_true", help="do not apply a step whose gradients hold an inf or a NaN (decided on "
+                    "the device, no host synchronisation); off by default.  This project's addition")
+    ap.add_argument("--max-consecutive-skips", type=int, default=50, metavar="N", help="with --skip-nonfinite: stop when more than N "
+                    "steps in a row were skipped (checked at log lines)")
     ap.add_argument("--log-iters", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args(argv)
@@ -357,6 +407,10 @@ def main(argv=None):
         ap.error(f"--ohem-thresh {args.ohem_thresh}: a probability in (0, 1]")
     if args.seg_loss == "focal" and not args.focal_gamma > 0:
         ap.error(f"--focal-gamma {args.focal_gamma}: must be > 0")
+    if args.clip_grad_norm is not None and not (args.clip_grad_norm > 0 and math.isfinite(args.clip_grad_norm)):
+        ap.error(f"--clip-grad-norm {args.clip_grad_norm}: must be a finite number > 0")
+    if args.max_consecutive_skips < 1:
+        ap.error(f"--max-consecutive-skips {args.max_consecutive_skips}: must be >= 1")
     seg_pixels = max(1, args.samples_per_gpu // 2) * args.crop_size ** 2
     if args.ohem_n_min is None:
         args.ohem_n_min = max(1, seg_pixels // 16)
@@ -401,6 +455,12 @@ def main(argv=None):
         print(f"[train] --seg-loss {args.seg_loss}" + (f" --label-smoothing {args.label_smoothing}" if args.label_smoothing else "")
               + ": NOT the reference's segmentation objective (segmentation phase only; the fusion phase's segmentation term keeps CE)")
     sched = dict(weight_decay=args.weight_decay, betas=args.betas, max_iter=args.max_iters, warmup_ratio=args.warmup_ratio, power=args.power)
+    guarded = args.clip_grad_norm is not None or args.skip_nonfinite
+    if guarded:
+        sched.update(max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite)
+        print("[train] " + " ".join(([f"--clip-grad-norm {args.clip_grad_norm}"] if args.clip_grad_norm is not None else [])
+                                    + (["--skip-nonfinite"] if args.skip_nonfinite else []))
+              + ": this project's additions, NOT the reference's training (its train.py neither clips gradients nor skips a step)")
     loader_kw = dict(batch=batch, crop_size=args.crop_size, rescale_range=tuple(args.rescale_range), fliplr=True)
     best, wrote_seg = None, False
     fusion_loss = make_fusion_loss(args.fusion_loss) if args.fusion_loss is not None else None
@@ -417,13 +477,16 @@ def main(argv=None):
             seg.load_state_dict(torch.load(seg_path, map_location="cuda"))
         trainer = FusionTrainer(seg, fus, make_fusion_optimizer(fus, iter_, lr=args.lr, **sched), crit, iter_=iter_,
                                 fusion_loss=fusion_loss)
+        glog = _GuardLog(trainer.opt, [("fusion_net", fus)], args.max_consecutive_skips) if guarded else None
         batches = AugmentedBatches(train_set, seed=args.seed + 2 * iter_, **loader_kw)
         n_fus = args.fusion_iters if args.fusion_iters is not None else (6000 if iter_ == 1 else 4000)
         for n in range(n_fus):
             _, ir3, vis3, mask3, label = next(batches)
             loss = trainer.step(ir3, vis3, mask3, label)
             if (n + 1) % args.log_iters == 0 or n + 1 == n_fus:
-                print(f"[train] round {iter_} fusion iter {n + 1}/{n_fus}: loss {float(loss):.6f}")
+                print(f"[train] round {iter_} fusion iter {n + 1}/{n_fus}: loss {float(loss):.6f}" + (glog.line() if guarded else ""))
+                if guarded:
+                    glog.check()
             if (n + 1) % 500 == 0:
                 torch.save(fus.state_dict(), fus_path)
         torch.save(fus.state_dict(), fus_path)
@@ -435,13 +498,17 @@ def main(argv=None):
             best = _miou(seg, fus, val_set, batch)
             print(f"[train] initial mIoU {best:.4f}")
         opt = make_seg_optimizer(seg, iter_curr=(iter_ - 1) * 10000, lr=args.lr, warmup_iter=args.warmup_iter, **sched)
+        glog = _GuardLog(opt, [("seg_net", seg)], args.max_consecutive_skips) if guarded else None
         batches = AugmentedBatches(fused_set, seed=args.seed + 2 * iter_ + 1, photometric=(), **loader_kw)
         n_seg = args.seg_iters if args.seg_iters is not None else 10000
         for n in range(n_seg):
             _, _, fused3, _, label = next(batches)
             loss = seg_train_step(seg, opt, fused3, label, seg_crit)
             if (n + 1) % args.log_iters == 0 or n + 1 == n_seg:
-                print(f"[train] round {iter_} segmentation iter {n + 1}/{n_seg}: lr {opt.param_groups[0]['lr']:.3e} loss {float(loss):.6f}")
+                print(f"[train] round {iter_} segmentation iter {n + 1}/{n_seg}: lr {opt.param_groups[0]['lr']:.3e} loss {float(loss):.6f}"
+                      + (glog.line() if guarded else ""))
+                if guarded:
+                    glog.check()
             if (n + 1) % 1000 == 0 or n + 1 == n_seg:
                 miou = _miou(seg, fus, val_set, batch)
                 if miou > best:  # (train.py:237: only an improvement is written)
