@@ -878,6 +878,46 @@ int segmif_seg_objective_bwd_f32(const SegmifSegObjective* desc, const float* lo
                                  const float* class_weight, const void* workspace, const float* record4, const float* upstream,
                                  float* dlogits, int64_t rows, int C, int ld, int ldd, void* stream);
 
+/* The region objectives that go with them (csrc/region_objective.hip): Lovasz-Softmax (Berman et al. 2018, the batch as one set)
+ * and soft Dice over the same rows (rows x C, pitch ld >= C, C <= 32, int64 labels).  Neither is the reference's.  A row is valid
+ * when its label lies in [0, C) and is not ignore_index; invalid rows take no part and get gradient 0.  With p = softmax(x),
+ * fg_ic = [y_i == c] and the sums over the P valid rows:
+ *   SEGMIF_REGION_LOVASZ  e_ic = |fg_ic - p_ic|, for the labelled class formed as q = sum_{k != y} e_k / sum e_k.  The errors of a
+ *                         class are sorted in descending order, rows with bit-equal float32 errors by ASCENDING ROW INDEX.  With
+ *                         G = sum fg and F_k the foreground rows among the first k: J_k = 1 - (G - F_k) / (G + k - F_k), J_0 = 0,
+ *                         g_k = J_k - J_{k-1}, loss_c = sum_k e_(k) g_k (an absent class: max_i p_ic).  The gradient takes g as
+ *                         constant: d loss_c / d e_i = g_rank(i), chained through sign(p_ic - fg_ic) and the softmax.
+ *   SEGMIF_REGION_DICE    I_c = sum p_ic fg_ic, S_c = sum p_ic, G_c = sum fg_ic, D_c = 1 - (2 I_c + smooth) / (S_c + G_c + smooth).
+ * The result is the mean over the classes with G > 0 (SEGMIF_REGION_PRESENT) or over all C (SEGMIF_REGION_ALL); with no class to
+ * average, or no valid row, it is 0 with gradient 0.
+ *   segmif_region_objective_workspace_bytes  bytes of `workspace` (16-byte aligned); 0: rows < 1, C outside 1..32, rows * C beyond
+ *                                    2^31 - 1 (the kernels' index type), an unknown kind.  Lovasz keeps two (key, row) pairs per
+ *                                    row and class for its sort: 16 rows C bytes and a little more.
+ *   segmif_region_objective_f32      record4 = {loss, 1 / n, n, P}, n the classes averaged (device floats).  Lovasz: a stable LSD
+ *                                    radix sort of every class's errors (ranks from ballots and prefix sums, never from atomics:
+ *                                    the tie order, and with it the gradient, is the same in every run), an integer scan of the
+ *                                    sorted foreground flags, g_k in double from (k, F_k, G); the workspace keeps g per row and class.
+ *   segmif_region_objective_bwd_f32  dlogits (pitch ldd >= C) = upstream[0] * d loss / d logits, the softmax recomputed, already
+ *                                    scaled; workspace (the forward's), record4 and upstream are read on the device.
+ * No host synchronisation, no floating-point atomics, fixed-order sums, a launch sequence that does not depend on the data:
+ * bit-identical from run to run, capturable in a hipGraph.  SEGMIF_EINVAL before any launch: the size query's zero cases, ld < C,
+ * ldd < C, an unknown kind or classes, smooth negative or not finite, a NULL or misaligned workspace. */
+enum { SEGMIF_REGION_LOVASZ = 0, SEGMIF_REGION_DICE = 1 };
+enum { SEGMIF_REGION_PRESENT = 0, SEGMIF_REGION_ALL = 1 };
+
+typedef struct {
+  int32_t kind, classes, ignore_index;
+  float smooth;
+  int32_t reserved[4];
+} SegmifRegionObjective;
+
+int64_t segmif_region_objective_workspace_bytes(int64_t rows, int C, int kind);
+int segmif_region_objective_f32(const SegmifRegionObjective* desc, const float* logits, const int64_t* labels, void* workspace,
+                                float* record4, int64_t rows, int C, int ld, void* stream);
+int segmif_region_objective_bwd_f32(const SegmifRegionObjective* desc, const float* logits, const int64_t* labels,
+                                    const void* workspace, const float* record4, const float* upstream, float* dlogits,
+                                    int64_t rows, int C, int ld, int ldd, void* stream);
+
 /* The fusion net's shared scalar PReLU (core/model_fusion.py:1038) on the training path, kept apart from the conv so
  * that the backward reads the branch off the pre-activation z (any slope, also <= 0): y = z > 0 ? z : a z;
  * dz = dy (z > 0 ? 1 : a), dslope[0] = sum over z <= 0 of dy z (fp64 two-pass).  16-byte path when n % 4 == 0 and the

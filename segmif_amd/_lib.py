@@ -105,6 +105,10 @@ class SegmifSegObjective(ctypes.Structure):
                 ("ignore_index", c_int32), ("reserved", c_int32), ("ohem_n_min", c_int64)]
 
 
+class SegmifRegionObjective(ctypes.Structure):
+    _fields_ = [("kind", c_int32), ("classes", c_int32), ("ignore_index", c_int32), ("smooth", c_float), ("reserved", c_int32 * 4)]
+
+
 class SegmifGradGuardRecord(ctypes.Structure):
     _fields_ = [("sumsq", c_double), ("norm", c_float), ("coef", c_float), ("nonfinite", ctypes.c_uint32),
                 ("skip_now", ctypes.c_uint32), ("attempts", ctypes.c_uint32), ("applied", ctypes.c_uint32),
@@ -280,6 +284,11 @@ SIGNATURES = {
                                          c_int, c_void_p]),
     "segmif_seg_objective_bwd_f32": (c_int, [POINTER(SegmifSegObjective), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
+    "segmif_region_objective_workspace_bytes": (c_int64, [c_int64, c_int, c_int]),
+    "segmif_region_objective_f32": (c_int, [POINTER(SegmifRegionObjective), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                            c_void_p]),
+    "segmif_region_objective_bwd_f32": (c_int, [POINTER(SegmifRegionObjective), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "segmif_adamw_entry_bytes": (c_int, []),
     "segmif_adamw_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_float, c_float, c_float,
                                c_void_p]),

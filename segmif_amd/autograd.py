@@ -1527,6 +1527,51 @@ class SegObjectiveFn(torch.autograd.Function):
         return dlog, None, None, None
 
 
+_REGION_KINDS = {"lovasz": 0, "dice": 1}
+_REGION_CLASSES = {"present": 0, "all": 1}
+
+
+def region_objective_descriptor(kind="lovasz", classes="present", ignore_index=255, smooth=1.0):
+    """The SegmifRegionObjective of losses.RegionObjective's settings."""
+    d = _lib.SegmifRegionObjective()
+    d.kind, d.classes, d.ignore_index, d.smooth = _REGION_KINDS[kind], _REGION_CLASSES[classes], ignore_index, smooth
+    return d
+
+
+class RegionObjectiveFn(torch.autograd.Function):
+    """losses.RegionObjective on the device (csrc/region_objective.hip).  Forward: Lovasz-Softmax - the per-class errors, their
+    stable radix sort, the Jaccard increments g and a 4-float device record {loss, 1 / classes averaged, classes averaged, valid
+    rows}; Dice - the per-class sums and the same record.  Backward: one launch that recomputes the softmax and writes dlogits
+    already scaled by the record and the upstream gradient; what it keeps from the forward is the workspace (Lovasz: g per row and
+    class inside the sort's buffers; Dice: a few hundred bytes of per-class coefficients).  No host sync."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, desc):
+        rows, C, ld = rows_view(logits, "logits")
+        lib = _lib.load()
+        nbytes = lib.segmif_region_objective_workspace_bytes(rows, C, desc.kind)
+        if nbytes <= 0:
+            raise RuntimeError(f"segmif_region_objective_workspace_bytes refused rows = {rows}, C = {C}, kind = {desc.kind}")
+        ws = torch.empty((nbytes,), device=logits.device, dtype=torch.uint8)
+        rec = torch.empty((4,), device=logits.device, dtype=torch.float32)
+        _lib.check(lib.segmif_region_objective_f32(ctypes.byref(desc), logits.data_ptr(), labels.data_ptr(), ws.data_ptr(),
+                                                   rec.data_ptr(), rows, C, ld, _stream()), "segmif_region_objective_f32")
+        ctx.save_for_backward(logits, labels, ws, rec)
+        ctx.desc = desc
+        return rec[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, labels, ws, rec = ctx.saved_tensors
+        rows, C, ld = rows_view(logits, "logits")
+        up = g.reshape(1).float().contiguous()
+        dlog = torch.empty(logits.shape, device=logits.device, dtype=torch.float32)
+        _lib.check(_lib.load().segmif_region_objective_bwd_f32(ctypes.byref(ctx.desc), logits.data_ptr(), labels.data_ptr(),
+                                                               ws.data_ptr(), rec.data_ptr(), up.data_ptr(), dlog.data_ptr(), rows, C,
+                                                               ld, C, _stream()), "segmif_region_objective_bwd_f32")
+        return dlog, None, None
+
+
 class NchwToNhwcFn(torch.autograd.Function):
     """contiguous (B, C, H, W) -> contiguous (B, H, W, C) and back for the gradient: the two layout kernels"""
 
@@ -1562,18 +1607,23 @@ def nhwc_rows_of(logits):
     raise RuntimeError(f"logits must be contiguous or channels-last in memory, got strides {logits.stride()} for {tuple(logits.shape)}")
 
 
-def seg_objective(logits_nhwc, labels, gamma=0.0, label_smoothing=0.0, weight=None, ignore_index=255, reduction="mean", ohem_t=0.0,
-                  ohem_n_min=0):
-    """losses.SegObjective's value for NHWC logits (..., C) - a rows view, C <= 32 - and labels with one entry per row (any integer
-    type; converted to int64 on the device).  weight: (C,) float32 device class weights or None.  ohem_t = -log(thresh)."""
+def _seg_rows_and_labels(logits_nhwc, labels, what):
+    """(rows, C, int64 labels) of NHWC logits (..., C) - a rows view, C <= 32 - and labels with one entry per row"""
     rows, C, _ = rows_view(logits_nhwc, "logits")
     if C > 32:
-        raise RuntimeError(f"the segmentation-objective kernel holds a row of at most 32 classes in registers, got {C}")
+        raise RuntimeError(f"the {what} kernel holds a row of at most 32 classes in registers, got {C}")
     if not isinstance(labels, torch.Tensor) or not labels.is_cuda or labels.is_floating_point():
         raise RuntimeError("segmif_amd: labels must be an integer tensor on the MI355X device (the HIP path has no CPU fallback)")
     if labels.numel() != rows:
         raise RuntimeError(f"labels hold {labels.numel()} entries for {rows} rows of logits")
-    labels = labels.detach().long().contiguous()
+    return rows, C, labels.detach().long().contiguous()
+
+
+def seg_objective(logits_nhwc, labels, gamma=0.0, label_smoothing=0.0, weight=None, ignore_index=255, reduction="mean", ohem_t=0.0,
+                  ohem_n_min=0):
+    """losses.SegObjective's value for NHWC logits (..., C) - a rows view, C <= 32 - and labels with one entry per row (any integer
+    type; converted to int64 on the device).  weight: (C,) float32 device class weights or None.  ohem_t = -log(thresh)."""
+    rows, C, labels = _seg_rows_and_labels(logits_nhwc, labels, "segmentation-objective")
     if weight is not None:
         weight = _req(weight, "class weights").detach().contiguous()
         if weight.numel() != C:
@@ -1583,6 +1633,16 @@ def seg_objective(logits_nhwc, labels, gamma=0.0, label_smoothing=0.0, weight=No
                          "out of range")
     desc = seg_objective_descriptor(gamma, label_smoothing, ignore_index, reduction, ohem_t, ohem_n_min)
     return SegObjectiveFn.apply(logits_nhwc, labels, weight, desc)
+
+
+def region_objective(logits_nhwc, labels, kind="lovasz", classes="present", ignore_index=255, smooth=1.0):
+    """losses.RegionObjective's value for NHWC logits (..., C) - a rows view, C <= 32 - and labels with one entry per row (any integer
+    type; converted to int64 on the device)."""
+    if kind not in _REGION_KINDS or classes not in _REGION_CLASSES:
+        raise ValueError(f"region_objective: kind {kind!r} / classes {classes!r}: one of {', '.join(_REGION_KINDS)} / "
+                         f"{', '.join(_REGION_CLASSES)}")
+    _, _, labels = _seg_rows_and_labels(logits_nhwc, labels, "region-objective")
+    return RegionObjectiveFn.apply(logits_nhwc, labels, region_objective_descriptor(kind, classes, ignore_index, smooth))
 
 
 # functional front-ends ------------------------------------------------------------------------------

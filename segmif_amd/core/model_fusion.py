@@ -760,7 +760,8 @@ def seg_criterion_loss(seg, label, criterion):
     """criterion(bilinear-up(seg -> label size), label) for NHWC logits `seg` (ref :1095-1096, :241-244).  With the criterion
     train.py builds - nn.CrossEntropyLoss(ignore_index=...), mean reduction, no class weights - the whole chain (x4 bilinear,
     softmax-CE with ignore_index, their backward) runs in two HIP kernels.  A losses.SegObjective, or one of core/loss.py's OhemCELoss /
-    SoftmaxFocalLoss / NormalLoss, which hold one, gets the bilinear kernel's NHWC output directly.  Any other criterion is the CALLER's code: it receives
+    SoftmaxFocalLoss / NormalLoss, which hold one, gets the bilinear kernel's NHWC output directly, and so does a
+    losses.RegionObjective or a losses.SegLossSum (whose plain-CE base stays on ag.softmax_ce).  Any other criterion is the CALLER's code: it receives
     the up-sampled logits as an NCHW view of the HIP bilinear kernel's output (with its HIP backward) - (r6) no F.interpolate, no
     aten op of this package's own on the way."""
     H, W = label.shape[1:]
@@ -771,6 +772,8 @@ def seg_criterion_loss(seg, label, criterion):
             and getattr(criterion, "label_smoothing", 0.0) == 0.0 and seg.shape[-1] <= 32:
         return ag.softmax_ce(up, label.type(torch.long), criterion.ignore_index)
     if isinstance(criterion, (losses.SegObjective, losses.SegObjectiveLoss)):  # OHEM / focal / weighted CE: csrc/seg_objective.hip
+        return criterion.forward_nhwc(up, label)
+    if isinstance(criterion, (losses.RegionObjective, losses.SegLossSum)):  # Lovasz / Dice, alone or added: csrc/region_objective.hip
         return criterion.forward_nhwc(up, label)
     return criterion(ops.as_nchw(up), label.type(torch.long))
 

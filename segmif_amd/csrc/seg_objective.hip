@@ -26,12 +26,13 @@
 #include <cmath>
 #include <stdint.h>
 
+#include "seg_rows.h"
 #include "segmif_hip.h"
+
+using namespace segmif;
 
 namespace {
 
-constexpr int ROWS = 256;        // rows of a block: one per thread
-constexpr int PITCH = 33;        // LDS row pitch in floats (odd: a wave's rows fall into distinct banks)
 constexpr int HEADER = 4352;     // bytes: 4 x 256 histogram counters, then the select state (4 counters), padded
 constexpr int NPART = 5;         // doubles of a block's partial: sum l, denominator, #{l > t}, sum_{l > t} l, sum_{l > kappa} l
 
@@ -69,54 +70,6 @@ __device__ __forceinline__ unsigned order_key(float v) {
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 __device__ __forceinline__ float key_value(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-// the block's rows r0 .. r0 + nr - 1 -> tile[row * PITCH + c]
-__device__ __forceinline__ void stage_rows(float* __restrict__ tile, const float* __restrict__ x, long long r0, int nr, int C, int ld,
-                                           int vec) {
-  const int n = nr * C;
-  if (vec) {  // ld == C, 16-byte aligned base: the block's floats are one aligned run (r0 * C * 4 bytes is a multiple of 16)
-    const float* base = x + r0 * C;
-    for (int i = threadIdx.x; i < n / 4; i += ROWS) {
-      const float4 v = reinterpret_cast<const float4*>(base)[i];
-      const float e[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int f = 4 * i + j;
-        tile[(f / C) * PITCH + f % C] = e[j];
-      }
-    }
-    for (int f = (n / 4) * 4 + threadIdx.x; f < n; f += ROWS) tile[(f / C) * PITCH + f % C] = base[f];
-  } else {
-    for (int f = threadIdx.x; f < n; f += ROWS) {
-      const int r = f / C, c = f % C;
-      tile[r * PITCH + c] = x[(r0 + r) * ld + c];
-    }
-  }
-}
-
-// the same way back: tile -> g (pitch ldd)
-__device__ __forceinline__ void unstage_rows(const float* __restrict__ tile, float* __restrict__ g, long long r0, int nr, int C, int ldd,
-                                             int vec) {
-  const int n = nr * C;
-  if (vec) {
-    float* base = g + r0 * C;
-    for (int i = threadIdx.x; i < n / 4; i += ROWS) {
-      float e[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int f = 4 * i + j;
-        e[j] = tile[(f / C) * PITCH + f % C];
-      }
-      reinterpret_cast<float4*>(base)[i] = make_float4(e[0], e[1], e[2], e[3]);
-    }
-    for (int f = (n / 4) * 4 + threadIdx.x; f < n; f += ROWS) base[f] = tile[(f / C) * PITCH + f % C];
-  } else {
-    for (int f = threadIdx.x; f < n; f += ROWS) {
-      const int r = f / C, c = f % C;
-      g[(r0 + r) * ldd + c] = tile[r * PITCH + c];
-    }
-  }
-}
 
 // one row's softmax in registers: p[c] (0 for c >= C), and what the loss and its gradient need of it
 struct Row {
@@ -365,8 +318,6 @@ __global__ __launch_bounds__(ROWS) void seg_objective_bwd_kernel(SegArgs a, cons
   __syncthreads();
   unstage_rows(tile, g, r0, nr, a.C, ldd, vec_out);
 }
-
-bool aligned16(const void* p) { return !((uintptr_t)p & 15); }
 
 bool known_reduction(int r) { return r == SEGMIF_SEG_MEAN_VALID || r == SEGMIF_SEG_MEAN_ALL || r == SEGMIF_SEG_OHEM; }
 

@@ -13,6 +13,9 @@ mean rho(w (L(gen) - t)) and a function combining their means; one HIP kernel pa
 SegObjective is the segmentation phase's counterpart: cross entropy with class weights / label smoothing, the focal loss, and the
 three reductions (mean over valid pixels, mean over all pixels, OHEM) of core/loss.py:342-383 on one HIP kernel pair
 (csrc/seg_objective.hip).  Device float32 logits only: there is no torch formulation of it in the package.
+
+RegionObjective adds the region objectives - Lovasz-Softmax and soft Dice (csrc/region_objective.hip) - and SegLossSum adds one of
+them to a per-pixel criterion on the same logits.  Neither is the reference's.
 """
 import math
 from typing import NamedTuple
@@ -300,3 +303,84 @@ class SegObjectiveLoss(nn.Module):
 
     def forward_nhwc(self, logits_nhwc, labels):
         return self.objective.forward_nhwc(logits_nhwc, labels)
+
+
+# ---- the region objectives (csrc/region_objective.hip) ----------------------------------------------------------------------------------
+REGION_KINDS = ("lovasz", "dice")
+REGION_CLASSES = ("present", "all")
+
+
+class RegionObjective(nn.Module):
+    """A region objective over softmax(logits), forward and backward in csrc/region_objective.hip; not the reference's.  A pixel is
+    valid when its label lies in [0, C) and is not ignore_index; fg_ic = [y_i == c]; sums over the valid pixels of the whole batch:
+        kind "lovasz"  Lovasz-Softmax (Berman et al. 2018, per_image=False): per class the errors e_i = |fg_ic - p_ic| sorted in
+                       descending order (bit-equal float32 errors by ascending pixel index), G = sum fg, F_k the foreground pixels
+                       among the first k, J_k = 1 - (G - F_k) / (G + k - F_k), loss_c = sum_k e_(k) (J_k - J_{k-1})
+        kind "dice"    D_c = 1 - (2 sum p_ic fg_ic + smooth) / (sum p_ic + sum fg_ic + smooth)
+        classes        "present": the mean over the classes that have a pixel | "all": over all C (an absent class's Lovasz term
+                       is max_i p_ic).  With nothing to average the value is 0 and so is the gradient.
+    No host synchronisation: it runs inside GraphedSegTrainStep's capture.  Device float32 logits only."""
+
+    def __init__(self, kind="lovasz", classes="present", ignore_index=255, smooth=1.0):
+        super().__init__()
+        if kind not in REGION_KINDS:
+            raise ValueError(f"RegionObjective: kind must be one of {', '.join(REGION_KINDS)}, got {kind!r}")
+        if classes not in REGION_CLASSES:
+            raise ValueError(f"RegionObjective: classes must be one of {', '.join(REGION_CLASSES)}, got {classes!r}")
+        smooth = float(smooth)
+        if not (math.isfinite(smooth) and smooth >= 0.0):
+            raise ValueError(f"RegionObjective: smooth must be finite and >= 0, got {smooth}")
+        self.kind, self.classes, self.ignore_index, self.smooth = kind, classes, int(ignore_index), smooth
+
+    def extra_repr(self):
+        s = f"kind={self.kind!r}, classes={self.classes!r}, ignore_index={self.ignore_index}"
+        return s + (f", smooth={self.smooth}" if self.kind == "dice" else "")
+
+    def forward_nhwc(self, logits_nhwc, labels):
+        """logits_nhwc: (..., C) float32 device rows (a channel slice of a wider buffer is fine); labels: one per row"""
+        from . import autograd as ag
+        return ag.region_objective(logits_nhwc, labels, kind=self.kind, classes=self.classes, ignore_index=self.ignore_index,
+                                   smooth=self.smooth)
+
+    def forward(self, logits, labels):
+        """logits: logical (B, C, H, W), contiguous or channels-last in memory; the gradient comes back in the same layout"""
+        from . import autograd as ag
+        return self.forward_nhwc(ag.nhwc_rows_of(logits), labels)
+
+
+class SegLossSum(nn.Module):
+    """base(logits, labels) + region_weight * region(logits, labels) on the SAME NHWC logits.  base: an nn.CrossEntropyLoss that the
+    softmax-CE kernel covers (mean reduction, no class weights, no label smoothing: it stays on autograd.softmax_ce, the bits it
+    has on its own), a SegObjective or a SegObjectiveLoss; region: a RegionObjective."""
+
+    def __init__(self, base, region, region_weight=1.0):
+        super().__init__()
+        if isinstance(base, nn.CrossEntropyLoss):
+            if base.weight is not None or base.reduction != "mean" or getattr(base, "label_smoothing", 0.0) != 0.0:
+                raise ValueError("SegLossSum: an nn.CrossEntropyLoss base must have mean reduction, no class weights and no label "
+                                 "smoothing (SegObjective.from_criterion covers the rest)")
+        elif not isinstance(base, (SegObjective, SegObjectiveLoss)):
+            raise TypeError(f"SegLossSum: base must be an nn.CrossEntropyLoss, a SegObjective or a SegObjectiveLoss, got "
+                            f"{type(base).__name__}")
+        if not isinstance(region, RegionObjective):
+            raise TypeError(f"SegLossSum: region must be a RegionObjective, got {type(region).__name__}")
+        region_weight = float(region_weight)
+        if not (math.isfinite(region_weight) and region_weight > 0.0):
+            raise ValueError(f"SegLossSum: region_weight must be finite and > 0, got {region_weight}")
+        self.base, self.region, self.region_weight = base, region, region_weight
+
+    def extra_repr(self):
+        return f"region_weight={self.region_weight}"
+
+    def base_nhwc(self, logits_nhwc, labels):
+        if isinstance(self.base, nn.CrossEntropyLoss):
+            from . import autograd as ag
+            return ag.softmax_ce(logits_nhwc, labels.type(torch.long), self.base.ignore_index)
+        return self.base.forward_nhwc(logits_nhwc, labels)
+
+    def forward_nhwc(self, logits_nhwc, labels):
+        return self.base_nhwc(logits_nhwc, labels) + self.region_weight * self.region.forward_nhwc(logits_nhwc, labels)
+
+    def forward(self, logits, labels):
+        from . import autograd as ag
+        return self.forward_nhwc(ag.nhwc_rows_of(logits), labels)

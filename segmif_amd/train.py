@@ -14,6 +14,7 @@ feed train.py:369-374's dynamic weights are averaged too so every rank applies i
 runs the whole schedule of train.py:424-434 - seven rounds of a fusion phase then a segmentation phase - on batches that
 segmif_amd.data makes on the device (main() below; one process, one GPU).  --seg-loss picks the segmentation phase's objective
 (make_seg_loss): the reference's CE by default, or OHEM / focal / NormalLoss / class-weighted CE on csrc/seg_objective.hip.
+--seg-region adds a region term to it (make_seg_region): Lovasz-Softmax or soft Dice on csrc/region_objective.hip.
 """
 import argparse
 import math
@@ -279,6 +280,20 @@ def make_seg_loss(name, ignore_index=255, ohem_thresh=0.7, ohem_n_min=None, foca
     return losses.SegObjective(label_smoothing=label_smoothing, weight=class_weights, ignore_index=ignore_index)
 
 
+SEG_REGIONS = ("lovasz", "dice")
+
+
+def make_seg_region(criterion, kind, weight=1.0, classes="present", smooth=1.0, ignore_index=255):
+    """criterion + weight * the region objective `kind` ("lovasz" | "dice") as one losses.SegLossSum on the same logits, for
+    seg_train_step / GraphedSegTrainStep.  criterion: what make_seg_loss built.  The region term runs on csrc/region_objective.hip;
+    it is this project's addition, not the reference's objective.  smooth belongs to "dice"."""
+    if kind not in SEG_REGIONS:
+        raise ValueError(f"unknown region objective {kind!r}; one of {', '.join(SEG_REGIONS)}")
+    if kind != "dice" and smooth != 1.0:
+        raise ValueError(f"smooth belongs to the 'dice' region objective, not {kind!r}")
+    return losses.SegLossSum(criterion, losses.RegionObjective(kind, classes, ignore_index, smooth), weight)
+
+
 class _GuardLog:
     """What a log line adds when the optimizer is guarded: ONE grad_stats() readback per line (never per step) - the last step's
     gradient norm, the steps clipped and skipped since the previous line, the parameters that carried non-finite gradients - and
@@ -383,6 +398,13 @@ def main(argv=None):
     ap.add_argument("--label-smoothing", type=float, default=0.0, help="--seg-loss ce / weighted: label smoothing in [0, 1); above 0 it is "
                     "not the reference's objective")
     ap.add_argument("--seg-class-weights", type=float, nargs="+", metavar="W", help="--seg-loss weighted: one weight >= 0 per class (9)")
+    ap.add_argument("--seg-region", choices=SEG_REGIONS, help="add a region objective to whatever --seg-loss builds, for the "
+                    "SEGMENTATION phase only: lovasz is Lovasz-Softmax (the convex surrogate of the Jaccard index, the batch as one set), "
+                    "dice the soft Dice loss.  This project's addition, NOT the reference's objective: its train.py trains on CE alone")
+    ap.add_argument("--seg-region-weight", type=float, metavar="W", help="--seg-region: the region term's weight, > 0 (default 1.0)")
+    ap.add_argument("--seg-region-classes", choices=("present", "all"), help="--seg-region: average over the classes present in the "
+                    "batch (default) or over all of them")
+    ap.add_argument("--dice-smooth", type=float, metavar="S", help="--seg-region dice: the smoothing term, >= 0 (default 1.0)")
     ap.add_argument("--clip-grad-norm", type=float, metavar="X", help="clip the global gradient norm of every step of both phases to "
                     "X > 0 (torch.nn.utils.clip_grad_norm_'s rule, on the device); off by default.  This project's addition: the "
                     "reference's train.py does not clip")
@@ -407,6 +429,16 @@ def main(argv=None):
         ap.error(f"--ohem-thresh {args.ohem_thresh}: a probability in (0, 1]")
     if args.seg_loss == "focal" and not args.focal_gamma > 0:
         ap.error(f"--focal-gamma {args.focal_gamma}: must be > 0")
+    for flag, value in (("--seg-region-weight", args.seg_region_weight), ("--seg-region-classes", args.seg_region_classes),
+                        ("--dice-smooth", args.dice_smooth)):
+        if value is not None and args.seg_region is None:
+            ap.error(f"{flag} belongs to --seg-region, which is not given")
+    if args.dice_smooth is not None and args.seg_region != "dice":
+        ap.error(f"--dice-smooth belongs to --seg-region dice, not {args.seg_region}")
+    if args.seg_region_weight is not None and not (args.seg_region_weight > 0 and math.isfinite(args.seg_region_weight)):
+        ap.error(f"--seg-region-weight {args.seg_region_weight}: must be a finite number > 0")
+    if args.dice_smooth is not None and not (args.dice_smooth >= 0 and math.isfinite(args.dice_smooth)):
+        ap.error(f"--dice-smooth {args.dice_smooth}: must be a finite number >= 0")
     if args.clip_grad_norm is not None and not (args.clip_grad_norm > 0 and math.isfinite(args.clip_grad_norm)):
         ap.error(f"--clip-grad-norm {args.clip_grad_norm}: must be a finite number > 0")
     if args.max_consecutive_skips < 1:
@@ -454,6 +486,14 @@ def main(argv=None):
     if args.seg_loss != "ce" or args.label_smoothing:
         print(f"[train] --seg-loss {args.seg_loss}" + (f" --label-smoothing {args.label_smoothing}" if args.label_smoothing else "")
               + ": NOT the reference's segmentation objective (segmentation phase only; the fusion phase's segmentation term keeps CE)")
+    if args.seg_region is not None:
+        weight = 1.0 if args.seg_region_weight is None else args.seg_region_weight
+        seg_crit = make_seg_region(seg_crit, args.seg_region, weight, args.seg_region_classes or "present",
+                                   1.0 if args.dice_smooth is None else args.dice_smooth).cuda()
+        print(f"[train] --seg-region {args.seg_region} (weight {weight}, classes {args.seg_region_classes or 'present'}"
+              + (f", smooth {seg_crit.region.smooth}" if args.seg_region == "dice" else "") + "): a region term added to the "
+              "segmentation objective, NOT the reference's objective (segmentation phase only; the fusion phase's segmentation term "
+              "keeps CE)")
     sched = dict(weight_decay=args.weight_decay, betas=args.betas, max_iter=args.max_iters, warmup_ratio=args.warmup_ratio, power=args.power)
     guarded = args.clip_grad_norm is not None or args.skip_nonfinite
     if guarded:
