@@ -982,6 +982,25 @@ int segmif_adamw_guarded_f32(const void* table, const int32_t* chunk_entry, cons
 int segmif_grad_scale_f32(const void* table, const int32_t* chunk_entry, const int64_t* chunk_off, int nchunks, int chunk_elems,
                           const SegmifGradGuardRecord* record, void* stream);
 
+/* Exponential moving average of the parameters (csrc/weight_ema.hip), one launch AFTER segmif_adamw_f32 / segmif_adamw_guarded_f32 over
+ * the same table and chunk arrays (a sub-range of the chunks is allowed, as for the guarded update); of an entry only p and n are
+ * read, and p is the value the update before it left.  Neither the reference nor its optimizer has any of this.
+ *   ema        device array of 2 * nentries pointers indexed by the table's entry: ema[2 i] = hi, ema[2 i + 1] = lo, n floats each.
+ *              The average is the pair hi + lo; hi is its float32 rounding (what a model loads), lo the remainder.
+ *   record     NULL, or the guard's record of this step: with record->skip_now set no block touches hi or lo.
+ *   entry_slot / param_count (both or neither): t = step - param_count[entry_slot[entry]].skipped, the parameter's applied steps
+ *              with this one included, floored at 1 - the count the guarded bias correction uses.  Without them t = step.
+ * Per block, in double: d_t = warmup ? min(decay, (1 + t) / (10 + t)) : decay, a = 1 - d_t.  Per element, in double:
+ *   e = hi + lo;  e += a * (p - e);  hi = (float)e;  lo = (float)(e - hi)
+ * A float32 average updated as ema += a * (p - ema) loses increments under half an ulp - at decay 0.9999 and learning rates around
+ * 1e-4 that is most of them - and stalls; the pair keeps 48 bits.  Non-finite values are not special-cased: a p that is inf or NaN
+ * makes its average NaN from then on.  Element-wise only, no atomics, no reductions: bitwise reproducible.  16-byte accesses where
+ * p, hi and lo of the chunk are 16-byte aligned.  decay inside (0, 1), chunk_elems a multiple of 4, step >= 1. */
+int segmif_weight_ema_f32(const void* table, float* const* ema, const int32_t* chunk_entry, const int64_t* chunk_off,
+                          int nchunks, int chunk_elems, double decay, int warmup, int step,
+                          const SegmifGradGuardRecord* record, const int32_t* entry_slot,
+                          const SegmifGradParamCount* param_count, void* stream);
+
 /*
  * Mix-FFN of a MiT block as ONE kernel (csrc/mixffn.hip), C = 64 | 128 (stages 1-2 of mit_b1 .. b5):
  *     out = x + fc2(GELU(dwconv3x3(fc1(LayerNorm(x)))))     core/mix_transformer.py:46-53, :376-387, :152-155

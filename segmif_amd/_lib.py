@@ -301,6 +301,8 @@ SIGNATURES = {
     "segmif_adamw_guarded_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_float, c_int, c_void_p,
                                        c_void_p, c_void_p, c_void_p]),
     "segmif_grad_scale_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "segmif_weight_ema_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_int, c_int, c_void_p, c_void_p,
+                                    c_void_p, c_void_p]),
     "segmif_seg_normalize_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "segmif_nchw_to_nhwc_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p]),
     "segmif_nhwc_to_nchw_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p]),

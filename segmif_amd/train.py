@@ -15,8 +15,11 @@ runs the whole schedule of train.py:424-434 - seven rounds of a fusion phase the
 segmif_amd.data makes on the device (main() below; one process, one GPU).  --seg-loss picks the segmentation phase's objective
 (make_seg_loss): the reference's CE by default, or OHEM / focal / NormalLoss / class-weighted CE on csrc/seg_objective.hip.
 --seg-region adds a region term to it (make_seg_region): Lovasz-Softmax or soft Dice on csrc/region_objective.hip.
+--ema-decay keeps an exponential moving average of the weights in the optimizer step (csrc/weight_ema.hip) and validates and
+writes the AVERAGED weights.
 """
 import argparse
+import contextlib
 import math
 import os
 import sys
@@ -197,26 +200,29 @@ SEG_CKPT, FUSION_CKPT = "model-fusion_add_final2.pth", "modelfusion-final2.pth" 
 
 
 def make_seg_optimizer(seg_net, iter_curr=0, lr=8e-5, weight_decay=0.01, betas=(0.9, 0.999), warmup_iter=3000, max_iter=160000,
-                       warmup_ratio=1e-6, power=1.0, max_grad_norm=None, skip_nonfinite=False):
+                       warmup_ratio=1e-6, power=1.0, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False):
     """train.py:173-200: [encoder non-norm | encoder norm, no decay | decoder + classifier at 10 x lr].  max_grad_norm /
-    skip_nonfinite: the optimizer's guard (utils/optimizer.FusedAdamW), off by default; not the reference's."""
+    skip_nonfinite: the optimizer's guard (utils/optimizer.FusedAdamW); ema_decay / ema_warmup: its average of the weights.  All
+    off by default; none is the reference's."""
     from .utils.optimizer import PolyWarmupAdamW_seg
     g = seg_net.denoise_net.get_param_groups()
     return PolyWarmupAdamW_seg(
         params=[{"params": g[0], "lr": lr, "weight_decay": weight_decay}, {"params": g[1], "lr": lr, "weight_decay": 0.0},
                 {"params": g[2], "lr": lr * 10, "weight_decay": weight_decay}],
         lr=lr, weight_decay=weight_decay, betas=list(betas), iter_curr=iter_curr, warmup_iter=warmup_iter, max_iter=max_iter,
-        warmup_ratio=warmup_ratio, power=power, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+        warmup_ratio=warmup_ratio, power=power, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay,
+        ema_warmup=ema_warmup)
 
 
 def make_fusion_optimizer(fusion_net, iter_, lr=8e-5, weight_decay=0.01, betas=(0.9, 0.999), max_iter=160000, warmup_ratio=1e-6,
-                          power=1.0, max_grad_norm=None, skip_nonfinite=False):
+                          power=1.0, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False):
     """train.py:316-332: one group at lr / iter_; the default 3e-4 / iter_ and warmup_iter = 3e-5 / iter_ are constants of the
     reference's code (the warm-up branch is never taken)"""
     from .utils.optimizer import PolyWarmupAdamW
     return PolyWarmupAdamW(params=[{"params": list(fusion_net.parameters()), "lr": lr / iter_, "weight_decay": weight_decay}],
                            lr=3e-4 / iter_, weight_decay=weight_decay, betas=list(betas), warmup_iter=3e-5 / iter_, max_iter=max_iter,
-                           warmup_ratio=warmup_ratio, power=power, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+                           warmup_ratio=warmup_ratio, power=power, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
+                           ema_decay=ema_decay, ema_warmup=ema_warmup)
 
 
 def fusion_loss_names():
@@ -412,6 +418,12 @@ def main(argv=None):
                     "the device, no host synchronisation); off by default.  This project's addition")
     ap.add_argument("--max-consecutive-skips", type=int, default=50, metavar="N", help="with --skip-nonfinite: stop when more than N "
                     "steps in a row were skipped (checked at log lines)")
+    ap.add_argument("--ema-decay", type=float, metavar="D", help="keep an exponential moving average of the weights, decay D inside "
+                    "(0, 1), updated on the device in every applied optimizer step; validation, checkpoint selection and the written "
+                    "checkpoints then use the AVERAGED weights.  Off by default.  This project's addition: the reference's train.py "
+                    "averages nothing")
+    ap.add_argument("--ema-warmup", action="store_true", help="with --ema-decay: the decay of update t is min(D, (1 + t) / (10 + t))")
+    ap.add_argument("--ema-nets", choices=("seg", "fusion", "both"), help="with --ema-decay: the nets that are averaged (default seg)")
     ap.add_argument("--log-iters", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args(argv)
@@ -443,6 +455,10 @@ def main(argv=None):
         ap.error(f"--clip-grad-norm {args.clip_grad_norm}: must be a finite number > 0")
     if args.max_consecutive_skips < 1:
         ap.error(f"--max-consecutive-skips {args.max_consecutive_skips}: must be >= 1")
+    if args.ema_decay is None and (args.ema_warmup or args.ema_nets is not None):
+        ap.error("--ema-warmup / --ema-nets belong to --ema-decay, which is not given")
+    if args.ema_decay is not None and not 0.0 < args.ema_decay < 1.0:
+        ap.error(f"--ema-decay {args.ema_decay}: must lie inside (0, 1)")
     seg_pixels = max(1, args.samples_per_gpu // 2) * args.crop_size ** 2
     if args.ohem_n_min is None:
         args.ohem_n_min = max(1, seg_pixels // 16)
@@ -501,8 +517,23 @@ def main(argv=None):
         print("[train] " + " ".join(([f"--clip-grad-norm {args.clip_grad_norm}"] if args.clip_grad_norm is not None else [])
                                     + (["--skip-nonfinite"] if args.skip_nonfinite else []))
               + ": this project's additions, NOT the reference's training (its train.py neither clips gradients nor skips a step)")
+    ema_seg = args.ema_decay is not None and (args.ema_nets or "seg") in ("seg", "both")
+    ema_fus = args.ema_decay is not None and args.ema_nets in ("fusion", "both")
+    ema_kw = dict(ema_decay=args.ema_decay, ema_warmup=args.ema_warmup)
+    if args.ema_decay is not None:
+        from .utils.optimizer import ema_weights
+        print(f"[train] --ema-decay {args.ema_decay}" + (" --ema-warmup" if args.ema_warmup else "") + f" --ema-nets {args.ema_nets or 'seg'}"
+              ": this project's addition, NOT the reference's training (its train.py averages nothing).  "
+              + ("Every validation runs on the AVERAGED segmentation weights and the segmentation checkpoint holds them; each phase "
+                 "starts from the best checkpoint so far, so it starts from averaged weights.  " if ema_seg else "")
+              + ("The fusion checkpoint and the fused training frames come from the AVERAGED fusion weights; its training continues "
+                 "from the raw ones." if ema_fus else ""))
+
+    def averaged(on, optimizer, net):
+        return ema_weights(optimizer, net) if on else contextlib.nullcontext()
+
     loader_kw = dict(batch=batch, crop_size=args.crop_size, rescale_range=tuple(args.rescale_range), fliplr=True)
-    best, wrote_seg = None, False
+    best, wrote_seg, opt = None, False, None
     fusion_loss = make_fusion_loss(args.fusion_loss) if args.fusion_loss is not None else None
     if fusion_loss is not None:
         print(f"[train] --fusion-loss {args.fusion_loss}: NOT the reference's schedule of objectives")
@@ -515,8 +546,8 @@ def main(argv=None):
             seg.load_state_dict(seg_initial)
         elif wrote_seg:
             seg.load_state_dict(torch.load(seg_path, map_location="cuda"))
-        trainer = FusionTrainer(seg, fus, make_fusion_optimizer(fus, iter_, lr=args.lr, **sched), crit, iter_=iter_,
-                                fusion_loss=fusion_loss)
+        trainer = FusionTrainer(seg, fus, make_fusion_optimizer(fus, iter_, lr=args.lr, **sched, **(ema_kw if ema_fus else {})), crit,
+                                iter_=iter_, fusion_loss=fusion_loss)
         glog = _GuardLog(trainer.opt, [("fusion_net", fus)], args.max_consecutive_skips) if guarded else None
         batches = AugmentedBatches(train_set, seed=args.seed + 2 * iter_, **loader_kw)
         n_fus = args.fusion_iters if args.fusion_iters is not None else (6000 if iter_ == 1 else 4000)
@@ -528,16 +559,21 @@ def main(argv=None):
                 if guarded:
                     glog.check()
             if (n + 1) % 500 == 0:
-                torch.save(fus.state_dict(), fus_path)
-        torch.save(fus.state_dict(), fus_path)
-        fused_set = DeviceDataset(train_set.names, train_set.ir, _fused_frames(seg, fus, train_set, batch), train_set.mask, train_set.label)
+                with averaged(ema_fus, trainer.opt, fus):
+                    torch.save(fus.state_dict(), fus_path)
+        with averaged(ema_fus, trainer.opt, fus):
+            torch.save(fus.state_dict(), fus_path)
+            fused = _fused_frames(seg, fus, train_set, batch)
+        fused_set = DeviceDataset(train_set.names, train_set.ir, fused, train_set.mask, train_set.label)
         # ---- segmentation phase (train.py:115-245) on the fused training frames, from the best checkpoint so far (:159-160)
         print(f"[train] round {iter_}: segmentation")
         seg.load_state_dict(torch.load(seg_path, map_location="cuda") if (wrote_seg and iter_ > 1) else seg_state)
+        opt = make_seg_optimizer(seg, iter_curr=(iter_ - 1) * 10000, lr=args.lr, warmup_iter=args.warmup_iter, **sched,
+                                 **(ema_kw if ema_seg else {}))
         if best is None:
-            best = _miou(seg, fus, val_set, batch)
+            with averaged(ema_seg, opt, seg):  # (no step yet: no average yet, the weights as they are)
+                best = _miou(seg, fus, val_set, batch)
             print(f"[train] initial mIoU {best:.4f}")
-        opt = make_seg_optimizer(seg, iter_curr=(iter_ - 1) * 10000, lr=args.lr, warmup_iter=args.warmup_iter, **sched)
         glog = _GuardLog(opt, [("seg_net", seg)], args.max_consecutive_skips) if guarded else None
         batches = AugmentedBatches(fused_set, seed=args.seed + 2 * iter_ + 1, photometric=(), **loader_kw)
         n_seg = args.seg_iters if args.seg_iters is not None else 10000
@@ -550,15 +586,17 @@ def main(argv=None):
                 if guarded:
                     glog.check()
             if (n + 1) % 1000 == 0 or n + 1 == n_seg:
-                miou = _miou(seg, fus, val_set, batch)
-                if miou > best:  # (train.py:237: only an improvement is written)
-                    torch.save(seg.state_dict(), seg_path)
-                    best, wrote_seg = miou, True
+                with averaged(ema_seg, opt, seg):
+                    miou = _miou(seg, fus, val_set, batch)
+                    if miou > best:  # (train.py:237: only an improvement is written)
+                        torch.save(seg.state_dict(), seg_path)
+                        best, wrote_seg = miou, True
                 print(f"[train] round {iter_} segmentation iter {n + 1}: mIoU {miou:.4f} (best {best:.4f})")
     if not wrote_seg:
         # no validation ever beat the initial mIoU: the reference would leave no segmentation checkpoint; the last state is written
         # here, after the last round, so that a run leaves both files and no round has loaded a state that was not an improvement
-        torch.save(seg.state_dict(), seg_path)
+        with averaged(ema_seg and opt is not None, opt, seg):  # the last AVERAGED state
+            torch.save(seg.state_dict(), seg_path)
         print(f"[train] no segmentation state improved on the initial mIoU {best:.4f}: {seg_path} holds the LAST state, not a best one")
     print(f"[train] wrote {seg_path} and {fus_path}")
     return 0

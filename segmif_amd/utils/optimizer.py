@@ -7,6 +7,7 @@ torch.optim.AdamW(eps=1e-8) — decoupled weight decay, bias correction, paramet
 None are skipped.  One kernel launch updates every tensor (586 of them in the
 segmentation step) instead of one aten foreach chain per group.
 """
+import contextlib
 import ctypes
 
 import numpy as np
@@ -38,9 +39,16 @@ class _AdamEntry(ctypes.Structure):
                 ("n", ctypes.c_int64), ("lr", ctypes.c_float), ("wd", ctypes.c_float)]
 
 
-def _upload_table(items, slots, dev):
+def _ema_pointers(pairs):
+    """the (hi, lo) pointer array of segmif_weight_ema_f32, in table order, as bytes"""
+    return np.asarray([t.data_ptr() for pair in pairs for t in pair], dtype=np.uint64).tobytes()
+
+
+def _upload_table(items, slots, dev, ema=None):
     """One host buffer, one copy: [AdamEntry table | chunk_off int64 | chunk_entry int32 | entry_slot int32] for `items` =
-    (p, g, m, v, lr, wd) tuples in table order.  Returns the device bytes, the byte offsets of the three arrays and the counts."""
+    (p, g, m, v, lr, wd) tuples in table order.  Returns the device bytes, the byte offsets of the three arrays and the counts.
+    ema: one (hi, lo) pair per item; their 2 * len(items) pointers then sit between the table and chunk_off, at byte
+    len(items) * sizeof(AdamEntry), and everything after them moves down."""
     entries = (_AdamEntry * len(items))()
     chunk_entry, chunk_off = [], []
     for i, (p, g, m, v, lr, wd) in enumerate(items):
@@ -53,8 +61,9 @@ def _upload_table(items, slots, dev):
     co = np.asarray(chunk_off, dtype=np.int64).tobytes()
     ce = np.asarray(chunk_entry, dtype=np.int32).tobytes()
     sl = np.asarray(slots if slots is not None else [], dtype=np.int32).tobytes()
-    host = bytearray(bytes(entries) + co + ce + sl)
-    o_co = ctypes.sizeof(entries)
+    pt = _ema_pointers(ema) if ema is not None else b""
+    host = bytearray(bytes(entries) + pt + co + ce + sl)
+    o_co = ctypes.sizeof(entries) + len(pt)
     o_ce = o_co + len(co)
     o_sl = o_ce + len(ce)
     blob = torch.frombuffer(host, dtype=torch.uint8).to(dev)
@@ -70,6 +79,23 @@ def _grown(buf, nbytes, dev):
 _ENTRY_STAT = np.dtype([("sumsq", "<f8"), ("nonfinite", "<u4"), ("reserved", "<u4")])
 _PARAM_COUNT = np.dtype([("skipped", "<u4"), ("offended", "<u4")])
 _COUNTERS = ("attempts", "applied", "skipped", "clipped", "consecutive_skips")
+
+
+def ema_decay_at(decay, warmup, t):
+    """The decay of the average's update number t (t = 1 is the first): `decay`, or with warm-up min(decay, (1 + t) / (10 + t)) -
+    the host restatement, in Python floats, of what csrc/weight_ema.hip forms per block in double."""
+    decay, t = float(decay), max(int(t), 1)
+    return min(decay, (1.0 + t) / (10.0 + t)) if warmup else decay
+
+
+def _check_ema_args(decay, warmup, who):
+    if decay is None:
+        if warmup:
+            raise ValueError(f"{who}: ema_warmup without ema_decay")
+        return None
+    if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 < float(decay) < 1.0:
+        raise ValueError(f"{who}: ema_decay {decay!r} must be a float inside (0, 1) (or None)")
+    return float(decay)
 
 
 def _check_guard_abi(lib):
@@ -96,11 +122,22 @@ class FusedAdamW(torch.optim.Optimizer):
     applied: the training loops run a fixed number of iterations and the schedule stays aligned with them.
     Data parallel runs: seg_train_step and FusionTrainer.step reduce the gradients before they call step(), so every rank
     sees the same gradients, forms the same norm and takes the same decision; the guard adds no collective.
-    grad_stats() reads the device record back (one copy, one synchronisation): call it at log lines, not per step."""
+    grad_stats() reads the device record back (one copy, one synchronisation): call it at log lines, not per step.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, skip_nonfinite=False):
+    ema_decay (a float inside (0, 1)) adds an exponential moving average of every parameter, also this project's and also off by
+    default: state["ema"] (hi, a float32 clone of the parameter made at its first step, before the update) and state["ema_lo"],
+    a PAIR of floats whose sum is the average.  After each hyper-parameter group's update one more launch (csrc/weight_ema.hip)
+    forms, in double, ema += (1 - d_t) * (p - ema) with d_t = ema_decay, or with ema_warmup min(ema_decay, (1 + t) / (10 + t)),
+    t the parameter's count of APPLIED steps - the bias correction's count.  A skipped step moves no average and does not advance
+    t; a parameter without a gradient is not in the table and its average stays where it is.  No host synchronisation and no
+    copy beyond the table upload, which carries the pointers.  ema_tensors() / ema_weights() / ema_state_dict() read it."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, skip_nonfinite=False,
+                 ema_decay=None, ema_warmup=False):
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
             raise ValueError(f"max_grad_norm {max_grad_norm}: must be > 0 (or None)")
+        self.ema_decay = _check_ema_args(ema_decay, ema_warmup, "FusedAdamW")
+        self.ema_warmup = bool(ema_warmup)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._layout = None  # (signature, chunk_entry, chunk_off) cached while the grad set is unchanged
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
@@ -137,6 +174,8 @@ class FusedAdamW(torch.optim.Optimizer):
                     st["step"] = 0
                     st["exp_avg"] = torch.zeros_like(p)
                     st["exp_avg_sq"] = torch.zeros_like(p)
+                if self.ema_decay is not None and "ema" not in st:
+                    self._ema_begin(st, p)
                 st["step"] = int(st["step"]) + 1  # a torch.optim.AdamW checkpoint stores `step` as a tensor
                 key = (st["step"], group["betas"], group["eps"], p.device)
                 by_hyper.setdefault(key, []).append((p, p.grad.contiguous(), st, group["lr"], group["weight_decay"]))
@@ -152,7 +191,9 @@ class FusedAdamW(torch.optim.Optimizer):
                 for off in range(0, p.numel(), _CHUNK):
                     chunk_entry.append(i)
                     chunk_off.append(off)
-            table = torch.frombuffer(bytearray(bytes(entries)), dtype=torch.uint8).to(dev)
+            ema = self.ema_decay is not None  # (the average's pointers ride behind the table, in the same copy)
+            pointers = _ema_pointers((st["ema"], st["ema_lo"]) for _, _, st, _, _ in items) if ema else b""
+            table = torch.frombuffer(bytearray(bytes(entries) + pointers), dtype=torch.uint8).to(dev)
             ce = torch.tensor(chunk_entry, dtype=torch.int32, device=dev)
             co = torch.tensor(chunk_off, dtype=torch.int64, device=dev)
             stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -161,9 +202,28 @@ class FusedAdamW(torch.optim.Optimizer):
             bc2_sqrt = (1.0 - float(betas[1]) ** step) ** 0.5
             _lib.check(lib.segmif_adamw_f32(table.data_ptr(), ce.data_ptr(), co.data_ptr(), len(chunk_entry), _CHUNK,
                                             betas[0], betas[1], eps, bc1, bc2_sqrt, stream), "segmif_adamw_f32")
+            if ema:
+                _lib.check(lib.segmif_weight_ema_f32(table.data_ptr(), table.data_ptr() + ctypes.sizeof(entries), ce.data_ptr(),
+                                                     co.data_ptr(), len(chunk_entry), _CHUNK, self.ema_decay, int(self.ema_warmup), step,
+                                                     None, None, None, stream), "segmif_weight_ema_f32")
             self._keepalive = (table, ce, co, keep)
             _bump_versions([p for p, *_ in items])
         return loss
+
+    # --------------------------------------------------------------------------------------------------- average
+    @staticmethod
+    def _ema_begin(st, p):
+        """the pair starts at the parameter's value BEFORE its first averaged update (also for a state loaded without one)"""
+        st["ema"] = p.detach().clone()
+        st["ema_lo"] = torch.zeros_like(p)
+
+    def ema_tensors(self):
+        """{parameter: (hi, lo)} for the parameters that have an average (those that have had a gradient).  hi + lo is the
+        average, hi its float32 rounding; both are the optimizer's own state tensors."""
+        if self.ema_decay is None:
+            raise RuntimeError("ema_tensors(): this optimizer keeps no average (ema_decay)")
+        return {p: (self.state[p]["ema"], self.state[p]["ema_lo"]) for g in self.param_groups for p in g["params"]
+                if "ema" in self.state.get(p, ())}
 
     # ---------------------------------------------------------------------------------------------- guarded path
     def _guard_layout(self, n_slots=None):
@@ -209,15 +269,19 @@ class FusedAdamW(torch.optim.Optimizer):
                     st["step"] = 0
                     st["exp_avg"] = torch.zeros_like(p)
                     st["exp_avg_sq"] = torch.zeros_like(p)
+                if self.ema_decay is not None and "ema" not in st:
+                    self._ema_begin(st, p)
                 st["step"] = int(st["step"]) + 1  # attempts; the device subtracts the parameter's skipped ones
                 key = (st["step"], tuple(group["betas"]), group["eps"])
                 by_hyper.setdefault(key, []).append((p, p.grad.contiguous(), st["exp_avg"], st["exp_avg_sq"], group["lr"],
                                                      group["weight_decay"]))
+        ema = [(self.state[it[0]]["ema"], self.state[it[0]]["ema_lo"]) for its in by_hyper.values() for it in its] \
+            if self.ema_decay is not None else None
         items = [it for group_items in by_hyper.values() for it in group_items]  # table order: hyper-parameter groups in a row
         if not any(it[0].numel() for it in items):
             return
         buf, o_counts, o_entries = self._guard_buffer(dev)
-        blob, (o_co, o_ce, o_sl), nchunks = _upload_table(items, [self._g_slots[id(it[0])] for it in items], dev)
+        blob, (o_co, o_ce, o_sl), nchunks = _upload_table(items, [self._g_slots[id(it[0])] for it in items], dev, ema)
         self._g_work = _grown(self._g_work, lib.segmif_grad_norm_workspace_bytes(nchunks), dev)
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         base, rec = blob.data_ptr(), buf.data_ptr()
@@ -232,6 +296,10 @@ class FusedAdamW(torch.optim.Optimizer):
                 _lib.check(lib.segmif_adamw_guarded_f32(base, base + o_ce + 4 * c0, base + o_co + 8 * c0, nc, _CHUNK, float(betas[0]),
                                                         float(betas[1]), eps, step, rec, base + o_sl, rec + o_counts, stream),
                            "segmif_adamw_guarded_f32")
+                if ema is not None:
+                    _lib.check(lib.segmif_weight_ema_f32(base, base + len(items) * ctypes.sizeof(_AdamEntry), base + o_ce + 4 * c0,
+                                                         base + o_co + 8 * c0, nc, _CHUNK, self.ema_decay, int(self.ema_warmup), step,
+                                                         rec, base + o_sl, rec + o_counts, stream), "segmif_weight_ema_f32")
             c0 += nc
         self._keepalive = (blob, [it[1] for it in items])
         self._g_last = [it[0] for it in items]
@@ -325,6 +393,92 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
     return torch.where(nonfinite != 0, torch.full_like(norm, float("nan")), norm)
 
 
+class WeightEMA:
+    """The average of FusedAdamW(ema_decay=...) on its own, for loops that keep a torch optimizer (as clip_grad_norm_ is the
+    stand-alone form of the guard): hi (a clone) and lo are made here, update() - call it after optimizer.step() - is one launch
+    of csrc/weight_ema.hip over all parameters with this object's own count of updates as t.  No CPU fallback: update() on
+    anything but contiguous fp32 tensors of one GPU raises."""
+
+    def __init__(self, params, decay, warmup=False):
+        if decay is None:
+            raise ValueError("WeightEMA: decay must be a float inside (0, 1)")
+        self.decay = _check_ema_args(decay, warmup, "WeightEMA")
+        self.warmup = bool(warmup)
+        self.params = [params] if isinstance(params, torch.Tensor) else list(params)
+        self.hi = [p.detach().clone() for p in self.params]
+        self.lo = [torch.zeros_like(p) for p in self.params]
+        self.step = 0
+        self._table = None  # (signature, device bytes, offsets, chunks): the pointers change only when a tensor is rebound
+
+    def ema_tensors(self):
+        return {p: (h, l) for p, h, l in zip(self.params, self.hi, self.lo)}
+
+    @torch.no_grad()
+    def update(self):
+        if not self.params:
+            return
+        dev = self.params[0].device
+        for t in self.params + self.hi + self.lo:
+            if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+                raise RuntimeError("WeightEMA.update: parameters must be contiguous fp32 tensors on one GPU (there is no CPU path)")
+        lib = _lib.load()
+        assert lib.segmif_adamw_entry_bytes() == ctypes.sizeof(_AdamEntry)
+        sig = tuple(t.data_ptr() for t in self.params + self.hi + self.lo)
+        if self._table is None or self._table[0] != sig:
+            blob, offs, nchunks = _upload_table([(p, p, None, None, 0.0, 0.0) for p in self.params], None, dev,
+                                                list(zip(self.hi, self.lo)))
+            self._table = (sig, blob, offs, nchunks)
+        _, blob, (o_co, o_ce, _), nchunks = self._table
+        self.step += 1
+        if nchunks:
+            base = blob.data_ptr()
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _lib.check(lib.segmif_weight_ema_f32(base, base + len(self.params) * ctypes.sizeof(_AdamEntry), base + o_ce, base + o_co,
+                                                 nchunks, _CHUNK, self.decay, int(self.warmup), self.step, None, None, None, stream),
+                       "segmif_weight_ema_f32")
+
+    def state_dict(self):
+        return {"step": self.step, "decay": self.decay, "warmup": self.warmup, "ema": [t.clone() for t in self.hi],
+                "ema_lo": [t.clone() for t in self.lo]}
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict):
+        hi, lo = state_dict["ema"], state_dict["ema_lo"]
+        if len(hi) != len(self.hi) or len(lo) != len(self.lo) or any(a.shape != b.shape for a, b in zip(hi + lo, self.hi + self.lo)):
+            raise ValueError("WeightEMA.load_state_dict: the stored averages do not match the parameters")
+        for dst, src in zip(self.hi + self.lo, hi + lo):
+            dst.copy_(src)  # in place: the uploaded table keeps pointing at them
+        self.step = int(state_dict["step"])
+
+
+@contextlib.contextmanager
+def ema_weights(source, module):
+    """`with ema_weights(source, module):` runs its body on the AVERAGED weights.  source: a FusedAdamW with ema_decay or a
+    WeightEMA.  On entry every parameter of `module` that has an average is overwritten in place with hi (copy_ under no_grad,
+    never a rebind of .data: graph captures and the gradient reducer's buckets hold the pointers), the raw values stashed first;
+    on exit - after an exception too - they are copied back bit for bit.  Buffers (BatchNorm's running statistics) and
+    parameters without an average are left alone.  Both copies raise the parameters' _version, so core/_util.PackedCache
+    repacks.  torch operators only: works on CPU tensors as well."""
+    avg = source.ema_tensors()
+    swapped = [(p, p.detach().clone(), avg[p][0]) for p in module.parameters() if p in avg]
+    with torch.no_grad():
+        for p, _, hi in swapped:
+            p.copy_(hi)
+    try:
+        yield module
+    finally:
+        with torch.no_grad():
+            for p, raw, _ in swapped:
+                p.copy_(raw)
+
+
+def ema_state_dict(source, module):
+    """module.state_dict() with hi in place of every averaged parameter: the same keys, every tensor cloned, the module untouched."""
+    avg = source.ema_tensors()
+    hi = {n: avg[p][0] for n, p in module.named_parameters(remove_duplicate=False) if p in avg}
+    return {k: (hi[k] if k in hi else v).detach().clone() for k, v in module.state_dict().items()}
+
+
 class _PolyWarmupMixin:
     def _init_schedule(self, global_step, warmup_iter, max_iter, warmup_ratio, power):
         self.global_step = global_step
@@ -344,9 +498,9 @@ class _PolyWarmupMixin:
 
 class PolyWarmupAdamW(_PolyWarmupMixin, FusedAdamW):
     def __init__(self, params, lr, weight_decay, betas, warmup_iter=None, max_iter=None, warmup_ratio=None, power=None,
-                 max_grad_norm=None, skip_nonfinite=False):
+                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False):
         FusedAdamW.__init__(self, params, lr=lr, betas=tuple(betas), weight_decay=weight_decay, eps=1e-8, max_grad_norm=max_grad_norm,
-                            skip_nonfinite=skip_nonfinite)
+                            skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, ema_warmup=ema_warmup)
         self._init_schedule(0, warmup_iter, max_iter, warmup_ratio, power)
 
     def step(self, closure=None):
@@ -358,9 +512,9 @@ class PolyWarmupAdamW(_PolyWarmupMixin, FusedAdamW):
 
 class PolyWarmupAdamW_seg(_PolyWarmupMixin, FusedAdamW):
     def __init__(self, params, lr, weight_decay, betas, iter_curr, warmup_iter=None, max_iter=None, warmup_ratio=None,
-                 power=None, max_grad_norm=None, skip_nonfinite=False):
+                 power=None, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False):
         FusedAdamW.__init__(self, params, lr=lr, betas=tuple(betas), weight_decay=weight_decay, eps=1e-8, max_grad_norm=max_grad_norm,
-                            skip_nonfinite=skip_nonfinite)
+                            skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, ema_warmup=ema_warmup)
         self._init_schedule(iter_curr, warmup_iter, max_iter, warmup_ratio, power)
 
     def step(self, closure=None):
