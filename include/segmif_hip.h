@@ -670,7 +670,7 @@ typedef struct {
   int32_t ticket, accept_mask;     /* pick's scratch: zero on entry, zero again on exit */
   int32_t accepted;                /* written by pick: bit c set = candidate c passed the class-balance test */
   int32_t tab_x, tab_y, near_x, near_y, taps_x, taps_y;
-  int32_t reserved[2];
+  int32_t reserved[2];             /* zero.  segmif_augment_pick_class_u8 uses the pair as one 64-bit scratch word: zero on entry and on exit */
 } SegmifAugmentRec;
 int segmif_augment_record_bytes(void);
 /* imutils.py:223-238 for every sample: counts the classes of each candidate window of the virtual label (nearest-resized,
@@ -678,12 +678,33 @@ int segmif_augment_record_bytes(void);
  * in float64 for counts below 2^18; `len(cnt > 1)` there is len(cnt)), else the tenth.  Writes box_h, box_w, chosen, accepted. */
 int segmif_augment_pick_u8(const uint8_t* label, int N, int h, int w, SegmifAugmentRec* rec, const int32_t* tab, int64_t tab_words,
                            int B, int crop_h, int crop_w, void* stream);
+/* The same pick with a second acceptance rule, for rare-class sampling (Hoyer et al. 2022, DAFormer; NOT the reference's
+ * loader).  want (B, 2) int32 on the device: per sample a class c and a threshold t.
+ *   c < 0:         segmif_augment_pick_u8's rule and exactly its record words; got[b] = -1.
+ *   0 <= c <= 254: with n_k the pixels equal to c in candidate k's window of the virtual label, candidate k is accepted iff
+ *                  n_k > t (strict; the 0.75 test is not applied).  chosen = the first accepted candidate, else the one with
+ *                  the largest n_k, the lowest index on ties (candidate 0 when the class is in no window); accepted = the mask
+ *                  of accepted candidates; got[b] = n_chosen.  With tally (n_class_tally, 2) int64 given and c < n_class_tally:
+ *                  tally[c][0] += 1 (drawn), tally[c][1] += 1 if a candidate was accepted (hit).  The call does not zero tally.
+ * c > 254 or t < 0 is the caller's to refuse (the values live on the device); such a sample is treated as c < 0.  rec and tally
+ * must be 8-byte aligned.  A record that fails the geometry checks is left alone, its got[b] too. */
+int segmif_augment_pick_class_u8(const uint8_t* label, int N, int h, int w, SegmifAugmentRec* rec, const int32_t* tab, int64_t tab_words,
+                                 int B, int crop_h, int crop_w, const int32_t* want, int32_t* got, int64_t* tally, int n_class_tally,
+                                 void* stream);
 /* The batch itself: ir3, vis3, mask3 (B, 3, crop_h, crop_w) fp32 = value / 255 (IEEE division) and label_out (B, crop_h, crop_w)
  * int64, from box_h / box_w of the records.  Outside the image: float32(123.675 | 116.28 | 103.53) / 255 per channel in all
  * three images (random_crop2 pads the grey ones the same way) and label 255.  crop_w % 4 == 0, outputs 16-byte aligned. */
 int segmif_augment_apply_u8(const uint8_t* ir, const uint8_t* vis, const uint8_t* mask, const uint8_t* label, int N, int h, int w,
                             const SegmifAugmentRec* rec, const int32_t* tab, int64_t tab_words, int B, int crop_h, int crop_w,
                             float* ir3, float* vis3, float* mask3, int64_t* label_out, void* stream);
+
+/* Class statistics of label maps: counts (N, 257) int64, counts[n][v] = pixels of frame n equal to v for v in 0..255, column
+ * 256 = values outside 0..255 (always 0 for the uint8 entry).  Frame n is the `pixels` elements at label + n * pixels.  The
+ * call zeroes counts itself, on `stream`; exact integers (LDS and global integer atomics, no float arithmetic).  Any
+ * pixels >= 1; the uint8 pointer may have any alignment (a slice of a larger tensor).  SEGMIF_EINVAL: a null pointer, N < 1,
+ * pixels < 1, counts not 8-byte aligned. */
+int segmif_label_stats_u8(const uint8_t* label, int N, int64_t pixels, int64_t* counts, void* stream);
+int segmif_label_stats_i64(const int64_t* label, int N, int64_t pixels, int64_t* counts, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * Training path (backward of the ops above; autograd in the reference: loss.backward() at

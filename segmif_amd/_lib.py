@@ -205,6 +205,10 @@ SIGNATURES = {
     "segmif_palette_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "segmif_augment_record_bytes": (c_int, []),
     "segmif_augment_pick_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
+    "segmif_augment_pick_class_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p,
+                                             c_void_p, c_void_p, c_int, c_void_p]),
+    "segmif_label_stats_u8": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p]),
+    "segmif_label_stats_i64": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p]),
     "segmif_augment_apply_u8": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int]
                                 + [c_void_p] * 5),
     "segmif_wgrad_workspace_size":(c_int64, [c_int64, c_int, c_int]),

@@ -7,6 +7,7 @@
 //   pick  : grid (10 candidates, B).  Class counts of the candidate's crop window over the VIRTUAL label (nearest-resized
 //           through the index tables, flipped, padded with 255), LDS histograms; the last block of a sample to finish keeps
 //           the first accepted candidate (imutils.py:225-238) and writes its origin into the record.
+//           pick_class is the same kernel with a second rule per sample: more than t pixels of a wanted class in the window.
 //   apply : grid (crop_w / 64, crop_h / 16, B).  Horizontal pass of the rows the tile needs into LDS as uint8 (Pillow rounds
 //           between its passes), vertical pass from LDS, then flip / photometric / pad / crop / 255 and 16-byte stores.
 #include <hip/hip_runtime.h>
@@ -59,8 +60,15 @@ __device__ __forceinline__ int virtual_label(const Geo& g, const uint8_t* __rest
   return lab[(long long)sy * g.w + sx];
 }
 
+// CLASS: the second acceptance rule (segmif_augment_pick_class_u8).  A sample with want = (c, t), 0 <= c <= 254, accepts the
+// candidates whose window holds MORE than t pixels of class c and keeps the first of them, else the candidate with the most
+// such pixels (lowest index on ties); any other sample goes through the reference's rule below, word for word.  Each block
+// folds (accepted, index, n) into one 64-bit key whose maximum is the kept candidate, in the record's reserved words.
+template <bool CLASS>
 __global__ __launch_bounds__(1024) void pick_kernel(const uint8_t* __restrict__ label, int N, int h, int w, SegmifAugmentRec* __restrict__ rec,
-                                                    const int32_t* __restrict__ tab, long long tab_words, int crop_h, int crop_w) {
+                                                    const int32_t* __restrict__ tab, long long tab_words, int crop_h, int crop_w,
+                                                    const int32_t* __restrict__ want, int32_t* __restrict__ got,
+                                                    unsigned long long* __restrict__ tally, int n_class_tally) {
   __shared__ unsigned int hist[16][256];
   __shared__ unsigned int tot[256];
   SegmifAugmentRec* r = rec + blockIdx.y;
@@ -102,6 +110,40 @@ __global__ __launch_bounds__(1024) void pick_kernel(const uint8_t* __restrict__ 
   }
   __syncthreads();
   if (threadIdx.x == 0) {
+    if constexpr (CLASS) {
+      const int wc = want[2 * blockIdx.y], wt = want[2 * blockIdx.y + 1];
+      if (wc >= 0 && wc <= 254 && wt >= 0) {  // (the wrapper refuses anything else that is not negative; here it falls through)
+        const unsigned int n = tot[wc];
+        const bool ok = n > (unsigned)wt;
+        // accepted candidates beat rejected ones and the lower index wins among them; rejected ones compare by n, then index
+        const unsigned long long key = ok ? (1ull << 62) | ((unsigned long long)(15 - c) << 32) | n
+                                          : ((unsigned long long)n << 4) | (unsigned long long)(15 - c);
+        unsigned long long* slot = reinterpret_cast<unsigned long long*>(&r->reserved[0]);
+        atomicMax(slot, key);
+        if (ok) atomicOr(reinterpret_cast<unsigned int*>(&r->accept_mask), 1u << c);
+        __threadfence();
+        const unsigned int ticket = atomicAdd(reinterpret_cast<unsigned int*>(&r->ticket), 1u);
+        if (ticket == NCAND - 1) {
+          __threadfence();
+          const unsigned int mask = atomicExch(reinterpret_cast<unsigned int*>(&r->accept_mask), 0u);
+          const unsigned long long best = atomicExch(slot, 0ull);
+          const bool hit = (best >> 62) != 0;
+          const int chosen = hit ? 15 - (int)((best >> 32) & 15u) : 15 - (int)(best & 15u);
+          const unsigned int n_chosen = hit ? (unsigned int)best : (unsigned int)(best >> 4);
+          r->accepted = (int32_t)mask;
+          r->chosen = chosen;
+          r->box_h = r->cand[2 * chosen];
+          r->box_w = r->cand[2 * chosen + 1];
+          got[blockIdx.y] = (int32_t)n_chosen;
+          if (tally && wc < n_class_tally) {
+            atomicAdd(&tally[2 * wc], 1ull);
+            if (hit) atomicAdd(&tally[2 * wc + 1], 1ull);
+          }
+          atomicExch(reinterpret_cast<unsigned int*>(&r->ticket), 0u);
+        }
+        return;
+      }
+    }
     unsigned long long sum = 0, mx = 0;
     for (int k = 0; k < 255; ++k) {  // bin 255 is the ignore label
       sum += tot[k];
@@ -122,6 +164,7 @@ __global__ __launch_bounds__(1024) void pick_kernel(const uint8_t* __restrict__ 
       r->chosen = chosen;
       r->box_h = r->cand[2 * chosen];
       r->box_w = r->cand[2 * chosen + 1];
+      if constexpr (CLASS) got[blockIdx.y] = -1;
       atomicExch(reinterpret_cast<unsigned int*>(&r->ticket), 0u);
     }
   }
@@ -275,8 +318,18 @@ extern "C" int segmif_augment_record_bytes(void) { return (int)sizeof(SegmifAugm
 extern "C" int segmif_augment_pick_u8(const uint8_t* label, int N, int h, int w, SegmifAugmentRec* rec, const int32_t* tab,
                                       int64_t tab_words, int B, int crop_h, int crop_w, void* stream) {
   if (!label || !rec || !tab || tab_words <= 0 || !sizes_ok(N, h, w, B, crop_h, crop_w)) return SEGMIF_EINVAL;
-  hipLaunchKernelGGL(pick_kernel, dim3(NCAND, (unsigned)B), dim3(1024), 0, (hipStream_t)stream, label, N, h, w, rec, tab,
-                     (long long)tab_words, crop_h, crop_w);
+  hipLaunchKernelGGL(pick_kernel<false>, dim3(NCAND, (unsigned)B), dim3(1024), 0, (hipStream_t)stream, label, N, h, w, rec, tab,
+                     (long long)tab_words, crop_h, crop_w, (const int32_t*)nullptr, (int32_t*)nullptr, (unsigned long long*)nullptr, 0);
+  return (int)hipGetLastError();
+}
+
+extern "C" int segmif_augment_pick_class_u8(const uint8_t* label, int N, int h, int w, SegmifAugmentRec* rec, const int32_t* tab,
+                                            int64_t tab_words, int B, int crop_h, int crop_w, const int32_t* want, int32_t* got,
+                                            int64_t* tally, int n_class_tally, void* stream) {
+  if (!label || !rec || !tab || tab_words <= 0 || !want || !got || !sizes_ok(N, h, w, B, crop_h, crop_w)) return SEGMIF_EINVAL;
+  if ((uintptr_t)rec & 7 || (uintptr_t)tally & 7 || (tally && n_class_tally < 1) || n_class_tally < 0) return SEGMIF_EINVAL;  // 64-bit atomics
+  hipLaunchKernelGGL(pick_kernel<true>, dim3(NCAND, (unsigned)B), dim3(1024), 0, (hipStream_t)stream, label, N, h, w, rec, tab,
+                     (long long)tab_words, crop_h, crop_w, want, got, reinterpret_cast<unsigned long long*>(tally), n_class_tally);
   return (int)hipGetLastError();
 }
 

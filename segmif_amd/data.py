@@ -238,21 +238,43 @@ class DeviceDataset:
         stack_same_size(items)
         return cls.from_arrays([it[0] for it in items], *(np.stack([it[k] for it in items]) for k in (1, 2, 3, 4)), device=device)
 
-    def augment(self, rec, tab, crop_h, crop_w, pick=True):
+    def augment(self, rec, tab, crop_h, crop_w, pick=True, want=None, tally=None):
         """rec (B, REC_WORDS), tab: host int32 arrays of pack_records -> (ir3, vis3, mask3, label, rec_dev).  One pinned,
-        asynchronous upload, then the two kernels on the current stream."""
+        asynchronous upload, then the two kernels on the current stream.
+
+        want: None, or a host (B, 2) integer array (class or -1, threshold) per sample.  It travels in the same upload and the
+        pick step becomes ops.augment_pick_class (rare-class sampling, NOT the reference's loader); the result then ends with
+        one more tensor, got (B,) int32.  tally: the (n_class, 2) int64 device tensor that step adds (drawn, hit) to."""
         from . import ops
         B = rec.shape[0]
-        blob = self._staging(rec.size + tab.size)
+        if want is not None:
+            if not pick:
+                raise ValueError("augment: want belongs to the pick step (pick=True)")
+            want = ops.check_want(want, B)
+        words = rec.size + tab.size + (want.size if want is not None else 0)
+        blob = self._staging(words)
         blob[:rec.size].copy_(torch.from_numpy(rec.reshape(-1)))
         blob[rec.size:rec.size + tab.size].copy_(torch.from_numpy(tab))
-        dev = torch.empty(rec.size + tab.size, dtype=torch.int32, device=self.ir.device)
-        dev.copy_(blob[:rec.size + tab.size], non_blocking=True)
+        if want is not None:
+            blob[rec.size + tab.size:words].copy_(torch.from_numpy(want.reshape(-1)))
+        dev = torch.empty(words, dtype=torch.int32, device=self.ir.device)
+        dev.copy_(blob[:words], non_blocking=True)
         self._staged[self._turn][1].record()
-        rec_d, tab_d = dev[:rec.size].view(B, REC_WORDS), dev[rec.size:]
-        if pick:
+        rec_d, tab_d = dev[:rec.size].view(B, REC_WORDS), dev[rec.size:rec.size + tab.size]
+        extra = (rec_d,)
+        if want is not None:
+            extra += (ops.augment_pick_class(self.label, rec_d, tab_d, crop_h, crop_w, dev[rec.size + tab.size:].view(B, 2), tally),)
+        elif pick:
             ops.augment_pick(self.label, rec_d, tab_d, crop_h, crop_w)
-        return ops.augment_apply(self.ir, self.vis, self.mask, self.label, rec_d, tab_d, crop_h, crop_w) + (rec_d,)
+        return ops.augment_apply(self.ir, self.vis, self.mask, self.label, rec_d, tab_d, crop_h, crop_w) + extra
+
+    def label_stats(self, n_class=9, ignore_index=255):
+        """-> LabelStats of the resident labels: one launch (csrc/label_stats.hip) and one readback, then cached.  Raises
+        ValueError for a label that is neither below n_class nor ignore_index."""
+        from . import ops
+        if not hasattr(self, "_label_counts"):
+            self._label_counts = ops.label_stats(self.label).cpu().numpy()
+        return LabelStats(self._label_counts, self.names, n_class, ignore_index)
 
     def _staging(self, words):
         """Two pinned buffers used in turn; a buffer is rewritten only after the copy that last read it has completed."""
@@ -280,6 +302,123 @@ def stack_same_size(items):
                                    f"{items[0][0]} is {h} x {w}.  Resize the set, or split it by size into several data sets.")
 
 
+# ------------------------------------------------------------------------------------------------------------ class balance
+
+RULES = ("inverse", "median", "enet")
+
+
+class LabelStats:
+    """Class statistics of a label set, from the (N, 257) int64 count table of ops.label_stats (a host array): what class
+    weights and rare-class sampling are computed from.  None of it is the reference's.
+
+    counts (N, K): pixels of class c in frame n; pixels (K,): per class over the set; frames (K,): frames holding at least one
+    pixel of the class; freq (K,): pixels / pixels.sum(); valid (N,): labelled (non-ignore) pixels per frame."""
+
+    def __init__(self, counts, names, n_class=9, ignore_index=255):
+        counts = np.asarray(counts)
+        if counts.ndim != 2 or counts.shape[1] != 257 or counts.dtype.kind not in "iu" or len(names) != counts.shape[0]:
+            raise ValueError(f"LabelStats: counts must be an (N, 257) integer table with one name per row, got {counts.dtype} {counts.shape}")
+        if not 1 <= n_class <= 255:
+            raise ValueError(f"LabelStats: n_class {n_class} outside 1..255")
+        bad = counts > 0
+        bad[:, :n_class] = False
+        if 0 <= ignore_index <= 255:
+            bad[:, ignore_index] = False
+        if bad.any():
+            n = int(np.argmax(bad.any(axis=1)))
+            v = int(np.argmax(bad[n]))
+            raise ValueError(f"label_stats: frame {n} ({names[n]}) holds {int(counts[n, v])} pixels of "
+                             + (f"value {v}" if v < 256 else "values outside 0..255")
+                             + f", which is neither a class below {n_class} nor the ignore index {ignore_index}")
+        self.names, self.n_class, self.ignore_index = list(names), n_class, ignore_index
+        self.counts = counts[:, :n_class].astype(np.int64)
+        self.pixels = self.counts.sum(axis=0)
+        self.frames = (self.counts > 0).sum(axis=0)
+        self.valid = self.counts.sum(axis=1)
+        total = int(self.pixels.sum())
+        self.freq = self.pixels / float(total) if total else np.zeros(n_class, dtype=np.float64)
+
+    def table(self):
+        """-> printable rows: a header, then class, pixels, share of the labelled pixels and frames per class"""
+        rows = [f"{'class':>5} {'pixels':>14} {'share':>9} {'frames':>7}  of {len(self.names)} frames, {int(self.valid.sum())} labelled pixels"]
+        for c in range(self.n_class):
+            rows.append(f"{c:>5} {int(self.pixels[c]):>14} {self.freq[c]:>9.6f} {int(self.frames[c]):>7}")
+        return rows
+
+    def class_weights(self, rule):
+        """-> (K,) float64 weights for weighted cross entropy; a class without a pixel gets 0.
+        inverse: 1 / f_c, divided by the mean of 1 / f over the present classes.
+        median:  median-frequency balancing (Eigen and Fergus 2015): phi_c = pixels_c / (labelled pixels of the frames that hold
+                 c), w_c = median(phi over the present classes) / phi_c.
+        enet:    1 / ln(1.02 + f_c) (Paszke et al. 2016)."""
+        if rule not in RULES:
+            raise ValueError(f"class_weights: rule {rule!r} is not one of {', '.join(RULES)}")
+        present = self.pixels > 0
+        w = np.zeros(self.n_class, dtype=np.float64)
+        if not present.any():
+            return w
+        f = self.freq[present]
+        if rule == "inverse":
+            inv = 1.0 / f
+            w[present] = inv / inv.mean()
+        elif rule == "median":
+            held = ((self.counts > 0) * self.valid[:, None]).sum(axis=0)[present]
+            phi = self.pixels[present] / held.astype(np.float64)
+            w[present] = np.median(phi) / phi
+        else:
+            w[present] = 1.0 / np.log(1.02 + f)
+        return w
+
+
+class RareClassSampler:
+    """Rare-class sampling as DAFormer defines it (Hoyer et al. 2022); NOT the reference's loader, which walks its slice front
+    to back.  P(c) is proportional to exp((1 - f_c) / temperature) over the classes that have a candidate frame, a frame of
+    `indices` with MORE than min_pixels pixels of the class; f_c is the class's share of the whole table.  A sample is, with
+    probability `fraction`, a class drawn from P and a frame drawn uniformly from that class's candidates, else the next frame of
+    `indices` in order (that cursor moves for such samples only).  temperature, min_pixels and min_crop_ratio default to
+    DAFormer's values; fraction is this project's.  Private generators: random.Random(seed), numpy RandomState(seed)."""
+
+    def __init__(self, stats, indices, temperature=0.01, min_pixels=3000, min_crop_ratio=0.5, fraction=1.0, seed=0):
+        if not temperature > 0 or min_pixels < 0 or not 0 <= min_crop_ratio or not 0.0 <= fraction <= 1.0:
+            raise ValueError(f"RareClassSampler: temperature {temperature} > 0, min_pixels {min_pixels} >= 0, min_crop_ratio "
+                             f"{min_crop_ratio} >= 0 and fraction {fraction} in [0, 1] are required")
+        self.stats, self.indices = stats, [int(i) for i in indices]
+        if not self.indices or min(self.indices) < 0 or max(self.indices) >= stats.counts.shape[0]:
+            raise ValueError("RareClassSampler: indices must name frames of the statistics' table")
+        self.temperature, self.min_pixels, self.min_crop_ratio, self.fraction = temperature, min_pixels, min_crop_ratio, fraction
+        sub = stats.counts[self.indices]
+        self.candidates = [[i for i, n in zip(self.indices, sub[:, c]) if n > min_pixels] for c in range(stats.n_class)]
+        self.classes = [c for c in range(stats.n_class) if self.candidates[c]]
+        self.dropped = [c for c in range(stats.n_class) if not self.candidates[c]]
+        if not self.classes:
+            raise ValueError(f"RareClassSampler: no class has a frame with more than {min_pixels} pixels of it: nothing to sample")
+        z = (1.0 - stats.freq[self.classes].astype(np.float64)) / float(temperature)
+        e = np.exp(z - z.max())
+        self.prob = np.zeros(stats.n_class, dtype=np.float64)
+        self.prob[self.classes] = e / e.sum()
+        self._cum = np.cumsum(self.prob[self.classes])
+        self._py, self._np = random.Random(seed), np.random.RandomState(seed)
+        self._at = 0
+
+    def crop_threshold(self, scaled_pixels, frame_pixels):
+        """pixels of the wanted class a crop window must EXCEED: min_pixels * min_crop_ratio, scaled by the frame's resize"""
+        return int(np.floor(self.min_pixels * self.min_crop_ratio * scaled_pixels / frame_pixels))
+
+    def draw(self, n):
+        """-> [(frame index, class or -1), ...]: -1 marks a sequential sample"""
+        out = []
+        for _ in range(n):
+            if self._py.random() < self.fraction:
+                k = min(int(np.searchsorted(self._cum, self._np.random_sample(), side="right")), len(self.classes) - 1)
+                c = self.classes[k]
+                frames = self.candidates[c]
+                out.append((frames[self._py.randrange(len(frames))], c))
+            else:
+                out.append((self.indices[self._at], -1))
+                self._at = (self._at + 1) % len(self.indices)
+        return out
+
+
 # ------------------------------------------------------------------------------------------------------------------ iterator
 
 class AugmentedBatches:
@@ -296,10 +435,15 @@ class AugmentedBatches:
     other numbers while the distribution of the results is the same.
 
     photometric: any subset of ("brightness", "contrast"); saturation and hue are not available.
-    aug=False: every frame whole, value / 255, no resize, flip, distortion or crop."""
+    aug=False: every frame whole, value / 255, no resize, flip, distortion or crop.
+
+    sampler: None, or a RareClassSampler over this rank's slice.  The frames then come from sampler.draw and a sample drawn for
+    a class keeps the first crop candidate with more than floor(min_pixels * min_crop_ratio * (nw * nh) / (w * h)) pixels of
+    it (else the candidate with the most); last_params[i]["want"] is (class or -1, threshold), rcs_tally() the device's count
+    of drawn / hit samples per class.  NOT the reference's loader.  With None nothing changes, the random stream included."""
 
     def __init__(self, dataset, batch, crop_size=512, rescale_range=(0.5, 2.0), fliplr=True, photometric=PHOTOMETRIC, seed=0,
-                 rank=0, world=1, aug=True):
+                 rank=0, world=1, aug=True, sampler=None):
         unknown = [p for p in photometric if p not in PHOTOMETRIC]
         if unknown:
             raise ValueError(f"photometric: {unknown} not available; this loader applies {PHOTOMETRIC} only (saturation and hue go "
@@ -319,6 +463,14 @@ class AugmentedBatches:
         self._py, self._np = random.Random(seed + rank), np.random.RandomState(seed + rank)
         self._at = 0
         self.last_params = None
+        self.sampler = sampler
+        if sampler is not None:
+            if not aug:
+                raise ValueError("sampler: rare-class sampling picks crops, aug=False has none")
+            if list(sampler.indices) != self.indices:
+                raise ValueError("sampler: built over other frames than this rank's slice of the data set "
+                                 "(RareClassSampler(stats, list(dist.shard(len(dataset), rank, world)), ...))")
+            self._tally = torch.zeros((sampler.stats.n_class, 2), dtype=torch.int64, device=dataset.label.device)
 
     def __len__(self):
         """batches per pass (drop_last)"""
@@ -334,7 +486,31 @@ class AugmentedBatches:
         return [sample_params(self._py, self._np, h, w, self.crop, self.crop, self.rescale_range, self.fliplr, self.photometric)
                 for _ in range(n)]
 
+    def rcs_tally(self):
+        """-> (n_class, 2) int64 numpy array: per class the samples drawn for it so far and those of them for which a candidate
+        window passed the threshold.  One readback of the device tally."""
+        if self.sampler is None:
+            raise RuntimeError("rcs_tally: this iterator has no sampler")
+        return self._tally.cpu().numpy()
+
+    def _next_sampled(self):
+        """One batch whose frames (and wanted classes) come from the sampler; the crop parameters are drawn as ever."""
+        drawn = self.sampler.draw(self.batch)
+        idx = [i for i, _ in drawn]
+        self.last_params = params = self.draw(len(idx))
+        h, w = self.dataset.shape
+        want = np.zeros((len(idx), 2), dtype=np.int32)
+        for b, ((_, c), p) in enumerate(zip(drawn, params)):
+            # the crop is cut after the random rescale: the threshold scales with the frame's area
+            want[b] = (c, self.sampler.crop_threshold(p["nw"] * p["nh"], w * h)) if c >= 0 else (-1, 0)
+            p["want"] = (int(want[b, 0]), int(want[b, 1]))
+        rec, tab = pack_records(idx, params, h, w)
+        out = self.dataset.augment(rec, tab, self.crop, self.crop, pick=True, want=want, tally=self._tally)[:4]
+        return (tuple(self.dataset.names[i] for i in idx),) + tuple(out)
+
     def __next__(self):
+        if self.sampler is not None:
+            return self._next_sampled()
         if self._at + self.batch > len(self.indices):  # drop_last, then a fresh pass
             self._at = 0
         idx = self.indices[self._at:self._at + self.batch]

@@ -1513,3 +1513,54 @@ def augment_apply(ir, vis, mask, label, rec, tab, crop_h, crop_w):
                                                    vis3.data_ptr(), mask3.data_ptr(), out.data_ptr(), _stream()),
                "segmif_augment_apply_u8")
     return ir3, vis3, mask3, out
+
+
+def check_want(want, B=None):
+    """Host-side check of a pick_class `want` table (it lives on the device when the kernel reads it): (B, 2) integers, the
+    class -1 (any negative value: the reference's rule) or 0..254, the threshold >= 0 -> (B, 2) int32 numpy array."""
+    import numpy as np
+    w = np.asarray(want)
+    if w.ndim != 2 or w.shape[1] != 2 or w.shape[0] < 1 or (B is not None and w.shape[0] != B) or w.dtype.kind not in "iu":
+        raise ValueError(f"augment_pick_class: want must be (B, 2) integers (class or -1, threshold), got {w.dtype} {w.shape}")
+    if (w[:, 0] > 254).any() or (w[:, 1] < 0).any() or (w > 2 ** 31 - 1).any() or (w < -2 ** 31).any():
+        raise ValueError("augment_pick_class: a wanted class lies in 0..254 (or is -1) and a threshold is >= 0 "
+                         f"(SEGMIF_EINVAL), got {w.tolist()}")
+    return np.ascontiguousarray(w, dtype=np.int32)
+
+
+def augment_pick_class(label, rec, tab, crop_h, crop_w, want, tally=None):
+    """segmif_augment_pick_class_u8: augment_pick with a second rule per sample.  want: (B, 2) (class or -1, threshold), either a
+    host array / list, which is checked and uploaded here, or an int32 device tensor whose values the caller has passed through
+    check_want.  tally: None or an (n_class, 2) int64 device tensor that accumulates (drawn, hit) per class.  -> got (B,) int32
+    on the device: the chosen window's pixels of the wanted class, -1 for a sample without one."""
+    N, h, w = _augment_args(label, rec, tab, crop_h, crop_w)
+    B = rec.shape[0]
+    if not isinstance(want, torch.Tensor) or not want.is_cuda:
+        want = torch.from_numpy(check_want(want.numpy() if isinstance(want, torch.Tensor) else want, B)).to(label.device)
+    _req_u8(want, "want", (B, 2), dtype=torch.int32)
+    if tally is not None:
+        _req_u8(tally, "tally", dtype=torch.int64)
+        if tally.dim() != 2 or tally.shape[1] != 2 or tally.shape[0] < 1:
+            raise RuntimeError("augment_pick_class: tally must be (n_class, 2) int64")
+    got = torch.empty(B, device=label.device, dtype=torch.int32)
+    _lib.check(_lib.load().segmif_augment_pick_class_u8(label.data_ptr(), N, h, w, rec.data_ptr(), tab.data_ptr(), tab.numel(), B, crop_h,
+                                                        crop_w, want.data_ptr(), got.data_ptr(),
+                                                        tally.data_ptr() if tally is not None else None,
+                                                        tally.shape[0] if tally is not None else 0, _stream()),
+               "segmif_augment_pick_class_u8")
+    return got
+
+
+def label_stats(label):
+    """segmif_label_stats_u8 / _i64: per-frame class counts of uint8 (N, H, W) or int64 (B, H, W) label maps -> (N, 257) int64 on
+    the device; column v < 256 counts the pixels equal to v, column 256 the values outside 0..255 (int64 maps only)."""
+    if not isinstance(label, torch.Tensor) or not label.is_cuda:
+        raise RuntimeError("segmif_amd: label_stats needs a tensor on the MI355X device (the HIP path has no CPU fallback)")
+    if label.dtype not in (torch.uint8, torch.int64) or label.dim() != 3 or not label.is_contiguous() or label.numel() < 1:
+        raise RuntimeError(f"label_stats: label must be a contiguous, non-empty (N, H, W) uint8 or int64 tensor, got {label.dtype} "
+                           f"{tuple(label.shape)}")
+    N = label.shape[0]
+    counts = torch.empty((N, 257), device=label.device, dtype=torch.int64)
+    fn = "segmif_label_stats_u8" if label.dtype == torch.uint8 else "segmif_label_stats_i64"
+    _lib.check(getattr(_lib.load(), fn)(label.data_ptr(), N, label.shape[1] * label.shape[2], counts.data_ptr(), _stream()), fn)
+    return counts

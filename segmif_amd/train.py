@@ -336,6 +336,21 @@ class _GuardLog:
             raise SystemExit(self.stop)
 
 
+class _RcsLog:
+    """What a log line adds under rare-class sampling: ONE rcs_tally() readback per line - per class the samples drawn for it and
+    those of them whose crop passed the threshold, since the previous line.  Nothing for a loader without a sampler."""
+
+    def __init__(self, batches):
+        self.batches, self.last = batches, 0
+
+    def line(self):
+        if self.batches.sampler is None:
+            return ""
+        now = self.batches.rcs_tally()
+        d, self.last = now - self.last, now
+        return " rcs drawn/hit " + (" ".join(f"{c}:{int(d[c, 0])}/{int(d[c, 1])}" for c in range(len(d)) if d[c, 0]) or "none")
+
+
 def _miou(seg, fus, val, batch):
     """mIoU of the pair forward (fusion net -> segmentation net) over a DeviceDataset, through segmif_amd.evaluate.Evaluator"""
     from .evaluate import Evaluator
@@ -404,6 +419,24 @@ def main(argv=None):
     ap.add_argument("--label-smoothing", type=float, default=0.0, help="--seg-loss ce / weighted: label smoothing in [0, 1); above 0 it is "
                     "not the reference's objective")
     ap.add_argument("--seg-class-weights", type=float, nargs="+", metavar="W", help="--seg-loss weighted: one weight >= 0 per class (9)")
+    ap.add_argument("--seg-class-weights-from", choices=("inverse", "median", "enet"), help="--seg-loss weighted: compute "
+                    "the class weights from the training split's labels, counted on the device, instead of typing them: inverse "
+                    "(1 / frequency, mean 1 over the present classes), median (median-frequency balancing, Eigen and Fergus 2015) or "
+                    "enet (1 / ln(1.02 + frequency), Paszke et al. 2016).  A class without a pixel gets "
+                    "weight 0.  Excludes --seg-class-weights")
+    ap.add_argument("--rare-class-sampling", action="store_true", help="draw the training frames by rare-class sampling (Hoyer et al. "
+                    "2022, DAFormer) instead of walking the split front to back: a class c with probability proportional to "
+                    "exp((1 - frequency_c) / T), a frame that holds it, and a crop that shows it.  Off by default.  This project's "
+                    "addition, NOT the reference's loader")
+    ap.add_argument("--rcs-temperature", type=float, metavar="T", help="with --rare-class-sampling: T > 0 (default 0.01, DAFormer's)")
+    ap.add_argument("--rcs-min-pixels", type=int, metavar="N", help="with --rare-class-sampling: a frame is a candidate of a class when "
+                    "it holds more than N pixels of it (default 3000, DAFormer's)")
+    ap.add_argument("--rcs-min-crop-ratio", type=float, metavar="R", help="with --rare-class-sampling: a crop is accepted when it holds "
+                    "more than N * R pixels of the class, scaled by the frame's resize (default 0.5, DAFormer's)")
+    ap.add_argument("--rcs-fraction", type=float, metavar="F", help="with --rare-class-sampling: the share of samples drawn that way, in "
+                    "(0, 1]; the others walk the split in order (default 1.0)" + ours)
+    ap.add_argument("--rcs-phases", choices=("seg", "fusion", "both"), help="with --rare-class-sampling: the phases whose loader "
+                    "samples (default seg)")
     ap.add_argument("--seg-region", choices=SEG_REGIONS, help="add a region objective to whatever --seg-loss builds, for the "
                     "SEGMENTATION phase only: lovasz is Lovasz-Softmax (the convex surrogate of the Jaccard index, the batch as one set), "
                     "dice the soft Dice loss.  This project's addition, NOT the reference's objective: its train.py trains on CE alone")
@@ -430,9 +463,26 @@ def main(argv=None):
     n_class = 9
     if args.seg_class_weights is not None and args.seg_loss != "weighted":
         ap.error(f"--seg-class-weights belongs to --seg-loss weighted, not {args.seg_loss}")
-    if args.seg_loss == "weighted" and (args.seg_class_weights is None or len(args.seg_class_weights) != n_class
-                                        or min(args.seg_class_weights) < 0):
-        ap.error(f"--seg-loss weighted needs --seg-class-weights with {n_class} values >= 0")
+    if args.seg_class_weights_from is not None and args.seg_loss != "weighted":
+        ap.error(f"--seg-class-weights-from belongs to --seg-loss weighted, not {args.seg_loss}")
+    if args.seg_class_weights_from is not None and args.seg_class_weights is not None:
+        ap.error("--seg-class-weights-from computes the weights that --seg-class-weights types: give one of the two")
+    if args.seg_loss == "weighted" and args.seg_class_weights_from is None and (
+            args.seg_class_weights is None or len(args.seg_class_weights) != n_class or min(args.seg_class_weights) < 0):
+        ap.error(f"--seg-loss weighted needs --seg-class-weights with {n_class} values >= 0, or --seg-class-weights-from inverse | median | enet")
+    for flag, value in (("--rcs-temperature", args.rcs_temperature), ("--rcs-min-pixels", args.rcs_min_pixels),
+                        ("--rcs-min-crop-ratio", args.rcs_min_crop_ratio), ("--rcs-fraction", args.rcs_fraction),
+                        ("--rcs-phases", args.rcs_phases)):
+        if value is not None and not args.rare_class_sampling:
+            ap.error(f"{flag} belongs to --rare-class-sampling, which is not given")
+    if args.rcs_temperature is not None and not (args.rcs_temperature > 0 and math.isfinite(args.rcs_temperature)):
+        ap.error(f"--rcs-temperature {args.rcs_temperature}: must be a finite number > 0")
+    if args.rcs_min_pixels is not None and args.rcs_min_pixels < 0:
+        ap.error(f"--rcs-min-pixels {args.rcs_min_pixels}: must be >= 0")
+    if args.rcs_min_crop_ratio is not None and not (args.rcs_min_crop_ratio >= 0 and math.isfinite(args.rcs_min_crop_ratio)):
+        ap.error(f"--rcs-min-crop-ratio {args.rcs_min_crop_ratio}: must be a finite number >= 0")
+    if args.rcs_fraction is not None and not 0.0 < args.rcs_fraction <= 1.0:
+        ap.error(f"--rcs-fraction {args.rcs_fraction}: must lie in (0, 1]")
     if not 0.0 <= args.label_smoothing < 1.0:
         ap.error(f"--label-smoothing {args.label_smoothing}: must lie in [0, 1)")
     if args.label_smoothing and args.seg_loss not in ("ce", "weighted"):
@@ -473,7 +523,7 @@ def main(argv=None):
     if args.backbone == "mit_b0":
         ap.error("--backbone mit_b0: Fusion_Network3_ac takes 64/128-channel segmentation features, mit_b0 gives 32/64")
     from .core import Fusion_Network3_ac, Network3
-    from .data import AugmentedBatches, DeviceDataset, PairFolder, synthetic_pairs
+    from .data import AugmentedBatches, DeviceDataset, PairFolder, RareClassSampler, synthetic_pairs
 
     torch.manual_seed(args.seed)
     if args.synthetic is not None:
@@ -496,6 +546,17 @@ def main(argv=None):
               f"(torch.manual_seed({args.seed}))")
     seg_initial = {k: v.clone() for k, v in seg.state_dict().items()}
     crit = torch.nn.CrossEntropyLoss(ignore_index=255)
+    stats = None
+    if args.seg_class_weights_from is not None or args.rare_class_sampling:
+        stats = train_set.label_stats(n_class)  # (the fused set of the segmentation phase shares these labels)
+        print(f"[train] classes of the {args.split if args.synthetic is None else 'synthetic'} labels, counted on the device:")
+        for row in stats.table():
+            print("[train]   " + row)
+    if args.seg_class_weights_from is not None:
+        args.seg_class_weights = [float(v) for v in stats.class_weights(args.seg_class_weights_from)]
+        absent = [c for c in range(n_class) if stats.pixels[c] == 0]
+        print(f"[train] --seg-class-weights-from {args.seg_class_weights_from}: " + " ".join(f"{v:.6g}" for v in args.seg_class_weights)
+              + (f"; class{'es' if len(absent) > 1 else ''} {', '.join(map(str, absent))} without a pixel: weight 0" if absent else ""))
     seg_crit = make_seg_loss(args.seg_loss, ohem_thresh=args.ohem_thresh, ohem_n_min=args.ohem_n_min if args.seg_loss == "ohem" else None,
                              focal_gamma=args.focal_gamma, label_smoothing=args.label_smoothing,
                              class_weights=args.seg_class_weights).cuda()
@@ -533,6 +594,28 @@ def main(argv=None):
         return ema_weights(optimizer, net) if on else contextlib.nullcontext()
 
     loader_kw = dict(batch=batch, crop_size=args.crop_size, rescale_range=tuple(args.rescale_range), fliplr=True)
+    rcs_kw, rcs_phases = None, ()
+    if args.rare_class_sampling:
+        rcs_kw = dict(temperature=0.01 if args.rcs_temperature is None else args.rcs_temperature,
+                      min_pixels=3000 if args.rcs_min_pixels is None else args.rcs_min_pixels,
+                      min_crop_ratio=0.5 if args.rcs_min_crop_ratio is None else args.rcs_min_crop_ratio,
+                      fraction=1.0 if args.rcs_fraction is None else args.rcs_fraction)
+        rcs_phases = {"seg": ("seg",), "fusion": ("fusion",), "both": ("seg", "fusion")}[args.rcs_phases or "seg"]
+        try:
+            probe = RareClassSampler(stats, range(len(train_set)), **rcs_kw)
+        except ValueError as e:
+            raise SystemExit(f"[train] --rare-class-sampling: {e}")
+        print(f"[train] --rare-class-sampling ({', '.join(f'{k} {v}' for k, v in rcs_kw.items())}; phases {', '.join(rcs_phases)}): this "
+              "project's addition, NOT the reference's loader (its train.py walks the split front to back and crops by the 0.75 test "
+              "alone)")
+        print("[train]   candidate frames per class: " + " ".join(f"{c}:{len(f)}" for c, f in enumerate(probe.candidates))
+              + "; sampling probability: " + " ".join(f"{c}:{probe.prob[c]:.4f}" for c in probe.classes)
+              + (f"; dropped (no frame with more than {rcs_kw['min_pixels']} pixels): {', '.join(map(str, probe.dropped))}"
+                 if probe.dropped else "; no class dropped"))
+
+    def loader(dataset, phase, seed, **kw):
+        sampler = RareClassSampler(stats, range(len(dataset)), seed=seed, **rcs_kw) if phase in rcs_phases else None
+        return AugmentedBatches(dataset, seed=seed, sampler=sampler, **loader_kw, **kw)
     best, wrote_seg, opt = None, False, None
     fusion_loss = make_fusion_loss(args.fusion_loss) if args.fusion_loss is not None else None
     if fusion_loss is not None:
@@ -549,13 +632,15 @@ def main(argv=None):
         trainer = FusionTrainer(seg, fus, make_fusion_optimizer(fus, iter_, lr=args.lr, **sched, **(ema_kw if ema_fus else {})), crit,
                                 iter_=iter_, fusion_loss=fusion_loss)
         glog = _GuardLog(trainer.opt, [("fusion_net", fus)], args.max_consecutive_skips) if guarded else None
-        batches = AugmentedBatches(train_set, seed=args.seed + 2 * iter_, **loader_kw)
+        batches = loader(train_set, "fusion", args.seed + 2 * iter_)
+        rlog = _RcsLog(batches)
         n_fus = args.fusion_iters if args.fusion_iters is not None else (6000 if iter_ == 1 else 4000)
         for n in range(n_fus):
             _, ir3, vis3, mask3, label = next(batches)
             loss = trainer.step(ir3, vis3, mask3, label)
             if (n + 1) % args.log_iters == 0 or n + 1 == n_fus:
-                print(f"[train] round {iter_} fusion iter {n + 1}/{n_fus}: loss {float(loss):.6f}" + (glog.line() if guarded else ""))
+                print(f"[train] round {iter_} fusion iter {n + 1}/{n_fus}: loss {float(loss):.6f}" + (glog.line() if guarded else "")
+                      + rlog.line())
                 if guarded:
                     glog.check()
             if (n + 1) % 500 == 0:
@@ -575,14 +660,15 @@ def main(argv=None):
                 best = _miou(seg, fus, val_set, batch)
             print(f"[train] initial mIoU {best:.4f}")
         glog = _GuardLog(opt, [("seg_net", seg)], args.max_consecutive_skips) if guarded else None
-        batches = AugmentedBatches(fused_set, seed=args.seed + 2 * iter_ + 1, photometric=(), **loader_kw)
+        batches = loader(fused_set, "seg", args.seed + 2 * iter_ + 1, photometric=())
+        rlog = _RcsLog(batches)
         n_seg = args.seg_iters if args.seg_iters is not None else 10000
         for n in range(n_seg):
             _, _, fused3, _, label = next(batches)
             loss = seg_train_step(seg, opt, fused3, label, seg_crit)
             if (n + 1) % args.log_iters == 0 or n + 1 == n_seg:
                 print(f"[train] round {iter_} segmentation iter {n + 1}/{n_seg}: lr {opt.param_groups[0]['lr']:.3e} loss {float(loss):.6f}"
-                      + (glog.line() if guarded else ""))
+                      + (glog.line() if guarded else "") + rlog.line())
                 if guarded:
                     glog.check()
             if (n + 1) % 1000 == 0 or n + 1 == n_seg:
