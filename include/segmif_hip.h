@@ -706,6 +706,41 @@ int segmif_augment_apply_u8(const uint8_t* ir, const uint8_t* vis, const uint8_t
 int segmif_label_stats_u8(const uint8_t* label, int N, int64_t pixels, int64_t* counts, void* stream);
 int segmif_label_stats_i64(const int64_t* label, int N, int64_t pixels, int64_t* counts, void* stream);
 
+/* ClassMix (Olsson et al. 2021; the mixing step of DAFormer, Hoyer et al. 2022): classes of one crop of an augmented batch
+ * pasted into another.  NOT the reference's loader, which mixes nothing.  The rule:
+ *
+ * Inputs: an augmented batch ir3, vis3, mask3 (B, 3, h, w) fp32 and label (B, h, w) int64 (what segmif_augment_apply_u8
+ * writes; w % 4 == 0), a per-sample table of int32 rows (donor, force, key[0], ..., key[n_class-1]), width 2 + n_class,
+ * n_class in 1..255 and min_pixels >= 0.  For receiver b with d = donor[b]:
+ *   - If d == b, the sample is not mixed.  Its output is its input, nothing is selected, and pasted[b] = 0.
+ *   - n_c is the number of pixels of crop d's label equal to c, for c in 0..n_class-1.  The value 255 never counts.  Any other
+ *     value outside 0..n_class-1 never counts either, whatever its low byte: negative values, 256 and 2^40 + 3 all stay out.
+ *   - present = {c : n_c > min_pixels}.  The comparison is strict.
+ *   - If force >= 0: selected = {force} when force is in present, else empty.
+ *   - If force < 0: selected is the k = ceil(|present| / 2) classes of present with the smallest key.  The keys of a row are a
+ *     permutation of 0..n_class-1, so there are no ties.  This is ClassMix's "half of the classes present, at random"; the count
+ *     is (n + n % 2) / 2, as ClassMix and DAFormer's get_class_masks compute it.
+ *   - M(y, x) = [label_d(y, x) in selected].  At every pixel, every channel of ir3, vis3, mask3 and the label take the donor's
+ *     value where M is set and the receiver's elsewhere.  Float values are copied bit for bit: NaN payloads and -0.0 survive,
+ *     no arithmetic is done.
+ *   - Donors are always the UNMIXED inputs: a chain 0 <- 1 <- 2 <- 0 pastes original pixels.  The call is out of place and
+ *     leaves its inputs untouched (the outputs must not overlap the inputs).
+ * Outputs: four new tensors; sel (B, 8) int32, bit c & 31 of word c >> 5 set for each selected class; pasted (B,) int64, the
+ * sum of n_c over the selected classes, which equals the number of set pixels of M; and, when tally (n_class, 2) int64 is
+ * given, tally[c][0] += 1 per sample that selected c and tally[c][1] += n_c.  The call does not zero tally.
+ *
+ * segmif_class_mix_select: counts (B, 257) int64 is segmif_label_stats_i64 over the batch's label; writes sel and pasted, adds
+ * to tally (null: none) through integer atomics.  segmif_class_mix_apply_f32: reads sel and writes the four outputs.  Values
+ * that live on the device are not checked by the entry points: a donor outside 0..B-1 is treated as donor == b, keys are taken
+ * as they are (equal keys rank by class), a force >= n_class selects nothing.  SEGMIF_EINVAL: a null pointer (tally may be
+ * null), B < 1 (apply: B > 65535), n_class outside 1..255, min_pixels < 0, h < 1, w % 4, a float or label pointer not 16-byte
+ * aligned, counts, sel, pasted or tally not 8-byte aligned. */
+int segmif_class_mix_select(const int64_t* counts, const int32_t* table, int B, int n_class, int64_t min_pixels, int32_t* sel,
+                            int64_t* pasted, int64_t* tally, void* stream);
+int segmif_class_mix_apply_f32(const float* ir3, const float* vis3, const float* mask3, const int64_t* label, const int32_t* table,
+                               const int32_t* sel, int B, int h, int w, int n_class, float* ir3_out, float* vis3_out,
+                               float* mask3_out, int64_t* label_out, void* stream);
+
 /* ----------------------------------------------------------------------------------------------
  * Training path (backward of the ops above; autograd in the reference: loss.backward() at
  * train.py:226, :384).  Contractions reuse segmif_igemm_f32 (input gradients, with transposed /

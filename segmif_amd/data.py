@@ -238,35 +238,51 @@ class DeviceDataset:
         stack_same_size(items)
         return cls.from_arrays([it[0] for it in items], *(np.stack([it[k] for it in items]) for k in (1, 2, 3, 4)), device=device)
 
-    def augment(self, rec, tab, crop_h, crop_w, pick=True, want=None, tally=None):
+    def augment(self, rec, tab, crop_h, crop_w, pick=True, want=None, tally=None, mix=None):
         """rec (B, REC_WORDS), tab: host int32 arrays of pack_records -> (ir3, vis3, mask3, label, rec_dev).  One pinned,
         asynchronous upload, then the two kernels on the current stream.
 
         want: None, or a host (B, 2) integer array (class or -1, threshold) per sample.  It travels in the same upload and the
         pick step becomes ops.augment_pick_class (rare-class sampling, NOT the reference's loader); the result then ends with
-        one more tensor, got (B,) int32.  tally: the (n_class, 2) int64 device tensor that step adds (drawn, hit) to."""
+        one more tensor, got (B,) int32.  tally: the (n_class, 2) int64 device tensor that step adds (drawn, hit) to.
+
+        mix: None, or (table, n_class, min_pixels, tally): a host ClassMix table (ops.check_mix_table) that travels in the same
+        upload.  The batch returned is then the MIXED one (ops.class_mix after apply; NOT the reference's loader) and the result
+        ends with two more tensors, sel (B, 8) int32 and pasted (B,) int64; tally is class_mix's (n_class, 2) int64 or None."""
         from . import ops
         B = rec.shape[0]
+        if mix is not None:
+            mix_table, mix_classes, mix_min_pixels, mix_tally = mix
+            mix_table = ops.check_mix_table(mix_table, B, mix_classes)
         if want is not None:
             if not pick:
                 raise ValueError("augment: want belongs to the pick step (pick=True)")
             want = ops.check_want(want, B)
         words = rec.size + tab.size + (want.size if want is not None else 0)
+        mix_at = words
+        if mix is not None:
+            words += mix_table.size
         blob = self._staging(words)
         blob[:rec.size].copy_(torch.from_numpy(rec.reshape(-1)))
         blob[rec.size:rec.size + tab.size].copy_(torch.from_numpy(tab))
         if want is not None:
-            blob[rec.size + tab.size:words].copy_(torch.from_numpy(want.reshape(-1)))
+            blob[rec.size + tab.size:mix_at].copy_(torch.from_numpy(want.reshape(-1)))
+        if mix is not None:
+            blob[mix_at:words].copy_(torch.from_numpy(mix_table.reshape(-1)))
         dev = torch.empty(words, dtype=torch.int32, device=self.ir.device)
         dev.copy_(blob[:words], non_blocking=True)
         self._staged[self._turn][1].record()
         rec_d, tab_d = dev[:rec.size].view(B, REC_WORDS), dev[rec.size:rec.size + tab.size]
         extra = (rec_d,)
         if want is not None:
-            extra += (ops.augment_pick_class(self.label, rec_d, tab_d, crop_h, crop_w, dev[rec.size + tab.size:].view(B, 2), tally),)
+            extra += (ops.augment_pick_class(self.label, rec_d, tab_d, crop_h, crop_w, dev[rec.size + tab.size:mix_at].view(B, 2), tally),)
         elif pick:
             ops.augment_pick(self.label, rec_d, tab_d, crop_h, crop_w)
-        return ops.augment_apply(self.ir, self.vis, self.mask, self.label, rec_d, tab_d, crop_h, crop_w) + extra
+        out = ops.augment_apply(self.ir, self.vis, self.mask, self.label, rec_d, tab_d, crop_h, crop_w)
+        if mix is None:
+            return out + extra
+        mixed = ops.class_mix(*out, dev[mix_at:].view(B, 2 + mix_classes), mix_classes, mix_min_pixels, mix_tally)
+        return mixed[:4] + extra + mixed[4:]
 
     def label_stats(self, n_class=9, ignore_index=255):
         """-> LabelStats of the resident labels: one launch (csrc/label_stats.hip) and one readback, then cached.  Raises
@@ -419,6 +435,50 @@ class RareClassSampler:
         return out
 
 
+class ClassMix:
+    """The policy of ClassMix (Olsson et al. 2021; the mixing step of DAFormer, Hoyer et al. 2022) for AugmentedBatches(mix=);
+    NOT the reference's loader, which mixes nothing.  With probability `prob` a sample receives, from ANOTHER sample of its own
+    batch, the pixels of half of the classes present in that donor's crop (classes="half": those with more than min_pixels
+    pixels, (n + n % 2) / 2 of them, chosen by a random permutation) or, with classes="wanted", of the one class the rare-class
+    sampler drew the donor for (the half rule for a donor drawn in order).  What differs from DAFormer: both samples are labelled
+    (there the receiver is a target-domain image with pseudo-labels), the probability is `prob` (there every sample is mixed;
+    the default 0.5 is this project's choice), and the donor comes from the same batch.  The rule itself: include/segmif_hip.h.
+
+    draw(B, wanted) builds the table from a private random.Random seeded from (seed, rank); neither the global generators nor the
+    loader's crop generators are touched.  Per sample, in order, it draws random() < prob, a donor uniform over the other B - 1
+    samples and a permutation of the classes - all three always, so the stream does not depend on the outcomes."""
+
+    CLASSES = ("half", "wanted")
+
+    def __init__(self, prob=0.5, classes="half", min_pixels=0, n_class=9, seed=0, rank=0):
+        if classes not in self.CLASSES:
+            raise ValueError(f"ClassMix: classes {classes!r} is not one of {', '.join(self.CLASSES)}")
+        if not 0.0 < prob <= 1.0 or min_pixels < 0 or not 1 <= n_class <= 255:
+            raise ValueError(f"ClassMix: prob {prob} in (0, 1], min_pixels {min_pixels} >= 0 and n_class {n_class} in 1..255 are required")
+        self.prob, self.classes, self.min_pixels, self.n_class, self.seed, self.rank = prob, classes, int(min_pixels), n_class, seed, rank
+        self._py = random.Random(f"ClassMix {seed} {rank}")
+
+    def draw(self, B, wanted=None):
+        """-> (B, 2 + n_class) int32 rows (donor, force, keys); donor == the sample itself marks one that is not mixed.
+        wanted: per sample the class the sampler drew it for, or -1 (classes="wanted" only)."""
+        if B < 2:
+            raise ValueError(f"ClassMix: mixing needs two samples, the batch holds {B}")
+        if self.classes == "wanted" and (wanted is None or len(wanted) != B):
+            raise ValueError("ClassMix: classes='wanted' needs the class each sample was drawn for (a RareClassSampler)")
+        table = np.empty((B, 2 + self.n_class), dtype=np.int32)
+        for b in range(B):
+            mixes = self._py.random() < self.prob
+            j = self._py.randrange(B - 1)
+            donor = j if j < b else j + 1
+            keys = list(range(self.n_class))
+            self._py.shuffle(keys)
+            force = -1
+            if self.classes == "wanted" and 0 <= int(wanted[donor]) < self.n_class:
+                force = int(wanted[donor])
+            table[b, 0], table[b, 1], table[b, 2:] = (donor if mixes else b), force, keys
+        return table
+
+
 # ------------------------------------------------------------------------------------------------------------------ iterator
 
 class AugmentedBatches:
@@ -440,10 +500,15 @@ class AugmentedBatches:
     sampler: None, or a RareClassSampler over this rank's slice.  The frames then come from sampler.draw and a sample drawn for
     a class keeps the first crop candidate with more than floor(min_pixels * min_crop_ratio * (nw * nh) / (w * h)) pixels of
     it (else the candidate with the most); last_params[i]["want"] is (class or -1, threshold), rcs_tally() the device's count
-    of drawn / hit samples per class.  NOT the reference's loader.  With None nothing changes, the random stream included."""
+    of drawn / hit samples per class.  NOT the reference's loader.  With None nothing changes, the random stream included.
+
+    mix: None, or a ClassMix.  Every batch is then mixed after augment_apply (ops.class_mix: classes of one crop pasted into
+    another of the same batch); the crops underneath are the ones the same seed gives without it, since the policy draws from
+    a generator of its own.  last_params[i]["mix"] is (donor, force, keys), mix_tally() the device's count of samples and pixels
+    pasted per class.  NOT the reference's loader.  With None nothing changes: the random stream, the launches, the batches."""
 
     def __init__(self, dataset, batch, crop_size=512, rescale_range=(0.5, 2.0), fliplr=True, photometric=PHOTOMETRIC, seed=0,
-                 rank=0, world=1, aug=True, sampler=None):
+                 rank=0, world=1, aug=True, sampler=None, mix=None):
         unknown = [p for p in photometric if p not in PHOTOMETRIC]
         if unknown:
             raise ValueError(f"photometric: {unknown} not available; this loader applies {PHOTOMETRIC} only (saturation and hue go "
@@ -471,6 +536,17 @@ class AugmentedBatches:
                 raise ValueError("sampler: built over other frames than this rank's slice of the data set "
                                  "(RareClassSampler(stats, list(dist.shard(len(dataset), rank, world)), ...))")
             self._tally = torch.zeros((sampler.stats.n_class, 2), dtype=torch.int64, device=dataset.label.device)
+        self.mix = mix
+        if mix is not None:
+            if batch < 2:
+                raise ValueError(f"mix: ClassMix pastes between the samples of a batch, batch {batch} has no second one")
+            if not aug:
+                raise ValueError("mix: ClassMix works on augmented crops, aug=False has none")
+            if mix.classes == "wanted" and sampler is None:
+                raise ValueError("mix: classes='wanted' pastes the class a RareClassSampler drew the donor for: give sampler=")
+            if mix.rank != rank:
+                raise ValueError(f"mix: the ClassMix was seeded for rank {mix.rank}, this iterator is rank {rank}")
+            self._mix_tally = torch.zeros((mix.n_class, 2), dtype=torch.int64, device=dataset.label.device)
 
     def __len__(self):
         """batches per pass (drop_last)"""
@@ -493,6 +569,22 @@ class AugmentedBatches:
             raise RuntimeError("rcs_tally: this iterator has no sampler")
         return self._tally.cpu().numpy()
 
+    def mix_tally(self):
+        """-> (n_class, 2) int64 numpy array: per class the samples that had it pasted in so far and the pixels pasted.  One
+        readback of the device tally."""
+        if self.mix is None:
+            raise RuntimeError("mix_tally: this iterator has no ClassMix")
+        return self._mix_tally.cpu().numpy()
+
+    def _mix_arg(self, params, wanted=None):
+        """The augment(mix=) tuple of one batch, drawn from the policy's own generator; notes it in the samples' params."""
+        if self.mix is None:
+            return None
+        table = self.mix.draw(len(params), wanted)
+        for p, row in zip(params, table):
+            p["mix"] = (int(row[0]), int(row[1]), tuple(int(k) for k in row[2:]))
+        return table, self.mix.n_class, self.mix.min_pixels, self._mix_tally
+
     def _next_sampled(self):
         """One batch whose frames (and wanted classes) come from the sampler; the crop parameters are drawn as ever."""
         drawn = self.sampler.draw(self.batch)
@@ -505,7 +597,8 @@ class AugmentedBatches:
             want[b] = (c, self.sampler.crop_threshold(p["nw"] * p["nh"], w * h)) if c >= 0 else (-1, 0)
             p["want"] = (int(want[b, 0]), int(want[b, 1]))
         rec, tab = pack_records(idx, params, h, w)
-        out = self.dataset.augment(rec, tab, self.crop, self.crop, pick=True, want=want, tally=self._tally)[:4]
+        out = self.dataset.augment(rec, tab, self.crop, self.crop, pick=True, want=want, tally=self._tally,
+                                   mix=self._mix_arg(params, [c for _, c in drawn]))[:4]
         return (tuple(self.dataset.names[i] for i in idx),) + tuple(out)
 
     def __next__(self):
@@ -522,4 +615,4 @@ class AugmentedBatches:
         h, w = self.dataset.shape
         rec, tab = pack_records(idx, params, h, w)
         ch, cw = (self.crop, self.crop) if self.aug else (h, w)
-        return self.dataset.augment(rec, tab, ch, cw, pick=self.aug)[:4]
+        return self.dataset.augment(rec, tab, ch, cw, pick=self.aug, mix=self._mix_arg(params))[:4]

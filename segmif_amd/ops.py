@@ -1564,3 +1564,63 @@ def label_stats(label):
     fn = "segmif_label_stats_u8" if label.dtype == torch.uint8 else "segmif_label_stats_i64"
     _lib.check(getattr(_lib.load(), fn)(label.data_ptr(), N, label.shape[1] * label.shape[2], counts.data_ptr(), _stream()), fn)
     return counts
+
+
+MIX_SEL_WORDS = 8
+
+
+def check_mix_table(table, B, n_class):
+    """Host-side check of a ClassMix table (it lives on the device when the kernels read it): (B, 2 + n_class) integers, rows
+    (donor, force, key[0..n_class-1]) with the donor in 0..B-1, force in -1..n_class-1 and the keys a permutation of
+    0..n_class-1 -> (B, 2 + n_class) int32 numpy array."""
+    import numpy as np
+    if not 1 <= n_class <= 255 or B < 1:
+        raise ValueError(f"class_mix: n_class {n_class} outside 1..255 or B {B} < 1 (SEGMIF_EINVAL)")
+    t = np.asarray(table)
+    if t.ndim != 2 or t.shape != (B, 2 + n_class) or t.dtype.kind not in "iu":
+        raise ValueError(f"class_mix: the table must be ({B}, {2 + n_class}) integers (donor, force, {n_class} keys), got {t.dtype} {t.shape}")
+    if (t[:, 0] < 0).any() or (t[:, 0] >= B).any():
+        raise ValueError(f"class_mix: a donor lies in 0..{B - 1}, got {t[:, 0].tolist()}")
+    if (t[:, 1] < -1).any() or (t[:, 1] >= n_class).any():
+        raise ValueError(f"class_mix: force is -1 (half of the present classes) or a class in 0..{n_class - 1}, got {t[:, 1].tolist()}")
+    if not (np.sort(t[:, 2:], axis=1) == np.arange(n_class)).all():
+        raise ValueError(f"class_mix: the keys of a row must be a permutation of 0..{n_class - 1}")
+    return np.ascontiguousarray(t, dtype=np.int32)
+
+
+def class_mix(ir3, vis3, mask3, label, table, n_class=9, min_pixels=0, tally=None):
+    """ClassMix on an augmented batch (the rule: include/segmif_hip.h, segmif_class_mix_select): receiver b takes, from crop
+    donor[b] of the SAME, unmixed batch, the pixels of the selected classes - half of the classes present in the donor (those
+    with more than min_pixels pixels), the ones with the smallest keys, or the one class `force` - in every plane and in the
+    label, bit for bit.  ir3, vis3, mask3 (B, 3, h, w) fp32, label (B, h, w) int64, w % 4 == 0.  table: (B, 2 + n_class) rows
+    (donor, force, keys), either a host array / list, which is checked and uploaded here, or an int32 device tensor whose values
+    the caller has passed through check_mix_table.  tally: None or an (n_class, 2) int64 device tensor that accumulates (samples
+    that selected the class, pixels pasted).  Three launches on the current stream (label_stats, select, apply), no
+    synchronisation.  -> (ir3', vis3', mask3', label', sel (B, 8) int32, pasted (B,) int64), new tensors.  NOT the reference's
+    loader."""
+    _req_u8(label, "label", dtype=torch.int64)
+    if label.dim() != 3 or label.numel() < 1:
+        raise RuntimeError(f"class_mix: label must be a non-empty (B, h, w) int64 tensor, got {tuple(label.shape)}")
+    B, h, w = label.shape
+    if w % 4:
+        raise RuntimeError(f"class_mix: the width must be a multiple of 4 (16-byte accesses), got {w}")
+    if not 1 <= n_class <= 255 or min_pixels < 0:
+        raise ValueError(f"class_mix: n_class {n_class} outside 1..255 or min_pixels {min_pixels} < 0 (SEGMIF_EINVAL)")
+    for t, name in ((ir3, "ir3"), (vis3, "vis3"), (mask3, "mask3")):
+        _req_u8(t, name, (B, 3, h, w), dtype=torch.float32)
+    if not isinstance(table, torch.Tensor) or not table.is_cuda:
+        table = torch.from_numpy(check_mix_table(table.numpy() if isinstance(table, torch.Tensor) else table, B, n_class)).to(label.device)
+    _req_u8(table, "table", (B, 2 + n_class), dtype=torch.int32)
+    if tally is not None:
+        _req_u8(tally, "tally", (n_class, 2), dtype=torch.int64)
+    lib = _lib.load()
+    counts = label_stats(label)
+    sel = torch.empty((B, MIX_SEL_WORDS), device=label.device, dtype=torch.int32)
+    pasted = torch.empty(B, device=label.device, dtype=torch.int64)
+    _lib.check(lib.segmif_class_mix_select(counts.data_ptr(), table.data_ptr(), B, n_class, int(min_pixels), sel.data_ptr(), pasted.data_ptr(),
+                                           tally.data_ptr() if tally is not None else None, _stream()), "segmif_class_mix_select")
+    out = tuple(torch.empty_like(t) for t in (ir3, vis3, mask3, label))
+    _lib.check(lib.segmif_class_mix_apply_f32(ir3.data_ptr(), vis3.data_ptr(), mask3.data_ptr(), label.data_ptr(), table.data_ptr(),
+                                              sel.data_ptr(), B, h, w, n_class, *(t.data_ptr() for t in out), _stream()),
+               "segmif_class_mix_apply_f32")
+    return out + (sel, pasted)

@@ -16,7 +16,7 @@ segmif_amd.data makes on the device (main() below; one process, one GPU).  --seg
 (make_seg_loss): the reference's CE by default, or OHEM / focal / NormalLoss / class-weighted CE on csrc/seg_objective.hip.
 --seg-region adds a region term to it (make_seg_region): Lovasz-Softmax or soft Dice on csrc/region_objective.hip.
 --ema-decay keeps an exponential moving average of the weights in the optimizer step (csrc/weight_ema.hip) and validates and
-writes the AVERAGED weights.
+writes the AVERAGED weights.  --class-mix pastes classes between the crops of a batch (ClassMix, csrc/class_mix.hip).
 """
 import argparse
 import contextlib
@@ -351,6 +351,21 @@ class _RcsLog:
         return " rcs drawn/hit " + (" ".join(f"{c}:{int(d[c, 0])}/{int(d[c, 1])}" for c in range(len(d)) if d[c, 0]) or "none")
 
 
+class _MixLog:
+    """What a log line adds under ClassMix: ONE mix_tally() readback per line - per class the samples that had it pasted in and
+    the pixels pasted, since the previous line.  Nothing for a loader without a ClassMix."""
+
+    def __init__(self, batches):
+        self.batches, self.last = batches, 0
+
+    def line(self):
+        if self.batches.mix is None:
+            return ""
+        now = self.batches.mix_tally()
+        d, self.last = now - self.last, now
+        return " mix sel/px " + (" ".join(f"{c}:{int(d[c, 0])}/{int(d[c, 1])}" for c in range(len(d)) if d[c, 0]) or "none")
+
+
 def _miou(seg, fus, val, batch):
     """mIoU of the pair forward (fusion net -> segmentation net) over a DeviceDataset, through segmif_amd.evaluate.Evaluator"""
     from .evaluate import Evaluator
@@ -437,6 +452,18 @@ def main(argv=None):
                     "(0, 1]; the others walk the split in order (default 1.0)" + ours)
     ap.add_argument("--rcs-phases", choices=("seg", "fusion", "both"), help="with --rare-class-sampling: the phases whose loader "
                     "samples (default seg)")
+    ap.add_argument("--class-mix", action="store_true", help="ClassMix (Olsson et al. 2021; the mixing step of DAFormer): with "
+                    "probability P a sample of a batch receives, from another sample of the same batch, the pixels of half of the "
+                    "classes present in that sample's crop, in every image and in the label, on the device.  Off by default.  This "
+                    "project's addition, NOT the reference's loader")
+    ap.add_argument("--class-mix-prob", type=float, metavar="P", help="with --class-mix: the probability that a sample is mixed, in "
+                    "(0, 1] (default 0.5, this project's choice: DAFormer mixes every sample)")
+    ap.add_argument("--class-mix-min-pixels", type=int, metavar="N", help="with --class-mix: a class is present in a donor crop when "
+                    "the crop holds more than N pixels of it (default 0)")
+    ap.add_argument("--class-mix-classes", choices=("half", "wanted"), help="with --class-mix: paste half of the donor's present "
+                    "classes (default), or the one class --rare-class-sampling drew the donor for")
+    ap.add_argument("--class-mix-phases", choices=("seg", "fusion", "both"), help="with --class-mix: the phases whose batches are "
+                    "mixed (default seg)")
     ap.add_argument("--seg-region", choices=SEG_REGIONS, help="add a region objective to whatever --seg-loss builds, for the "
                     "SEGMENTATION phase only: lovasz is Lovasz-Softmax (the convex surrogate of the Jaccard index, the batch as one set), "
                     "dice the soft Dice loss.  This project's addition, NOT the reference's objective: its train.py trains on CE alone")
@@ -483,6 +510,24 @@ def main(argv=None):
         ap.error(f"--rcs-min-crop-ratio {args.rcs_min_crop_ratio}: must be a finite number >= 0")
     if args.rcs_fraction is not None and not 0.0 < args.rcs_fraction <= 1.0:
         ap.error(f"--rcs-fraction {args.rcs_fraction}: must lie in (0, 1]")
+    for flag, value in (("--class-mix-prob", args.class_mix_prob), ("--class-mix-min-pixels", args.class_mix_min_pixels),
+                        ("--class-mix-classes", args.class_mix_classes), ("--class-mix-phases", args.class_mix_phases)):
+        if value is not None and not args.class_mix:
+            ap.error(f"{flag} belongs to --class-mix, which is not given")
+    if args.class_mix_prob is not None and not 0.0 < args.class_mix_prob <= 1.0:
+        ap.error(f"--class-mix-prob {args.class_mix_prob}: must lie in (0, 1]")
+    if args.class_mix_min_pixels is not None and args.class_mix_min_pixels < 0:
+        ap.error(f"--class-mix-min-pixels {args.class_mix_min_pixels}: must be >= 0")
+    mix_phases = {"seg": ("seg",), "fusion": ("fusion",), "both": ("seg", "fusion")}[args.class_mix_phases or "seg"] if args.class_mix else ()
+    if args.class_mix and args.class_mix_classes == "wanted":
+        sampled = {"seg": ("seg",), "fusion": ("fusion",), "both": ("seg", "fusion")}[args.rcs_phases or "seg"] if args.rare_class_sampling else ()
+        missing = [ph for ph in mix_phases if ph not in sampled]
+        if missing:
+            ap.error(f"--class-mix-classes wanted pastes the class --rare-class-sampling drew the donor for: the {', '.join(missing)} "
+                     "phase has no rare-class sampling (--rare-class-sampling, --rcs-phases)")
+    if args.class_mix and args.samples_per_gpu < 4:
+        ap.error(f"--class-mix with --samples-per-gpu {args.samples_per_gpu}: the loaders' batch is half of it and mixing needs two samples, "
+                 "give at least 4")
     if not 0.0 <= args.label_smoothing < 1.0:
         ap.error(f"--label-smoothing {args.label_smoothing}: must lie in [0, 1)")
     if args.label_smoothing and args.seg_loss not in ("ce", "weighted"):
@@ -523,7 +568,7 @@ def main(argv=None):
     if args.backbone == "mit_b0":
         ap.error("--backbone mit_b0: Fusion_Network3_ac takes 64/128-channel segmentation features, mit_b0 gives 32/64")
     from .core import Fusion_Network3_ac, Network3
-    from .data import AugmentedBatches, DeviceDataset, PairFolder, RareClassSampler, synthetic_pairs
+    from .data import AugmentedBatches, ClassMix, DeviceDataset, PairFolder, RareClassSampler, synthetic_pairs
 
     torch.manual_seed(args.seed)
     if args.synthetic is not None:
@@ -612,10 +657,18 @@ def main(argv=None):
               + "; sampling probability: " + " ".join(f"{c}:{probe.prob[c]:.4f}" for c in probe.classes)
               + (f"; dropped (no frame with more than {rcs_kw['min_pixels']} pixels): {', '.join(map(str, probe.dropped))}"
                  if probe.dropped else "; no class dropped"))
+    mix_kw = None
+    if args.class_mix:
+        mix_kw = dict(prob=0.5 if args.class_mix_prob is None else args.class_mix_prob, classes=args.class_mix_classes or "half",
+                      min_pixels=0 if args.class_mix_min_pixels is None else args.class_mix_min_pixels, n_class=n_class)
+        print(f"[train] --class-mix ({', '.join(f'{k} {v}' for k, v in mix_kw.items())}; phases {', '.join(mix_phases)}): this "
+              "project's addition, NOT the reference's loader (its train.py mixes nothing): classes of one crop of a batch are pasted "
+              "into another, images and label alike")
 
     def loader(dataset, phase, seed, **kw):
         sampler = RareClassSampler(stats, range(len(dataset)), seed=seed, **rcs_kw) if phase in rcs_phases else None
-        return AugmentedBatches(dataset, seed=seed, sampler=sampler, **loader_kw, **kw)
+        mix = ClassMix(seed=seed, **mix_kw) if phase in mix_phases else None
+        return AugmentedBatches(dataset, seed=seed, sampler=sampler, mix=mix, **loader_kw, **kw)
     best, wrote_seg, opt = None, False, None
     fusion_loss = make_fusion_loss(args.fusion_loss) if args.fusion_loss is not None else None
     if fusion_loss is not None:
@@ -633,14 +686,14 @@ def main(argv=None):
                                 iter_=iter_, fusion_loss=fusion_loss)
         glog = _GuardLog(trainer.opt, [("fusion_net", fus)], args.max_consecutive_skips) if guarded else None
         batches = loader(train_set, "fusion", args.seed + 2 * iter_)
-        rlog = _RcsLog(batches)
+        rlog, mlog = _RcsLog(batches), _MixLog(batches)
         n_fus = args.fusion_iters if args.fusion_iters is not None else (6000 if iter_ == 1 else 4000)
         for n in range(n_fus):
             _, ir3, vis3, mask3, label = next(batches)
             loss = trainer.step(ir3, vis3, mask3, label)
             if (n + 1) % args.log_iters == 0 or n + 1 == n_fus:
                 print(f"[train] round {iter_} fusion iter {n + 1}/{n_fus}: loss {float(loss):.6f}" + (glog.line() if guarded else "")
-                      + rlog.line())
+                      + rlog.line() + mlog.line())
                 if guarded:
                     glog.check()
             if (n + 1) % 500 == 0:
@@ -661,14 +714,14 @@ def main(argv=None):
             print(f"[train] initial mIoU {best:.4f}")
         glog = _GuardLog(opt, [("seg_net", seg)], args.max_consecutive_skips) if guarded else None
         batches = loader(fused_set, "seg", args.seed + 2 * iter_ + 1, photometric=())
-        rlog = _RcsLog(batches)
+        rlog, mlog = _RcsLog(batches), _MixLog(batches)
         n_seg = args.seg_iters if args.seg_iters is not None else 10000
         for n in range(n_seg):
             _, _, fused3, _, label = next(batches)
             loss = seg_train_step(seg, opt, fused3, label, seg_crit)
             if (n + 1) % args.log_iters == 0 or n + 1 == n_seg:
                 print(f"[train] round {iter_} segmentation iter {n + 1}/{n_seg}: lr {opt.param_groups[0]['lr']:.3e} loss {float(loss):.6f}"
-                      + (glog.line() if guarded else "") + rlog.line())
+                      + (glog.line() if guarded else "") + rlog.line() + mlog.line())
                 if guarded:
                     glog.check()
             if (n + 1) % 1000 == 0 or n + 1 == n_seg:
