@@ -788,14 +788,17 @@ int segmif_softmax_ce_blocks(int64_t rows);
 int segmif_softmax_ce_f32(const float* logits, const int64_t* labels, float* dlogits, double* partial,
                           int64_t rows, int C, int ld, int ldd, int ignore_index, void* stream);
 
-/* input gradient of a strided convolution (overlap patch embed, sr conv); wd = weight as [tap][n][c] */
-int segmif_conv_dgrad_strided_f32(const float* dy, const float* wd, float* dx, int B, int H, int W, int Cin, int N,
-                                  int KH, int KW, int stride, int pad, int OH, int OW, int lddy, int lddx, void* stream);
+/* input gradient of a strided convolution of any dilation (gather form, vector ALU); wd = weight as [tap][n][c]:
+ * dx[iy][ix] sums the taps with (iy + pad - ky dil) and (ix + pad - kx dil) multiples of the stride.  The training path
+ * takes it for stride > 1 with dil > 1 only (dilation 1: GEMM + segmif_col2im_f32 below). */
+int segmif_conv_dgrad_strided_dil_f32(const float* dy, const float* wd, float* dx, int B, int H, int W, int Cin, int N,
+                                      int KH, int KW, int stride, int pad, int dil, int OH, int OW, int lddy, int lddx,
+                                      void* stream);
 
 /* second half of the same gradient computed as GEMM + gather: cols (B, OH, OW, k*k*C) = dY . W^T with columns ordered
  * (ky, kx, c) -> dx (B, H, W, C), dx[y][x] = sum of the taps ky = (y + pad) mod stride (+ stride ..), likewise kx, read from
- * output pixel ((y + pad - ky) / stride, (x + pad - kx) / stride).  Replaces the scalar kernel above wherever the GEMM's
- * scratch (rows x k*k*C floats) is affordable (every strided conv of the path: overlap patch embeds). */
+ * output pixel ((y + pad - ky) / stride, (x + pad - kx) / stride).  Replaces the scalar kernel above at dilation 1
+ * (every strided conv of the networks: overlap patch embeds, sr convs). */
 int segmif_col2im_f32(const float* cols, float* dx, int B, int H, int W, int C, int k, int stride, int pad, int OH, int OW,
                       void* stream);
 

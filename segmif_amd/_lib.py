@@ -267,7 +267,7 @@ SIGNATURES = {
     "segmif_softmax_ce_blocks": (c_int, [c_int64]),
     "segmif_softmax_ce_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int,
                                       c_void_p]),
-    "segmif_conv_dgrad_strided_f32": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 13 + [c_void_p]),
+    "segmif_conv_dgrad_strided_dil_f32": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 14 + [c_void_p]),
     "segmif_col2im_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 9 + [c_void_p]),
     "segmif_bn_colstats_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
                                        c_void_p]),

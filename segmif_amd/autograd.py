@@ -3,7 +3,8 @@ only records the graph.  Layout conventions as in ops.py (NHWC / tokens, fp32).
 
 Backward building blocks
   input gradients  : segmif_igemm_f32 with transposed (linear) / rotated+swapped (stride-1 conv)
-                     weights; segmif_conv_dgrad_strided_f32 for strided convs
+                     weights; GEMM + segmif_col2im_f32 for strided convs (segmif_conv_dgrad_strided_dil_f32 when they
+                     are dilated as well)
   weight gradients : segmif_wgrad_f32 (fp32 MFMA over the row dimension, deterministic 2-pass)
   bias gradients   : segmif_colsum_f32
   the rest         : LayerNorm / dwconv+GELU / bilinear / row-softmax / cross-entropy kernels
@@ -136,7 +137,9 @@ def conv_wgrad(x, dy, w_shape, k, stride, pad, dil, want_bias=False, amax=None):
         d.wgrad_dy_amax, d.wgrad_dy_amax_n = ys.data_ptr(), ys.numel()
     dw = torch.empty(tuple(w_shape), device=x.device, dtype=torch.float32)
     db = _bias_out(want_bias, N, x)
-    _wgrad(d, dy, ldy, dw, db=db)
+    # (a 1x1 stride-1 unpadded conv is a dense problem to the kernel, which then writes dw[n][k] at n * sn + k * sk: the row
+    # pitch of the (N, Cin, 1, 1) tensor; every other geometry is written in OIHW order and ignores the two strides)
+    _wgrad(d, dy, ldy, dw, sn=k * k * cin, sk=1, db=db)
     return (dw, db) if want_bias else dw
 
 
@@ -282,12 +285,12 @@ class ConvFn(torch.autograd.Function):
                 dx = torch.empty((B, H, W, cin), device=x.device, dtype=torch.float32)
                 _lib.check(_lib.load().segmif_col2im_f32(cols.data_ptr(), dx.data_ptr(), B, H, W, cin, k, stride, pad, OH, OW,
                                                          _stream()), "segmif_col2im_f32")
-            else:
+            else:  # strided and dilated: the gather kernel that knows both
                 wd = w.permute(2, 3, 0, 1).contiguous()  # [ky][kx][n][c]
                 dx = torch.empty((B, H, W, cin), device=x.device, dtype=torch.float32)
-                _lib.check(_lib.load().segmif_conv_dgrad_strided_f32(
-                    dz.data_ptr(), wd.data_ptr(), dx.data_ptr(), B, H, W, cin, N, k, k, stride, pad, dz.shape[1],
-                    dz.shape[2], N, cin, _stream()), "segmif_conv_dgrad_strided_f32")
+                _lib.check(_lib.load().segmif_conv_dgrad_strided_dil_f32(
+                    dz.data_ptr(), wd.data_ptr(), dx.data_ptr(), B, H, W, cin, N, k, k, stride, pad, dil, dz.shape[1],
+                    dz.shape[2], rows_view(dz, "dz")[2], cin, _stream()), "segmif_conv_dgrad_strided_dil_f32")
         want_b = ctx.has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1]:
             r = conv_wgrad(x, dz, w.shape, k, stride, pad, dil, want_bias=want_b, amax=(xslot, zslot) if zslot is not None else None)

@@ -457,15 +457,16 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Input gradient of a STRIDED convolution (overlap patch embed k7s4 / k3s2, sr conv k = s):
-//   dx[b][iy][ix][c] = sum over taps (ky,kx) with (iy + pad - ky) % s == 0, (ix + pad - kx) % s == 0
+// Input gradient of a STRIDED convolution of any dilation (the dilation-1 geometries - overlap patch embed k7s4 / k3s2,
+// sr conv k = s - go through GEMM + col2im; this kernel is what is left: stride > 1 together with dilation > 1):
+//   dx[b][iy][ix][c] = sum over taps (ky,kx) with (iy + pad - ky dil) % s == 0, (ix + pad - kx dil) % s == 0
 //                      of sum_n dy[b][oy][ox][n] * W[n][c][ky][kx]
-// wd is the weight repacked to [tap][n][c].  VALU kernel: these layers are ~3 % of the FLOPs.
+// wd is the weight repacked to [tap][n][c].  VALU kernel: no layer of the networks has this geometry.
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void conv_dgrad_strided_kernel(const float* __restrict__ dy, const float* __restrict__ wd,
                                                                  float* __restrict__ dx, int H, int W, int Cin, int N, int KH,
-                                                                 int KW, int stride, int pad, int OH, int OW, int lddy,
-                                                                 int lddx, long long total) {
+                                                                 int KW, int stride, int pad, int dil, int OH, int OW,
+                                                                 int lddy, int lddx, long long total) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= total) return;
   const int c = (int)(idx % Cin);
@@ -476,12 +477,12 @@ __global__ __launch_bounds__(256) void conv_dgrad_strided_kernel(const float* __
   const long long b = pix / H;
   float acc = 0.f;
   for (int ky = 0; ky < KH; ++ky) {
-    const int ty = iy + pad - ky;
+    const int ty = iy + pad - ky * dil;
     if (ty < 0 || ty % stride) continue;
     const int oy = ty / stride;
     if (oy >= OH) continue;
     for (int kx = 0; kx < KW; ++kx) {
-      const int tx = ix + pad - kx;
+      const int tx = ix + pad - kx * dil;
       if (tx < 0 || tx % stride) continue;
       const int ox = tx / stride;
       if (ox >= OW) continue;
@@ -806,13 +807,15 @@ extern "C" int segmif_softmax_ce_f32(const float* logits, const int64_t* labels,
   return (int)hipGetLastError();
 }
 
-extern "C" int segmif_conv_dgrad_strided_f32(const float* dy, const float* wd, float* dx, int B, int H, int W, int Cin, int N,
-                                             int KH, int KW, int stride, int pad, int OH, int OW, int lddy, int lddx,
-                                             void* stream) {
-  if (!dy || !wd || !dx || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || N <= 0 || stride <= 0) return SEGMIF_EINVAL;
+extern "C" int segmif_conv_dgrad_strided_dil_f32(const float* dy, const float* wd, float* dx, int B, int H, int W, int Cin,
+                                                 int N, int KH, int KW, int stride, int pad, int dil, int OH, int OW, int lddy,
+                                                 int lddx, void* stream) {
+  if (!dy || !wd || !dx || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || N <= 0 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0 ||
+      dil <= 0 || OH <= 0 || OW <= 0 || lddy < N || lddx < Cin)
+    return SEGMIF_EINVAL;
   const long long total = (long long)B * H * W * Cin;
   hipLaunchKernelGGL(conv_dgrad_strided_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     dy, wd, dx, H, W, Cin, N, KH, KW, stride, pad, OH, OW, lddy, lddx, total);
+                     dy, wd, dx, H, W, Cin, N, KH, KW, stride, pad, dil, OH, OW, lddy, lddx, total);
   return (int)hipGetLastError();
 }
 
