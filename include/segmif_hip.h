@@ -741,6 +741,27 @@ int segmif_class_mix_apply_f32(const float* ir3, const float* vis3, const float*
                                const int32_t* sel, int B, int h, int w, int n_class, float* ir3_out, float* vis3_out,
                                float* mask3_out, int64_t* label_out, void* stream);
 
+/* Pseudo-labels for self-training (the EMA teacher of DAFormer, Hoyer et al. 2022; mean teacher, Tarvainen & Valpola 2017), in one
+ * pass from the teacher's NHWC logits x (B, IH, IW, C), pixel pitch ldx >= C, to full resolution (csrc/pseudo_label.hip).  NOT the
+ * reference's training, which uses labelled frames only.  The (B, OH, OW, C) resized logits are never written.  The rule, per
+ * output pixel:
+ *   - v_c is the bilinear resize of channel c (align_corners = False), segmif_bilinear_argmax_i32's expression: source coordinate
+ *     max(0, s (dst + 0.5) - 0.5) with s = in / out, and hy (hx p00 + lx p01) + ly (hx p10 + lx p11).
+ *   - label = argmax_c v_c; ties go to the lowest index.  The labels are segmif_bilinear_argmax_i32's.
+ *   - p_max = 1 / sum_c exp(v_c - v_max) in float32: the softmax probability of the label.
+ *   - The pixel is confident iff p_max > tau.  The comparison is strict; a NaN p_max (a NaN or infinite logit among the four
+ *     source pixels) is not confident.
+ *   - labels (B, OH, OW) int64: the argmax everywhere when below_ignore == 0 (DAFormer: the weight carries the confidence);
+ *     when below_ignore != 0 a pixel that is not confident holds ignore_index instead (per-pixel thresholding, FixMatch style).
+ *   - conf_or_null (B, OH, OW) float32 receives p_max; NULL: not written.
+ *   - count (B,) int64: the confident pixels of each sample.  The call zeroes it on `stream` first.  Exact: a ballot and popcount
+ *     per wave, one partial per block, one integer atomic per block; integer sums do not depend on their order, so the count is
+ *     the same in every run.  count[b] / (OH OW) is DAFormer's per-image pseudo_weight.
+ * No host synchronisation, no floating-point atomics: capturable in a hipGraph.  SEGMIF_EINVAL before any launch: a null pointer
+ * (conf_or_null may be null), a size < 1, C outside 1..32, ldx < C, B or OH > 65535, tau NaN or outside [0, 1]. */
+int segmif_pseudo_label_f32(const float* x, int64_t* labels, float* conf_or_null, int64_t* count, int B, int IH, int IW, int OH,
+                            int OW, int C, int ldx, float tau, int below_ignore, int ignore_index, void* stream);
+
 /* ----------------------------------------------------------------------------------------------
  * Training path (backward of the ops above; autograd in the reference: loss.backward() at
  * train.py:226, :384).  Contractions reuse segmif_igemm_f32 (input gradients, with transposed /
@@ -936,6 +957,24 @@ int segmif_seg_objective_f32(const SegmifSegObjective* desc, const float* logits
 int segmif_seg_objective_bwd_f32(const SegmifSegObjective* desc, const float* logits, const int64_t* labels,
                                  const float* class_weight, const void* workspace, const float* record4, const float* upstream,
                                  float* dlogits, int64_t rows, int C, int ld, int ldd, void* stream);
+/* The same pair with a weight per pixel and / or per sample (self-training: the confidence of a pseudo-label).  NOT the
+ * reference's objective.  pixel_weight: `rows` device floats, NULL: all 1; sample_weight: rows / rows_per_sample device floats,
+ * NULL: all 1; row i belongs to sample i / rows_per_sample.  With u_i = pixel_weight[i] * sample_weight[i / rows_per_sample] the
+ * per-pixel loss becomes u_i l_i, l_i exactly as above (gamma, label smoothing, class weights, the ignore rule).  THE DENOMINATORS
+ * DO NOT CONTAIN u: SEGMIF_SEG_MEAN_VALID divides by sum_valid w_y, SEGMIF_SEG_MEAN_ALL by rows - what mmsegmentation / DAFormer
+ * compute with a pixel weight, (loss * weight).mean().  A uniform weight q therefore scales value and gradient by q; it does not
+ * cancel.  The weights are data: they are read as given (any float; 0 gives the row an all-zero gradient) and receive no
+ * gradient.  With both weights NULL the calls ARE the unweighted ones, and an all-ones weight gives their bits (a product with
+ * 1.0f is exact).  Hand the backward the weights the forward had.  SEGMIF_EINVAL in addition to the cases above:
+ * SEGMIF_SEG_OHEM with a weight; with sample_weight given, rows_per_sample < 1 or rows % rows_per_sample != 0. */
+int segmif_seg_objective_weighted_f32(const SegmifSegObjective* desc, const float* logits, const int64_t* labels,
+                                      const float* class_weight, const float* pixel_weight, const float* sample_weight,
+                                      int64_t rows_per_sample, void* workspace, float* record4, int64_t rows, int C, int ld,
+                                      void* stream);
+int segmif_seg_objective_weighted_bwd_f32(const SegmifSegObjective* desc, const float* logits, const int64_t* labels,
+                                          const float* class_weight, const float* pixel_weight, const float* sample_weight,
+                                          int64_t rows_per_sample, const void* workspace, const float* record4, const float* upstream,
+                                          float* dlogits, int64_t rows, int C, int ld, int ldd, void* stream);
 
 /* The region objectives that go with them (csrc/region_objective.hip): Lovasz-Softmax (Berman et al. 2018, the batch as one set)
  * and soft Dice over the same rows (rows x C, pitch ld >= C, C <= 32, int64 labels).  Neither is the reference's.  A row is valid

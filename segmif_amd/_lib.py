@@ -290,6 +290,11 @@ SIGNATURES = {
                                          c_int, c_void_p]),
     "segmif_seg_objective_bwd_f32": (c_int, [POINTER(SegmifSegObjective), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
+    "segmif_seg_objective_weighted_f32": (c_int, [POINTER(SegmifSegObjective), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                                  c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "segmif_seg_objective_weighted_bwd_f32": (c_int, [POINTER(SegmifSegObjective), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                      c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
+                                                      c_void_p]),
     "segmif_region_objective_workspace_bytes": (c_int64, [c_int64, c_int, c_int]),
     "segmif_region_objective_f32": (c_int, [POINTER(SegmifRegionObjective), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
                                             c_void_p]),
@@ -322,6 +327,8 @@ SIGNATURES = {
                                         c_int, c_int, c_void_p]),
     "segmif_argmax_nhwc_i32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "segmif_bilinear_argmax_i32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "segmif_pseudo_label_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                                        c_int, c_int, c_void_p]),
     "segmif_tta_vote_f32": (c_int, [POINTER(SegmifTtaView), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "segmif_resize_flip_nchw_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
 }

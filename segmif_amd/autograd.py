@@ -1530,6 +1530,42 @@ class SegObjectiveFn(torch.autograd.Function):
         return dlog, None, None, None
 
 
+class SegObjectiveWeightedFn(torch.autograd.Function):
+    """SegObjectiveFn with a weight per pixel and / or per sample (segmif_seg_objective_weighted_f32: the same kernels,
+    instantiated with the multiply; the denominators do not contain the weights).  The weights are data: no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight, desc, pixel_weight, sample_weight, rows_per_sample):
+        rows, C, ld = rows_view(logits, "logits")
+        lib = _lib.load()
+        nbytes = lib.segmif_seg_objective_workspace_bytes(rows, desc.reduction)
+        if nbytes <= 0:
+            raise RuntimeError(f"segmif_seg_objective_workspace_bytes refused rows = {rows}, reduction = {desc.reduction}")
+        ws = torch.empty((nbytes,), device=logits.device, dtype=torch.uint8)
+        rec = torch.empty((4,), device=logits.device, dtype=torch.float32)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        _lib.check(lib.segmif_seg_objective_weighted_f32(ctypes.byref(desc), logits.data_ptr(), labels.data_ptr(), ptr(weight),
+                                                         ptr(pixel_weight), ptr(sample_weight), rows_per_sample, ws.data_ptr(),
+                                                         rec.data_ptr(), rows, C, ld, _stream()), "segmif_seg_objective_weighted_f32")
+        ctx.save_for_backward(logits, labels, weight, pixel_weight, sample_weight, rec)
+        ctx.desc, ctx.rows_per_sample = desc, rows_per_sample
+        return rec[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, labels, weight, pixel_weight, sample_weight, rec = ctx.saved_tensors
+        rows, C, ld = rows_view(logits, "logits")
+        up = g.reshape(1).float().contiguous()
+        dlog = torch.empty(logits.shape, device=logits.device, dtype=torch.float32)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        _lib.check(_lib.load().segmif_seg_objective_weighted_bwd_f32(ctypes.byref(ctx.desc), logits.data_ptr(), labels.data_ptr(),
+                                                                     ptr(weight), ptr(pixel_weight), ptr(sample_weight),
+                                                                     ctx.rows_per_sample, None, rec.data_ptr(), up.data_ptr(),
+                                                                     dlog.data_ptr(), rows, C, ld, C, _stream()),
+                   "segmif_seg_objective_weighted_bwd_f32")
+        return dlog, None, None, None, None, None, None
+
+
 _REGION_KINDS = {"lovasz": 0, "dice": 1}
 _REGION_CLASSES = {"present": 0, "all": 1}
 
@@ -1622,10 +1658,37 @@ def _seg_rows_and_labels(logits_nhwc, labels, what):
     return rows, C, labels.detach().long().contiguous()
 
 
+def _seg_weights(pixel_weight, sample_weight, rows, reduction):
+    """(pixel_weight, sample_weight, rows_per_sample) as the weighted kernels take them: contiguous float32 device tensors with one
+    value per row / per sample.  Weights are data: one that requires grad is refused rather than silently detached."""
+    if reduction == "ohem":
+        raise ValueError("seg_objective: the OHEM reduction takes no pixel_weight / sample_weight (SEGMIF_EINVAL; not built)")
+    rows_per_sample = 1
+    for name, w in (("pixel_weight", pixel_weight), ("sample_weight", sample_weight)):
+        if w is None:
+            continue
+        _req(w, name)
+        if w.requires_grad:
+            raise RuntimeError(f"seg_objective: {name} requires grad, but the weights are data and receive no gradient; detach it")
+    if pixel_weight is not None:
+        if pixel_weight.numel() != rows:
+            raise RuntimeError(f"seg_objective: pixel_weight holds {pixel_weight.numel()} values for {rows} rows of logits")
+        pixel_weight = pixel_weight.contiguous()
+    if sample_weight is not None:
+        if sample_weight.dim() != 1 or sample_weight.numel() < 1 or rows % sample_weight.numel():
+            raise RuntimeError(f"seg_objective: sample_weight must be (B,) with B dividing the {rows} rows, got {tuple(sample_weight.shape)}")
+        rows_per_sample = rows // sample_weight.numel()
+        sample_weight = sample_weight.contiguous()
+    return pixel_weight, sample_weight, rows_per_sample
+
+
 def seg_objective(logits_nhwc, labels, gamma=0.0, label_smoothing=0.0, weight=None, ignore_index=255, reduction="mean", ohem_t=0.0,
-                  ohem_n_min=0):
+                  ohem_n_min=0, pixel_weight=None, sample_weight=None):
     """losses.SegObjective's value for NHWC logits (..., C) - a rows view, C <= 32 - and labels with one entry per row (any integer
-    type; converted to int64 on the device).  weight: (C,) float32 device class weights or None.  ohem_t = -log(thresh)."""
+    type; converted to int64 on the device).  weight: (C,) float32 device class weights or None.  ohem_t = -log(thresh).
+    pixel_weight: (B, H, W) or (rows,) float32, sample_weight: (B,) float32, both data (no gradient): the per-pixel loss is
+    multiplied by their product, the denominator of the reduction is not (include/segmif_hip.h, segmif_seg_objective_weighted_f32).
+    With both None this is the unweighted path, unchanged."""
     rows, C, labels = _seg_rows_and_labels(logits_nhwc, labels, "segmentation-objective")
     if weight is not None:
         weight = _req(weight, "class weights").detach().contiguous()
@@ -1635,7 +1698,10 @@ def seg_objective(logits_nhwc, labels, gamma=0.0, label_smoothing=0.0, weight=No
         raise ValueError(f"ohem_n_min = {ohem_n_min} outside 1..{rows} (the pixels of this batch); the reference's sort would index "
                          "out of range")
     desc = seg_objective_descriptor(gamma, label_smoothing, ignore_index, reduction, ohem_t, ohem_n_min)
-    return SegObjectiveFn.apply(logits_nhwc, labels, weight, desc)
+    if pixel_weight is None and sample_weight is None:
+        return SegObjectiveFn.apply(logits_nhwc, labels, weight, desc)
+    pixel_weight, sample_weight, rows_per_sample = _seg_weights(pixel_weight, sample_weight, rows, reduction)
+    return SegObjectiveWeightedFn.apply(logits_nhwc, labels, weight, desc, pixel_weight, sample_weight, rows_per_sample)
 
 
 def region_objective(logits_nhwc, labels, kind="lovasz", classes="present", ignore_index=255, smooth=1.0):

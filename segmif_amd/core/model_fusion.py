@@ -756,16 +756,28 @@ class Fusion_Network3_ac(nn.Module):
     planes16_fallbacks = 0  # forwards repeated on the bf16x6 kernels because the f16x3 range guard tripped
 
 
-def seg_criterion_loss(seg, label, criterion):
+def seg_criterion_loss(seg, label, criterion, pixel_weight=None, sample_weight=None):
     """criterion(bilinear-up(seg -> label size), label) for NHWC logits `seg` (ref :1095-1096, :241-244).  With the criterion
     train.py builds - nn.CrossEntropyLoss(ignore_index=...), mean reduction, no class weights - the whole chain (x4 bilinear,
     softmax-CE with ignore_index, their backward) runs in two HIP kernels.  A losses.SegObjective, or one of core/loss.py's OhemCELoss /
     SoftmaxFocalLoss / NormalLoss, which hold one, gets the bilinear kernel's NHWC output directly, and so does a
     losses.RegionObjective or a losses.SegLossSum (whose plain-CE base stays on ag.softmax_ce).  Any other criterion is the CALLER's code: it receives
     the up-sampled logits as an NCHW view of the HIP bilinear kernel's output (with its HIP backward) - (r6) no F.interpolate, no
-    aten op of this package's own on the way."""
+    aten op of this package's own on the way.
+    pixel_weight (B, H, W) / sample_weight (B,): float32 device data that weight the per-pixel loss (self-training; csrc/seg_objective.hip's
+    weighted entries, the denominators without the weights).  A plain nn.CrossEntropyLoss (mean, no class weights) is then routed
+    through SegObjective.from_criterion; a SegObjective / SegObjectiveLoss takes them as it is; everything else - RegionObjective,
+    SegLossSum, the OHEM reduction, a foreign criterion - raises a TypeError: not built.  Both None: the paths above, unchanged."""
     H, W = label.shape[1:]
     up = ag.bilinear(seg, H, W) if seg.requires_grad else ops.bilinear(seg, H, W)
+    if pixel_weight is not None or sample_weight is not None:
+        if isinstance(criterion, nn.CrossEntropyLoss) and criterion.weight is None and criterion.reduction == "mean":
+            criterion = losses.SegObjective.from_criterion(criterion)
+        if not isinstance(criterion, (losses.SegObjective, losses.SegObjectiveLoss)):
+            raise TypeError(f"seg_criterion_loss: pixel_weight / sample_weight with a {type(criterion).__name__}: weights are built for "
+                            "nn.CrossEntropyLoss (mean, no class weights), SegObjective and SegObjectiveLoss (not OHEM) only - not for "
+                            "RegionObjective, SegLossSum or a criterion of the caller's")
+        return criterion.forward_nhwc(up, label, pixel_weight, sample_weight)
     # the HIP CE kernel holds a row's logits in 32 registers; labels outside [0, C) other than ignore_index are
     # treated as ignored there (torch raises), so the data pipeline must already guarantee the range (train.py's does)
     if isinstance(criterion, nn.CrossEntropyLoss) and criterion.weight is None and criterion.reduction == "mean" \
@@ -840,9 +852,9 @@ class Network3(nn.Module):
         OH, OW = size if size is not None else (H, W)
         return ops.tta_vote(views, [f for _, _, f in plan], OH, OW, want_probs=return_probs)
 
-    def _loss(self, fused_seg1, label, criterion):
-        """CE(bilinear-up(seg_map), label) (ref :1090-1097): seg_criterion_loss below."""
-        return seg_criterion_loss(self._segment_nhwc(fused_seg1), label, criterion)
+    def _loss(self, fused_seg1, label, criterion, pixel_weight=None, sample_weight=None):
+        """CE(bilinear-up(seg_map), label) (ref :1090-1097): seg_criterion_loss above; pixel_weight / sample_weight as there."""
+        return seg_criterion_loss(self._segment_nhwc(fused_seg1), label, criterion, pixel_weight, sample_weight)
 
     def denoise_net_parameters(self):
         return self.denoise_net.parameters()

@@ -22,6 +22,9 @@
 // 16-byte aligned: a row of C = 9 is 36 bytes, per-thread row reads would not coalesce), each thread holds its row in registers.
 // Backward: one launch; recomputes the softmax, reads the saved l (OHEM), the record and the upstream gradient from device memory
 // and writes dlogits already scaled.
+// The weighted entry points (self-training: a confidence weight per pixel and / or per sample) instantiate the SAME two kernels
+// with WEIGHTED = true: the forward sums u_i l_i, the backward scales the pixel's share by u_i, u_i = pixel_weight[i] *
+// sample_weight[i / rows_per_sample] (either NULL: 1).  The denominators do not contain u.  WEIGHTED = false is the code as it was.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <stdint.h>
@@ -43,6 +46,9 @@ struct SegArgs {
   long long rows;
   int C, ld, vec, ignore_index, reduction;
   float gamma, eps, t;
+  const float* pixel_weight;   // WEIGHTED only; NULL: all 1
+  const float* sample_weight;  // WEIGHTED only; NULL: all 1
+  long long rows_per_sample;
 };
 
 struct Workspace {
@@ -133,6 +139,13 @@ __device__ __forceinline__ float pixel_loss(const SegArgs& a, const Row& R) {
 
 __device__ __forceinline__ bool is_valid(const SegArgs& a, long long lab) { return lab != a.ignore_index && lab >= 0 && lab < a.C; }
 
+// u_i of row r (weights are data: read as given, no gradient)
+__device__ __forceinline__ float row_weight(const SegArgs& a, long long r) {
+  const float pw = a.pixel_weight ? a.pixel_weight[r] : 1.f;
+  const float sw = a.sample_weight ? a.sample_weight[r / a.rows_per_sample] : 1.f;
+  return pw * sw;
+}
+
 // block-wide fixed-order sums of NV doubles per thread -> out[0 .. NV) by thread 0
 template <int NV>
 __device__ __forceinline__ void block_sums(double (&v)[NV], double (*red)[NPART], double* __restrict__ out) {
@@ -148,6 +161,7 @@ __device__ __forceinline__ void block_sums(double (&v)[NV], double (*red)[NPART]
   if (threadIdx.x < NV) out[threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
 }
 
+template <bool WEIGHTED>
 __global__ __launch_bounds__(ROWS) void seg_objective_fwd_kernel(SegArgs a, void* ws) {
   __shared__ __attribute__((aligned(16))) float tile[ROWS * PITCH];
   __shared__ unsigned hist[256];
@@ -167,6 +181,7 @@ __global__ __launch_bounds__(ROWS) void seg_objective_fwd_kernel(SegArgs a, void
       Row R;
       row_softmax(tile + threadIdx.x * PITCH, a.w, a.C, (int)lab, a.eps > 0.f, R);
       l = pixel_loss(a, R);
+      if constexpr (WEIGHTED) l *= row_weight(a, r0 + threadIdx.x);  // (the denominator below stays w_y)
       v[0] = (double)l;
       v[1] = (double)R.w_y;
     }
@@ -268,6 +283,7 @@ __global__ __launch_bounds__(256) void seg_objective_final_kernel(void* ws, long
   }
 }
 
+template <bool WEIGHTED>
 __global__ __launch_bounds__(ROWS) void seg_objective_bwd_kernel(SegArgs a, const void* ws, const float* __restrict__ record,
                                                                  const float* __restrict__ upstream, float* __restrict__ g, int ldd,
                                                                  int vec_out) {
@@ -286,6 +302,7 @@ __global__ __launch_bounds__(ROWS) void seg_objective_bwd_kernel(SegArgs a, cons
         const float l = carve(const_cast<void*>(ws), a.rows).l[r0 + threadIdx.x], kappa = record[2];
         s = l > kappa ? s : (l == kappa ? s * record[3] : 0.f);
       }
+      if constexpr (WEIGHTED) s *= row_weight(a, r0 + threadIdx.x);
     }
     if (s != 0.f) {  // (an ignored or unselected pixel gets exact zeros, whatever the coefficient)
       Row R;
@@ -335,7 +352,51 @@ bool make_args(const SegmifSegObjective* d, const float* logits, const int64_t* 
   a.vec = ld == C && aligned16(logits);
   a.ignore_index = d->ignore_index, a.reduction = d->reduction;
   a.gamma = d->gamma, a.eps = d->label_smoothing, a.t = d->ohem_t;
+  a.pixel_weight = a.sample_weight = nullptr, a.rows_per_sample = 1;
   return true;
+}
+
+// the weighted entries' extra arguments; false: refused.  Both NULL leaves `a` what make_args made: the unweighted kernels run.
+bool add_weights(SegArgs& a, const float* pixel_weight, const float* sample_weight, int64_t rows_per_sample) {
+  if (!pixel_weight && !sample_weight) return true;
+  if (a.reduction == SEGMIF_SEG_OHEM) return false;
+  if (sample_weight && (rows_per_sample < 1 || a.rows % rows_per_sample != 0)) return false;
+  a.pixel_weight = pixel_weight, a.sample_weight = sample_weight;
+  a.rows_per_sample = sample_weight ? rows_per_sample : 1;
+  return true;
+}
+
+int launch_forward(const SegArgs& a, unsigned n_min, void* workspace, float* record4, hipStream_t s) {
+  const long long rows = a.rows;
+  const dim3 grid((unsigned)num_blocks(rows)), block(ROWS);
+  if (a.reduction == SEGMIF_SEG_OHEM) {
+    const hipError_t e = hipMemsetAsync(workspace, 0, HEADER, s);
+    if (e != hipSuccess) return (int)e;
+  }
+  if (a.pixel_weight || a.sample_weight)
+    hipLaunchKernelGGL(seg_objective_fwd_kernel<true>, grid, block, 0, s, a, workspace);
+  else
+    hipLaunchKernelGGL(seg_objective_fwd_kernel<false>, grid, block, 0, s, a, workspace);
+  if (a.reduction == SEGMIF_SEG_OHEM) {
+    for (int pass = 0; pass < 4; ++pass) {
+      if (pass) hipLaunchKernelGGL(seg_objective_hist_kernel, grid, block, 0, s, workspace, rows, pass);
+      hipLaunchKernelGGL(seg_objective_scan_kernel, dim3(1), dim3(256), 0, s, workspace, rows, pass, n_min);
+    }
+    hipLaunchKernelGGL(seg_objective_above_kernel, grid, block, 0, s, workspace, rows);
+  }
+  hipLaunchKernelGGL(seg_objective_final_kernel, dim3(1), dim3(256), 0, s, workspace, rows, a.reduction, a.t, n_min, record4);
+  return (int)hipGetLastError();
+}
+
+int launch_backward(const SegArgs& a, const void* workspace, const float* record4, const float* upstream, float* dlogits, int ldd,
+                    hipStream_t s) {
+  const int vec_out = ldd == a.C && aligned16(dlogits);
+  const dim3 grid((unsigned)num_blocks(a.rows)), block(ROWS);
+  if (a.pixel_weight || a.sample_weight)
+    hipLaunchKernelGGL(seg_objective_bwd_kernel<true>, grid, block, 0, s, a, workspace, record4, upstream, dlogits, ldd, vec_out);
+  else
+    hipLaunchKernelGGL(seg_objective_bwd_kernel<false>, grid, block, 0, s, a, workspace, record4, upstream, dlogits, ldd, vec_out);
+  return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -350,23 +411,7 @@ extern "C" int segmif_seg_objective_f32(const SegmifSegObjective* desc, const fl
                                         void* stream) {
   SegArgs a;
   if (!workspace || !record4 || !make_args(desc, logits, labels, class_weight, rows, C, ld, a)) return SEGMIF_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid((unsigned)num_blocks(rows)), block(ROWS);
-  const unsigned n_min = (unsigned)desc->ohem_n_min;
-  if (a.reduction == SEGMIF_SEG_OHEM) {
-    const hipError_t e = hipMemsetAsync(workspace, 0, HEADER, s);
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL(seg_objective_fwd_kernel, grid, block, 0, s, a, workspace);
-  if (a.reduction == SEGMIF_SEG_OHEM) {
-    for (int pass = 0; pass < 4; ++pass) {
-      if (pass) hipLaunchKernelGGL(seg_objective_hist_kernel, grid, block, 0, s, workspace, (long long)rows, pass);
-      hipLaunchKernelGGL(seg_objective_scan_kernel, dim3(1), dim3(256), 0, s, workspace, (long long)rows, pass, n_min);
-    }
-    hipLaunchKernelGGL(seg_objective_above_kernel, grid, block, 0, s, workspace, (long long)rows);
-  }
-  hipLaunchKernelGGL(seg_objective_final_kernel, dim3(1), dim3(256), 0, s, workspace, (long long)rows, a.reduction, a.t, n_min, record4);
-  return (int)hipGetLastError();
+  return launch_forward(a, (unsigned)desc->ohem_n_min, workspace, record4, (hipStream_t)stream);
 }
 
 extern "C" int segmif_seg_objective_bwd_f32(const SegmifSegObjective* desc, const float* logits, const int64_t* labels,
@@ -375,8 +420,27 @@ extern "C" int segmif_seg_objective_bwd_f32(const SegmifSegObjective* desc, cons
   SegArgs a;
   if (!record4 || !upstream || !dlogits || ldd < C || !make_args(desc, logits, labels, class_weight, rows, C, ld, a)) return SEGMIF_EINVAL;
   if (a.reduction == SEGMIF_SEG_OHEM && !workspace) return SEGMIF_EINVAL;
-  const int vec_out = ldd == C && aligned16(dlogits);
-  hipLaunchKernelGGL(seg_objective_bwd_kernel, dim3((unsigned)num_blocks(rows)), dim3(ROWS), 0, (hipStream_t)stream, a, workspace,
-                     record4, upstream, dlogits, ldd, vec_out);
-  return (int)hipGetLastError();
+  return launch_backward(a, workspace, record4, upstream, dlogits, ldd, (hipStream_t)stream);
+}
+
+extern "C" int segmif_seg_objective_weighted_f32(const SegmifSegObjective* desc, const float* logits, const int64_t* labels,
+                                                 const float* class_weight, const float* pixel_weight, const float* sample_weight,
+                                                 int64_t rows_per_sample, void* workspace, float* record4, int64_t rows, int C, int ld,
+                                                 void* stream) {
+  SegArgs a;
+  if (!workspace || !record4 || !make_args(desc, logits, labels, class_weight, rows, C, ld, a)) return SEGMIF_EINVAL;
+  if (!add_weights(a, pixel_weight, sample_weight, rows_per_sample)) return SEGMIF_EINVAL;
+  return launch_forward(a, (unsigned)desc->ohem_n_min, workspace, record4, (hipStream_t)stream);
+}
+
+extern "C" int segmif_seg_objective_weighted_bwd_f32(const SegmifSegObjective* desc, const float* logits, const int64_t* labels,
+                                                     const float* class_weight, const float* pixel_weight, const float* sample_weight,
+                                                     int64_t rows_per_sample, const void* workspace, const float* record4,
+                                                     const float* upstream, float* dlogits, int64_t rows, int C, int ld, int ldd,
+                                                     void* stream) {
+  SegArgs a;
+  if (!record4 || !upstream || !dlogits || ldd < C || !make_args(desc, logits, labels, class_weight, rows, C, ld, a)) return SEGMIF_EINVAL;
+  if (!add_weights(a, pixel_weight, sample_weight, rows_per_sample)) return SEGMIF_EINVAL;
+  if (a.reduction == SEGMIF_SEG_OHEM && !workspace) return SEGMIF_EINVAL;
+  return launch_backward(a, workspace, record4, upstream, dlogits, ldd, (hipStream_t)stream);
 }

@@ -139,12 +139,14 @@ def pack_records(indices, params, h, w):
 
 class PairFolder:
     """The reference's directory contract (voc_fusion3.py:25-30): ROOT/Infrared, Visible, Mask2, Label hold NAME.png (or
-    NAME.npy) for every NAME listed in NAME_LIST_DIR/SPLIT.txt.  .npy is always read, .png when PIL imports."""
+    NAME.npy) for every NAME listed in NAME_LIST_DIR/SPLIT.txt.  .npy is always read, .png when PIL imports.
+    labelled=False (an unlabelled split for self-training, segmif_amd.selftrain; not the reference's): Label/ is not read - it need
+    not exist - and every label is 255, the ignore value."""
 
     SUBDIRS = {"ir": "Infrared", "vis": "Visible", "mask": "Mask2", "label": "Label"}
 
-    def __init__(self, root_dir, name_list_dir, split="train"):
-        self.root_dir = root_dir
+    def __init__(self, root_dir, name_list_dir, split="train", labelled=True):
+        self.root_dir, self.labelled = root_dir, bool(labelled)
         path = os.path.join(name_list_dir, split + ".txt")
         with open(path) as f:
             self.names = [ln.split()[0] for ln in f if ln.strip()]
@@ -164,7 +166,8 @@ class PairFolder:
     def __getitem__(self, i):
         """-> (name, ir (h, w), vis (h, w, 3), mask (h, w), label (h, w)) uint8 arrays"""
         name = self.names[i]
-        ir, vis, mask, label = (np.asarray(_read(self._file(k, name))) for k in ("ir", "vis", "mask", "label"))
+        ir, vis, mask = (np.asarray(_read(self._file(k, name))) for k in ("ir", "vis", "mask"))
+        label = np.asarray(_read(self._file("label", name))) if self.labelled else np.full(ir.shape[:2], 255, dtype=np.uint8)
         if ir.ndim != 2 or mask.ndim != 2 or label.ndim != 2 or vis.ndim != 3 or vis.shape[2] != 3:
             raise RuntimeError(f"{name}: expected grey infrared / mask / label and an RGB visible image, got shapes "
                                f"{ir.shape}, {vis.shape}, {mask.shape}, {label.shape}")

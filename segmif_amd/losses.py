@@ -277,18 +277,22 @@ class SegObjective(nn.Module):
         s = f"gamma={self.gamma}, label_smoothing={self.label_smoothing}, ignore_index={self.ignore_index}, reduction={self.reduction!r}"
         return s + (f", ohem_t={self.ohem_t:.6f}, ohem_n_min={self.ohem_n_min}" if self.reduction == "ohem" else "")
 
-    def forward_nhwc(self, logits_nhwc, labels):
-        """logits_nhwc: (..., C) float32 device rows (a channel slice of a wider buffer is fine); labels: one per row"""
+    def forward_nhwc(self, logits_nhwc, labels, pixel_weight=None, sample_weight=None):
+        """logits_nhwc: (..., C) float32 device rows (a channel slice of a wider buffer is fine); labels: one per row.
+        pixel_weight (B, H, W) or (rows,), sample_weight (B,): float32 device DATA (no gradient) that multiply the per-pixel loss and
+        leave the reduction's denominator alone (self-training; not the reference's objective).  Both None: the path as it was."""
         from . import autograd as ag
+        if (pixel_weight is not None or sample_weight is not None) and self.reduction == "ohem":
+            raise TypeError("SegObjective: the 'ohem' reduction takes no pixel_weight / sample_weight (that combination is not built)")
         return ag.seg_objective(logits_nhwc, labels, gamma=self.gamma, label_smoothing=self.label_smoothing, weight=self.weight,
                                 ignore_index=self.ignore_index, reduction=self.reduction, ohem_t=self.ohem_t,
-                                ohem_n_min=self.ohem_n_min)
+                                ohem_n_min=self.ohem_n_min, pixel_weight=pixel_weight, sample_weight=sample_weight)
 
-    def forward(self, logits, labels):
+    def forward(self, logits, labels, pixel_weight=None, sample_weight=None):
         """logits: logical (B, C, H, W), contiguous or channels-last in memory (what ops.as_nchw returns); the gradient comes back
         in the same layout."""
         from . import autograd as ag
-        return self.forward_nhwc(ag.nhwc_rows_of(logits), labels)
+        return self.forward_nhwc(ag.nhwc_rows_of(logits), labels, pixel_weight, sample_weight)
 
 
 class SegObjectiveLoss(nn.Module):
@@ -299,10 +303,10 @@ class SegObjectiveLoss(nn.Module):
         self.objective = objective
 
     def forward(self, logits, labels):
-        return self.objective(logits, labels)
+        return self.objective(logits, labels)  # (the reference's signature; the weights of self-training go through forward_nhwc)
 
-    def forward_nhwc(self, logits_nhwc, labels):
-        return self.objective.forward_nhwc(logits_nhwc, labels)
+    def forward_nhwc(self, logits_nhwc, labels, pixel_weight=None, sample_weight=None):
+        return self.objective.forward_nhwc(logits_nhwc, labels, pixel_weight, sample_weight)
 
 
 # ---- the region objectives (csrc/region_objective.hip) ----------------------------------------------------------------------------------

@@ -1370,6 +1370,45 @@ def bilinear_argmax(x, OH, OW):
     return labels
 
 
+PSEUDO_BELOW = ("keep", "ignore")
+
+
+def pseudo_label(logits_nhwc, OH, OW, tau=0.968, below="keep", ignore_index=255, return_conf=False):
+    """Pseudo-labels of a teacher's NHWC logits (B, IH, IW, C) rows view, C <= 32, in one pass (csrc/pseudo_label.hip; the rule:
+    include/segmif_hip.h, segmif_pseudo_label_f32): labels (B, OH, OW) int64 = argmax of the bilinear resize (bilinear_argmax's
+    labels), count (B,) int64 = the pixels whose softmax maximum is > tau, and with return_conf the maximum itself (B, OH, OW)
+    float32.  below="keep" leaves the argmax everywhere (DAFormer: the weight carries the confidence), "ignore" writes ignore_index
+    where the maximum is not above tau.  tau = 0.968 is DAFormer's default.  The resized logits are never formed; no
+    synchronisation.  -> (labels, count) or (labels, count, conf).  NOT the reference's training."""
+    if logits_nhwc.dim() != 4:
+        raise RuntimeError("pseudo_label expects (B, H, W, C)")
+    if below not in PSEUDO_BELOW:
+        raise ValueError(f"pseudo_label: below must be one of {', '.join(PSEUDO_BELOW)}, got {below!r}")
+    tau = float(tau)
+    _, C, ldx = rows_view(logits_nhwc, "logits")
+    B, IH, IW = logits_nhwc.shape[0], logits_nhwc.shape[1], logits_nhwc.shape[2]
+    if min(B, IH, IW, int(OH), int(OW)) < 1 or not 1 <= C <= 32 or not 0.0 <= tau <= 1.0:  # (NaN fails the comparison)
+        raise ValueError(f"pseudo_label: sizes must be >= 1, C in 1..32 and tau in [0, 1]; got {tuple(logits_nhwc.shape)} -> "
+                         f"{OH} x {OW}, tau {tau} (SEGMIF_EINVAL)")
+    dev = logits_nhwc.device
+    labels = torch.empty((B, OH, OW), device=dev, dtype=torch.int64)
+    count = torch.empty((B,), device=dev, dtype=torch.int64)
+    conf = torch.empty((B, OH, OW), device=dev, dtype=torch.float32) if return_conf else None
+    _side("bilinear", lambda: _lib.check(_lib.load().segmif_pseudo_label_f32(
+        logits_nhwc.data_ptr(), labels.data_ptr(), conf.data_ptr() if return_conf else None, count.data_ptr(), B, IH, IW, int(OH),
+        int(OW), C, ldx, tau, int(below == "ignore"), int(ignore_index), _stream()), "segmif_pseudo_label_f32"),
+        4.0 * B * C * IH * IW + (12.0 if return_conf else 8.0) * B * OH * OW)
+    return (labels, count, conf) if return_conf else (labels, count)
+
+
+def pseudo_weight(count, OH, OW):
+    """DAFormer's pseudo_weight: q_b = count_b / (OH OW), the share of a sample's pixels above tau, as (B,) float32 on the device
+    (count: pseudo_label's; formed in double, no readback)."""
+    if not isinstance(count, torch.Tensor) or not count.is_cuda or count.dtype != torch.int64 or count.dim() != 1:
+        raise RuntimeError("pseudo_weight: count must be pseudo_label's (B,) int64 device tensor")
+    return (count.double() / float(int(OH) * int(OW))).float()
+
+
 def tta_vote(views, flips, OH, OW, want_probs=False):
     """Multi-scale + flip vote (csrc/tta.hip): views - up to 16 NHWC logit maps (B, ih, iw, C) rows views, C <= 32, as
     bilinear_argmax takes them; flips - one flag per view (the view's input was mirrored).  Every view is resized to OH x OW

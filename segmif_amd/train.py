@@ -17,6 +17,8 @@ segmif_amd.data makes on the device (main() below; one process, one GPU).  --seg
 --seg-region adds a region term to it (make_seg_region): Lovasz-Softmax or soft Dice on csrc/region_objective.hip.
 --ema-decay keeps an exponential moving average of the weights in the optimizer step (csrc/weight_ema.hip) and validates and
 writes the AVERAGED weights.  --class-mix pastes classes between the crops of a batch (ClassMix, csrc/class_mix.hip).
+--self-training adds an unlabelled split to the segmentation phase (segmif_amd.selftrain: the weight average as the teacher,
+pseudo-labels from csrc/pseudo_label.hip, a confidence-weighted CE on csrc/seg_objective.hip's weighted entries).
 """
 import argparse
 import contextlib
@@ -484,6 +486,24 @@ def main(argv=None):
                     "averages nothing")
     ap.add_argument("--ema-warmup", action="store_true", help="with --ema-decay: the decay of update t is min(D, (1 + t) / (10 + t))")
     ap.add_argument("--ema-nets", choices=("seg", "fusion", "both"), help="with --ema-decay: the nets that are averaged (default seg)")
+    ap.add_argument("--self-training", action="store_true", help="DAFormer-style self-training in the SEGMENTATION phase (Hoyer et al. "
+                    "2022): the weight average of --ema-decay is the teacher, its predictions on the frames of --unlabelled-split become "
+                    "pseudo-labels on the device, and the step adds a cross entropy on them, weighted by the share of confident pixels, "
+                    "to the labelled loss.  Needs --ema-decay with the segmentation net averaged.  Off by default.  This project's "
+                    "addition, NOT the reference's training; nothing here says what it does to mIoU")
+    ap.add_argument("--unlabelled-split", metavar="NAME", help="with --self-training: the split of --name-lists whose frames carry no "
+                    "Label/ image (Infrared/, Visible/ and Mask2/ only).  With --synthetic a seeded stand-in set is made instead")
+    ap.add_argument("--st-threshold", type=float, metavar="TAU", help="with --self-training: a pixel is confident when the teacher's "
+                    "softmax maximum is above TAU, in [0, 1] (default 0.968, DAFormer's)")
+    ap.add_argument("--st-below", choices=("keep", "ignore"), help="with --self-training: keep the pseudo-label of a pixel that is not "
+                    "confident (default; DAFormer: the per-image weight carries the confidence) or set it to the ignore value")
+    ap.add_argument("--st-weight", type=float, metavar="W", help="with --self-training: weight of the unlabelled term, > 0 (default 1.0)")
+    ap.add_argument("--st-mix", action="store_true", help="with --self-training: paste half of the classes of labelled sample i into "
+                    "unlabelled sample i (DAFormer's cross-set ClassMix, on csrc/class_mix.hip); pasted pixels get weight 1")
+    ap.add_argument("--st-mix-prob", type=float, metavar="P", help="with --st-mix: the probability that a sample is mixed, in (0, 1] "
+                    "(default 1.0, DAFormer's)")
+    ap.add_argument("--st-mix-min-pixels", type=int, metavar="N", help="with --st-mix: a class is present in a labelled crop when the "
+                    "crop holds more than N pixels of it (default 0)")
     ap.add_argument("--log-iters", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args(argv)
@@ -554,6 +574,30 @@ def main(argv=None):
         ap.error("--ema-warmup / --ema-nets belong to --ema-decay, which is not given")
     if args.ema_decay is not None and not 0.0 < args.ema_decay < 1.0:
         ap.error(f"--ema-decay {args.ema_decay}: must lie inside (0, 1)")
+    for flag, value in (("--unlabelled-split", args.unlabelled_split), ("--st-threshold", args.st_threshold), ("--st-below", args.st_below),
+                        ("--st-weight", args.st_weight), ("--st-mix", args.st_mix or None), ("--st-mix-prob", args.st_mix_prob),
+                        ("--st-mix-min-pixels", args.st_mix_min_pixels)):
+        if value is not None and not args.self_training:
+            ap.error(f"{flag} belongs to --self-training, which is not given")
+    for flag, value in (("--st-mix-prob", args.st_mix_prob), ("--st-mix-min-pixels", args.st_mix_min_pixels)):
+        if value is not None and not args.st_mix:
+            ap.error(f"{flag} belongs to --st-mix, which is not given")
+    if args.self_training:
+        if args.ema_decay is None or args.ema_nets == "fusion":
+            ap.error("--self-training takes the weight average as its teacher: give --ema-decay with the segmentation net averaged "
+                     "(--ema-nets seg, the default, or both)")
+        if args.synthetic is None and args.unlabelled_split is None:
+            ap.error("--self-training needs --unlabelled-split NAME (or --synthetic N, which makes a stand-in set)")
+        if args.synthetic is not None and args.unlabelled_split is not None:
+            ap.error("--unlabelled-split names a split of --name-lists; --synthetic makes its own unlabelled stand-in set")
+        if args.st_threshold is not None and not 0.0 <= args.st_threshold <= 1.0:
+            ap.error(f"--st-threshold {args.st_threshold}: must lie in [0, 1]")
+        if args.st_weight is not None and not (args.st_weight > 0 and math.isfinite(args.st_weight)):
+            ap.error(f"--st-weight {args.st_weight}: must be a finite number > 0")
+        if args.st_mix_prob is not None and not 0.0 < args.st_mix_prob <= 1.0:
+            ap.error(f"--st-mix-prob {args.st_mix_prob}: must lie in (0, 1]")
+        if args.st_mix_min_pixels is not None and args.st_mix_min_pixels < 0:
+            ap.error(f"--st-mix-min-pixels {args.st_mix_min_pixels}: must be >= 0")
     seg_pixels = max(1, args.samples_per_gpu // 2) * args.crop_size ** 2
     if args.ohem_n_min is None:
         args.ohem_n_min = max(1, seg_pixels // 16)
@@ -577,11 +621,17 @@ def main(argv=None):
               f"{H} x {W}) - a run of the machinery, not of a data set; validation on {max(2, args.synthetic // 4)} more of them")
         train_set = DeviceDataset.from_arrays(**synthetic_pairs(args.synthetic, H, W, args.seed))
         val_set = DeviceDataset.from_arrays(**synthetic_pairs(max(2, args.synthetic // 4), H, W, args.seed + 1))
+        if args.self_training:  # a stand-in unlabelled set of the same size: other frames, the labels dropped
+            unl = synthetic_pairs(args.synthetic, H, W, args.seed + 2)
+            unl["label"][:] = 255
+            unl_set = DeviceDataset.from_arrays(**unl)
     else:
         if not args.name_lists:
             ap.error("--root needs --name-lists")
         train_set = DeviceDataset.from_folder(PairFolder(args.root, args.name_lists, args.split))
         val_set = DeviceDataset.from_folder(PairFolder(args.root, args.name_lists, args.val_split))
+        if args.self_training:
+            unl_set = DeviceDataset.from_folder(PairFolder(args.root, args.name_lists, args.unlabelled_split, labelled=False))
     os.makedirs(args.out, exist_ok=True)
     seg_path, fus_path = os.path.join(args.out, SEG_CKPT), os.path.join(args.out, FUSION_CKPT)
     batch = max(1, args.samples_per_gpu // 2)
@@ -665,6 +715,23 @@ def main(argv=None):
               "project's addition, NOT the reference's loader (its train.py mixes nothing): classes of one crop of a batch are pasted "
               "into another, images and label alike")
 
+    st_kw = None
+    if args.self_training:
+        from .selftrain import EmaTeacher, SelfTrainingStep
+        st_kw = dict(tau=0.968 if args.st_threshold is None else args.st_threshold, below=args.st_below or "keep",
+                     unsup_weight=1.0 if args.st_weight is None else args.st_weight)
+        st_mix_kw = dict(prob=1.0 if args.st_mix_prob is None else args.st_mix_prob, classes="half",
+                         min_pixels=0 if args.st_mix_min_pixels is None else args.st_mix_min_pixels, n_class=n_class) if args.st_mix else None
+        if len(unl_set) < batch:
+            raise SystemExit(f"[train] --self-training: the unlabelled set holds {len(unl_set)} frames, fewer than one batch of {batch}")
+        print(f"[train] --self-training ({', '.join(f'{k} {v}' for k, v in st_kw.items())}; {len(unl_set)} unlabelled frames"
+              + (f"; --st-mix {', '.join(f'{k} {v}' for k, v in st_mix_kw.items())}" if args.st_mix else "") + "): this project's addition, "
+              "NOT the reference's training (its train.py uses labelled frames only).  DAFormer-style: the weight average is the "
+              "teacher, its argmax on an unlabelled batch the pseudo-label, the share of pixels above the threshold the weight of a "
+              "mean-over-all-pixels CE added to the labelled loss; no feature-distance term, one domain, the teacher's BatchNorm "
+              "buffers copied from the student.  Segmentation phase only.  Nothing here says what it does to mIoU: that takes a run "
+              "on a data set")
+
     def loader(dataset, phase, seed, **kw):
         sampler = RareClassSampler(stats, range(len(dataset)), seed=seed, **rcs_kw) if phase in rcs_phases else None
         mix = ClassMix(seed=seed, **mix_kw) if phase in mix_phases else None
@@ -702,6 +769,7 @@ def main(argv=None):
         with averaged(ema_fus, trainer.opt, fus):
             torch.save(fus.state_dict(), fus_path)
             fused = _fused_frames(seg, fus, train_set, batch)
+            fused_unl = _fused_frames(seg, fus, unl_set, batch) if st_kw is not None else None
         fused_set = DeviceDataset(train_set.names, train_set.ir, fused, train_set.mask, train_set.label)
         # ---- segmentation phase (train.py:115-245) on the fused training frames, from the best checkpoint so far (:159-160)
         print(f"[train] round {iter_}: segmentation")
@@ -715,12 +783,22 @@ def main(argv=None):
         glog = _GuardLog(opt, [("seg_net", seg)], args.max_consecutive_skips) if guarded else None
         batches = loader(fused_set, "seg", args.seed + 2 * iter_ + 1, photometric=())
         rlog, mlog = _RcsLog(batches), _MixLog(batches)
+        st = None
+        if st_kw is not None:  # the unlabelled frames, fused as the labelled ones are, walked by a loader of their own
+            unl_batches = AugmentedBatches(DeviceDataset(unl_set.names, unl_set.ir, fused_unl, unl_set.mask, unl_set.label),
+                                           seed=args.seed + 2 * iter_ + 1 + 7919, photometric=(), **loader_kw)
+            st = SelfTrainingStep(seg, EmaTeacher(opt, seg), opt, seg_crit,
+                                  mix=ClassMix(seed=args.seed + 2 * iter_ + 1 + 7919, **st_mix_kw) if st_mix_kw else None, **st_kw)
         n_seg = args.seg_iters if args.seg_iters is not None else 10000
         for n in range(n_seg):
             _, _, fused3, _, label = next(batches)
-            loss = seg_train_step(seg, opt, fused3, label, seg_crit)
+            if st is None:
+                loss = seg_train_step(seg, opt, fused3, label, seg_crit)
+            else:
+                loss, loss_unsup = st.step(fused3, label, next(unl_batches)[2])
             if (n + 1) % args.log_iters == 0 or n + 1 == n_seg:
                 print(f"[train] round {iter_} segmentation iter {n + 1}/{n_seg}: lr {opt.param_groups[0]['lr']:.3e} loss {float(loss):.6f}"
+                      + (f" unlabelled {float(loss_unsup):.6f} confident {st.confident_share():.4f}" if st is not None else "")
                       + (glog.line() if guarded else "") + rlog.line() + mlog.line())
                 if guarded:
                     glog.check()
