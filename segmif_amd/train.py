@@ -12,7 +12,14 @@ feed train.py:369-374's dynamic weights are averaged too so every rank applies i
     python -m segmif_amd.train --synthetic N ...
 
 runs the whole schedule of train.py:424-434 - seven rounds of a fusion phase then a segmentation phase - on batches that
-segmif_amd.data makes on the device (main() below; one process, one GPU).  --seg-loss picks the segmentation phase's objective
+segmif_amd.data makes on the device (one process, one GPU).  The command line is a stack of functions below the rule, and main()
+calls them in this order: build_parser (flags and help), check_args (what the flags cannot mean together: two tables, then the
+rules that read several flags) and resolve_defaults, all three host-only and kept with their tables in segmif_amd.train_args,
+make_plan (the host data of a run: keyword dicts, phases, iteration counts, announcements), _build_run (data, nets and objectives
+on the device: the run, the one object the phases share), then per round fusion_phase and seg_phase, each of which names the weights
+it starts from in its first lines.  A log line is a prefix plus what each log part's line() adds (_logger).  A new family of flags
+is one block in the parser, one row in each table, one entry in the plan and one log part.
+--seg-loss picks the segmentation phase's objective
 (make_seg_loss): the reference's CE by default, or OHEM / focal / NormalLoss / class-weighted CE on csrc/seg_objective.hip.
 --seg-region adds a region term to it (make_seg_region): Lovasz-Softmax or soft Dice on csrc/region_objective.hip.
 --ema-decay keeps an exponential moving average of the weights in the optimizer step (csrc/weight_ema.hip) and validates and
@@ -20,17 +27,19 @@ writes the AVERAGED weights.  --class-mix pastes classes between the crops of a 
 --self-training adds an unlabelled split to the segmentation phase (segmif_amd.selftrain: the weight average as the teacher,
 pseudo-labels from csrc/pseudo_label.hip, a confidence-weighted CE on csrc/seg_objective.hip's weighted entries).
 """
-import argparse
 import contextlib
 import math
 import os
 import sys
+import types
 
 import torch
 
 from . import losses, ops
 from .core.model_fusion import RGB2YCrCb, YCrCb2RGB
 from .parallel import allreduce_scalar_mean
+from .train_args import (FUSION_CKPT, N_CLASS, PHASES, SEG_CKPT, SEG_LOSSES, SEG_REGIONS, build_parser, check_args,  # noqa: F401
+                         fusion_loss_names, resolve_defaults)
 
 
 def _zero_grads(optimizer, reducer):
@@ -198,9 +207,6 @@ class FusionTrainer:
 
 # ------------------------------------------------------------------------------------------------------------- command line
 
-SEG_CKPT, FUSION_CKPT = "model-fusion_add_final2.pth", "modelfusion-final2.pth"  # train.py:237-238, :403-407
-
-
 def make_seg_optimizer(seg_net, iter_curr=0, lr=8e-5, weight_decay=0.01, betas=(0.9, 0.999), warmup_iter=3000, max_iter=160000,
                        warmup_ratio=1e-6, power=1.0, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False):
     """train.py:173-200: [encoder non-norm | encoder norm, no decay | decoder + classifier at 10 x lr].  max_grad_norm /
@@ -227,12 +233,6 @@ def make_fusion_optimizer(fusion_net, iter_, lr=8e-5, weight_decay=0.01, betas=(
                            ema_decay=ema_decay, ema_warmup=ema_warmup)
 
 
-def fusion_loss_names():
-    """the objectives of core/loss.py that --fusion-loss / make_fusion_loss build"""
-    from .core import loss
-    return sorted(n for n in loss.__all__ if n.startswith(("Fusionloss", "Total_fusion_loss", "new_loss_sobel")))
-
-
 def make_fusion_loss(name):
     """core/loss.py's objective `name` as FusionTrainer's fusion_loss hook (ir, vis_ycrcb, fused, mask3) -> scalar: the classes
     whose forward takes the mask third and the fused image last (Total_fusion_loss*, new_loss_sobel) are wrapped accordingly;
@@ -246,9 +246,6 @@ def make_fusion_loss(name):
     if name == "new_loss_sobel":
         return lambda ir, vis, fused, mask3: fn(ir[:, :1], vis[:, :1], mask3, fused)
     return fn
-
-
-SEG_LOSSES = ("ce", "ohem", "focal", "normal", "weighted")
 
 
 def seg_loss_names():
@@ -286,9 +283,6 @@ def make_seg_loss(name, ignore_index=255, ohem_thresh=0.7, ohem_n_min=None, foca
     if class_weights is None:
         raise ValueError("'weighted' needs class_weights")
     return losses.SegObjective(label_smoothing=label_smoothing, weight=class_weights, ignore_index=ignore_index)
-
-
-SEG_REGIONS = ("lovasz", "dice")
 
 
 def make_seg_region(criterion, kind, weight=1.0, classes="present", smooth=1.0, ignore_index=255):
@@ -338,34 +332,19 @@ class _GuardLog:
             raise SystemExit(self.stop)
 
 
-class _RcsLog:
-    """What a log line adds under rare-class sampling: ONE rcs_tally() readback per line - per class the samples drawn for it and
-    those of them whose crop passed the threshold, since the previous line.  Nothing for a loader without a sampler."""
+class _TallyLog:
+    """What a log line adds from a loader's tally since the previous line, ONE readback per line: rcs_tally's samples drawn per class
+    and those whose crop passed the threshold, or mix_tally's samples pasted into per class and pixels pasted.  tally None: nothing."""
 
-    def __init__(self, batches):
-        self.batches, self.last = batches, 0
-
-    def line(self):
-        if self.batches.sampler is None:
-            return ""
-        now = self.batches.rcs_tally()
-        d, self.last = now - self.last, now
-        return " rcs drawn/hit " + (" ".join(f"{c}:{int(d[c, 0])}/{int(d[c, 1])}" for c in range(len(d)) if d[c, 0]) or "none")
-
-
-class _MixLog:
-    """What a log line adds under ClassMix: ONE mix_tally() readback per line - per class the samples that had it pasted in and
-    the pixels pasted, since the previous line.  Nothing for a loader without a ClassMix."""
-
-    def __init__(self, batches):
-        self.batches, self.last = batches, 0
+    def __init__(self, label, tally):
+        self.label, self.tally, self.last = label, tally, 0
 
     def line(self):
-        if self.batches.mix is None:
+        if self.tally is None:
             return ""
-        now = self.batches.mix_tally()
+        now = self.tally()
         d, self.last = now - self.last, now
-        return " mix sel/px " + (" ".join(f"{c}:{int(d[c, 0])}/{int(d[c, 1])}" for c in range(len(d)) if d[c, 0]) or "none")
+        return self.label + (" ".join(f"{c}:{int(d[c, 0])}/{int(d[c, 1])}" for c in range(len(d)) if d[c, 0]) or "none")
 
 
 def _miou(seg, fus, val, batch):
@@ -392,233 +371,89 @@ def _fused_frames(seg, fus, ds, batch):
     return out
 
 
-def main(argv=None):
-    ours = " (this project's choice: the reference reads it from a configs/*.yaml it does not ship)"
-    ap = argparse.ArgumentParser(prog="python -m segmif_amd.train", description="The reference's training schedule (train.py:424-434) "
-                                 "on device-made batches: per round a fusion phase (FusionTrainer) then a segmentation phase "
-                                 "(seg_train_step).  Constants of the reference's code are fixed: 3e-4 / round as the fusion optimizer's "
-                                 "default rate, 6000 / 4000 fusion and 10000 segmentation iterations, loss weights 0.4 / round and 0.8, "
-                                 "7 rounds; --rounds / --fusion-iters / --seg-iters shorten a run.")
-    ap.add_argument("--root", help="data set root: Infrared/ Visible/ Mask2/ Label/ (voc_fusion3.py:25-28)")
-    ap.add_argument("--name-lists", help="folder of SPLIT.txt name lists")
-    ap.add_argument("--split", default="train")
-    ap.add_argument("--val-split", default="val", help="split whose mIoU decides which segmentation checkpoint is kept")
-    ap.add_argument("--synthetic", type=int, metavar="N", help="train on N seeded synthetic frames instead of a data set")
-    ap.add_argument("--synthetic-size", type=int, nargs=2, default=(480, 640), metavar=("H", "W"))
-    ap.add_argument("--out", default="checkpoint", help=f"folder of {SEG_CKPT} and {FUSION_CKPT}")
-    ap.add_argument("--backbone", default="mit_b3", help="mit_b1 .. mit_b5; mit_b0's 32/64-channel features do not fit "
-                    "the fusion net's conv3 / conv4, in the reference either" + ours)
-    ap.add_argument("--pretrained", action="store_true", help="load the backbone's ImageNet weights from pretrained/BACKBONE.pth as the "
-                    "reference does (model_fusion.py:49); without it: random initialisation")
-    ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--fusion-iters", type=int, help="fusion iterations per round (default 6000 in round 1, then 4000)")
-    ap.add_argument("--seg-iters", type=int, help="segmentation iterations per round (default 10000)")
-    ap.add_argument("--samples-per-gpu", type=int, default=8, help="the loaders' batch is HALF of it (train.py:138, :290)" + ours)
-    ap.add_argument("--crop-size", type=int, default=512, help="crop" + ours)
-    ap.add_argument("--rescale-range", type=float, nargs=2, default=(0.5, 2.0), help="random scaling" + ours)
-    ap.add_argument("--lr", type=float, default=8e-5, help="learning rate of both phases, / round in the fusion phase" + ours)
-    ap.add_argument("--weight-decay", type=float, default=0.01, help=ours.strip(" ()"))
-    ap.add_argument("--betas", type=float, nargs=2, default=(0.9, 0.999), help=ours.strip(" ()"))
-    ap.add_argument("--warmup-iter", type=int, default=3000, help="segmentation warm-up" + ours)
-    ap.add_argument("--warmup-ratio", type=float, default=1e-6, help=ours.strip(" ()"))
-    ap.add_argument("--power", type=float, default=1.0, help="polynomial decay" + ours)
-    ap.add_argument("--max-iters", type=int, default=160000, help="horizon of both schedules" + ours)
-    ap.add_argument("--fusion-loss", metavar="NAME", help="train the fusion net on this objective of core/loss.py instead of the "
-                    "reference's schedule (Fusionloss3 in round 1, then Fusionloss_grad3 as the intensity term), which is the default. "
-                    "Any objective other than that schedule is this project's choice: the reference's train.py instantiates no other")
-    ap.add_argument("--seg-loss", choices=SEG_LOSSES, default="ce", help="objective of the SEGMENTATION phase (the segmentation term "
-                    "inside the fusion phase keeps plain CE).  ce, the default, is the reference's nn.CrossEntropyLoss(ignore_index=255); "
-                    "ohem / focal / normal are core/loss.py's OhemCELoss / SoftmaxFocalLoss / NormalLoss, weighted is CE with "
-                    "--seg-class-weights: none of those is the reference's objective, its train.py instantiates CE only")
-    ap.add_argument("--ohem-thresh", type=float, default=0.7, help="--seg-loss ohem: probability threshold (losses above -log of it are hard)")
-    ap.add_argument("--ohem-n-min", type=int, help="--seg-loss ohem: least number of pixels averaged; default batch * crop^2 // 16" + ours)
-    ap.add_argument("--focal-gamma", type=float, default=2.0, help="--seg-loss focal: exponent of (1 - p)")
-    ap.add_argument("--label-smoothing", type=float, default=0.0, help="--seg-loss ce / weighted: label smoothing in [0, 1); above 0 it is "
-                    "not the reference's objective")
-    ap.add_argument("--seg-class-weights", type=float, nargs="+", metavar="W", help="--seg-loss weighted: one weight >= 0 per class (9)")
-    ap.add_argument("--seg-class-weights-from", choices=("inverse", "median", "enet"), help="--seg-loss weighted: compute "
-                    "the class weights from the training split's labels, counted on the device, instead of typing them: inverse "
-                    "(1 / frequency, mean 1 over the present classes), median (median-frequency balancing, Eigen and Fergus 2015) or "
-                    "enet (1 / ln(1.02 + frequency), Paszke et al. 2016).  A class without a pixel gets "
-                    "weight 0.  Excludes --seg-class-weights")
-    ap.add_argument("--rare-class-sampling", action="store_true", help="draw the training frames by rare-class sampling (Hoyer et al. "
-                    "2022, DAFormer) instead of walking the split front to back: a class c with probability proportional to "
-                    "exp((1 - frequency_c) / T), a frame that holds it, and a crop that shows it.  Off by default.  This project's "
-                    "addition, NOT the reference's loader")
-    ap.add_argument("--rcs-temperature", type=float, metavar="T", help="with --rare-class-sampling: T > 0 (default 0.01, DAFormer's)")
-    ap.add_argument("--rcs-min-pixels", type=int, metavar="N", help="with --rare-class-sampling: a frame is a candidate of a class when "
-                    "it holds more than N pixels of it (default 3000, DAFormer's)")
-    ap.add_argument("--rcs-min-crop-ratio", type=float, metavar="R", help="with --rare-class-sampling: a crop is accepted when it holds "
-                    "more than N * R pixels of the class, scaled by the frame's resize (default 0.5, DAFormer's)")
-    ap.add_argument("--rcs-fraction", type=float, metavar="F", help="with --rare-class-sampling: the share of samples drawn that way, in "
-                    "(0, 1]; the others walk the split in order (default 1.0)" + ours)
-    ap.add_argument("--rcs-phases", choices=("seg", "fusion", "both"), help="with --rare-class-sampling: the phases whose loader "
-                    "samples (default seg)")
-    ap.add_argument("--class-mix", action="store_true", help="ClassMix (Olsson et al. 2021; the mixing step of DAFormer): with "
-                    "probability P a sample of a batch receives, from another sample of the same batch, the pixels of half of the "
-                    "classes present in that sample's crop, in every image and in the label, on the device.  Off by default.  This "
-                    "project's addition, NOT the reference's loader")
-    ap.add_argument("--class-mix-prob", type=float, metavar="P", help="with --class-mix: the probability that a sample is mixed, in "
-                    "(0, 1] (default 0.5, this project's choice: DAFormer mixes every sample)")
-    ap.add_argument("--class-mix-min-pixels", type=int, metavar="N", help="with --class-mix: a class is present in a donor crop when "
-                    "the crop holds more than N pixels of it (default 0)")
-    ap.add_argument("--class-mix-classes", choices=("half", "wanted"), help="with --class-mix: paste half of the donor's present "
-                    "classes (default), or the one class --rare-class-sampling drew the donor for")
-    ap.add_argument("--class-mix-phases", choices=("seg", "fusion", "both"), help="with --class-mix: the phases whose batches are "
-                    "mixed (default seg)")
-    ap.add_argument("--seg-region", choices=SEG_REGIONS, help="add a region objective to whatever --seg-loss builds, for the "
-                    "SEGMENTATION phase only: lovasz is Lovasz-Softmax (the convex surrogate of the Jaccard index, the batch as one set), "
-                    "dice the soft Dice loss.  This project's addition, NOT the reference's objective: its train.py trains on CE alone")
-    ap.add_argument("--seg-region-weight", type=float, metavar="W", help="--seg-region: the region term's weight, > 0 (default 1.0)")
-    ap.add_argument("--seg-region-classes", choices=("present", "all"), help="--seg-region: average over the classes present in the "
-                    "batch (default) or over all of them")
-    ap.add_argument("--dice-smooth", type=float, metavar="S", help="--seg-region dice: the smoothing term, >= 0 (default 1.0)")
-    ap.add_argument("--clip-grad-norm", type=float, metavar="X", help="clip the global gradient norm of every step of both phases to "
-                    "X > 0 (torch.nn.utils.clip_grad_norm_'s rule, on the device); off by default.  This project's addition: the "
-                    "reference's train.py does not clip")
-    ap.add_argument("--skip-nonfinite", action="store_true", help="do not apply a step whose gradients hold an inf or a NaN (decided on "
-                    "the device, no host synchronisation); off by default.  This project's addition")
-    ap.add_argument("--max-consecutive-skips", type=int, default=50, metavar="N", help="with --skip-nonfinite: stop when more than N "
-                    "steps in a row were skipped (checked at log lines)")
-    ap.add_argument("--ema-decay", type=float, metavar="D", help="keep an exponential moving average of the weights, decay D inside "
-                    "(0, 1), updated on the device in every applied optimizer step; validation, checkpoint selection and the written "
-                    "checkpoints then use the AVERAGED weights.  Off by default.  This project's addition: the reference's train.py "
-                    "averages nothing")
-    ap.add_argument("--ema-warmup", action="store_true", help="with --ema-decay: the decay of update t is min(D, (1 + t) / (10 + t))")
-    ap.add_argument("--ema-nets", choices=("seg", "fusion", "both"), help="with --ema-decay: the nets that are averaged (default seg)")
-    ap.add_argument("--self-training", action="store_true", help="DAFormer-style self-training in the SEGMENTATION phase (Hoyer et al. "
-                    "2022): the weight average of --ema-decay is the teacher, its predictions on the frames of --unlabelled-split become "
-                    "pseudo-labels on the device, and the step adds a cross entropy on them, weighted by the share of confident pixels, "
-                    "to the labelled loss.  Needs --ema-decay with the segmentation net averaged.  Off by default.  This project's "
-                    "addition, NOT the reference's training; nothing here says what it does to mIoU")
-    ap.add_argument("--unlabelled-split", metavar="NAME", help="with --self-training: the split of --name-lists whose frames carry no "
-                    "Label/ image (Infrared/, Visible/ and Mask2/ only).  With --synthetic a seeded stand-in set is made instead")
-    ap.add_argument("--st-threshold", type=float, metavar="TAU", help="with --self-training: a pixel is confident when the teacher's "
-                    "softmax maximum is above TAU, in [0, 1] (default 0.968, DAFormer's)")
-    ap.add_argument("--st-below", choices=("keep", "ignore"), help="with --self-training: keep the pseudo-label of a pixel that is not "
-                    "confident (default; DAFormer: the per-image weight carries the confidence) or set it to the ignore value")
-    ap.add_argument("--st-weight", type=float, metavar="W", help="with --self-training: weight of the unlabelled term, > 0 (default 1.0)")
-    ap.add_argument("--st-mix", action="store_true", help="with --self-training: paste half of the classes of labelled sample i into "
-                    "unlabelled sample i (DAFormer's cross-set ClassMix, on csrc/class_mix.hip); pasted pixels get weight 1")
-    ap.add_argument("--st-mix-prob", type=float, metavar="P", help="with --st-mix: the probability that a sample is mixed, in (0, 1] "
-                    "(default 1.0, DAFormer's)")
-    ap.add_argument("--st-mix-min-pixels", type=int, metavar="N", help="with --st-mix: a class is present in a labelled crop when the "
-                    "crop holds more than N pixels of it (default 0)")
-    ap.add_argument("--log-iters", type=int, default=100)
-    ap.add_argument("--seed", type=int, default=0)
-    args = ap.parse_args(argv)
-    n_class = 9
-    if args.seg_class_weights is not None and args.seg_loss != "weighted":
-        ap.error(f"--seg-class-weights belongs to --seg-loss weighted, not {args.seg_loss}")
-    if args.seg_class_weights_from is not None and args.seg_loss != "weighted":
-        ap.error(f"--seg-class-weights-from belongs to --seg-loss weighted, not {args.seg_loss}")
-    if args.seg_class_weights_from is not None and args.seg_class_weights is not None:
-        ap.error("--seg-class-weights-from computes the weights that --seg-class-weights types: give one of the two")
-    if args.seg_loss == "weighted" and args.seg_class_weights_from is None and (
-            args.seg_class_weights is None or len(args.seg_class_weights) != n_class or min(args.seg_class_weights) < 0):
-        ap.error(f"--seg-loss weighted needs --seg-class-weights with {n_class} values >= 0, or --seg-class-weights-from inverse | median | enet")
-    for flag, value in (("--rcs-temperature", args.rcs_temperature), ("--rcs-min-pixels", args.rcs_min_pixels),
-                        ("--rcs-min-crop-ratio", args.rcs_min_crop_ratio), ("--rcs-fraction", args.rcs_fraction),
-                        ("--rcs-phases", args.rcs_phases)):
-        if value is not None and not args.rare_class_sampling:
-            ap.error(f"{flag} belongs to --rare-class-sampling, which is not given")
-    if args.rcs_temperature is not None and not (args.rcs_temperature > 0 and math.isfinite(args.rcs_temperature)):
-        ap.error(f"--rcs-temperature {args.rcs_temperature}: must be a finite number > 0")
-    if args.rcs_min_pixels is not None and args.rcs_min_pixels < 0:
-        ap.error(f"--rcs-min-pixels {args.rcs_min_pixels}: must be >= 0")
-    if args.rcs_min_crop_ratio is not None and not (args.rcs_min_crop_ratio >= 0 and math.isfinite(args.rcs_min_crop_ratio)):
-        ap.error(f"--rcs-min-crop-ratio {args.rcs_min_crop_ratio}: must be a finite number >= 0")
-    if args.rcs_fraction is not None and not 0.0 < args.rcs_fraction <= 1.0:
-        ap.error(f"--rcs-fraction {args.rcs_fraction}: must lie in (0, 1]")
-    for flag, value in (("--class-mix-prob", args.class_mix_prob), ("--class-mix-min-pixels", args.class_mix_min_pixels),
-                        ("--class-mix-classes", args.class_mix_classes), ("--class-mix-phases", args.class_mix_phases)):
-        if value is not None and not args.class_mix:
-            ap.error(f"{flag} belongs to --class-mix, which is not given")
-    if args.class_mix_prob is not None and not 0.0 < args.class_mix_prob <= 1.0:
-        ap.error(f"--class-mix-prob {args.class_mix_prob}: must lie in (0, 1]")
-    if args.class_mix_min_pixels is not None and args.class_mix_min_pixels < 0:
-        ap.error(f"--class-mix-min-pixels {args.class_mix_min_pixels}: must be >= 0")
-    mix_phases = {"seg": ("seg",), "fusion": ("fusion",), "both": ("seg", "fusion")}[args.class_mix_phases or "seg"] if args.class_mix else ()
-    if args.class_mix and args.class_mix_classes == "wanted":
-        sampled = {"seg": ("seg",), "fusion": ("fusion",), "both": ("seg", "fusion")}[args.rcs_phases or "seg"] if args.rare_class_sampling else ()
-        missing = [ph for ph in mix_phases if ph not in sampled]
-        if missing:
-            ap.error(f"--class-mix-classes wanted pastes the class --rare-class-sampling drew the donor for: the {', '.join(missing)} "
-                     "phase has no rare-class sampling (--rare-class-sampling, --rcs-phases)")
-    if args.class_mix and args.samples_per_gpu < 4:
-        ap.error(f"--class-mix with --samples-per-gpu {args.samples_per_gpu}: the loaders' batch is half of it and mixing needs two samples, "
-                 "give at least 4")
-    if not 0.0 <= args.label_smoothing < 1.0:
-        ap.error(f"--label-smoothing {args.label_smoothing}: must lie in [0, 1)")
-    if args.label_smoothing and args.seg_loss not in ("ce", "weighted"):
-        ap.error(f"--label-smoothing belongs to --seg-loss ce / weighted, not {args.seg_loss}")
-    if args.seg_loss == "ohem" and not 0.0 < args.ohem_thresh <= 1.0:
-        ap.error(f"--ohem-thresh {args.ohem_thresh}: a probability in (0, 1]")
-    if args.seg_loss == "focal" and not args.focal_gamma > 0:
-        ap.error(f"--focal-gamma {args.focal_gamma}: must be > 0")
-    for flag, value in (("--seg-region-weight", args.seg_region_weight), ("--seg-region-classes", args.seg_region_classes),
-                        ("--dice-smooth", args.dice_smooth)):
-        if value is not None and args.seg_region is None:
-            ap.error(f"{flag} belongs to --seg-region, which is not given")
-    if args.dice_smooth is not None and args.seg_region != "dice":
-        ap.error(f"--dice-smooth belongs to --seg-region dice, not {args.seg_region}")
-    if args.seg_region_weight is not None and not (args.seg_region_weight > 0 and math.isfinite(args.seg_region_weight)):
-        ap.error(f"--seg-region-weight {args.seg_region_weight}: must be a finite number > 0")
-    if args.dice_smooth is not None and not (args.dice_smooth >= 0 and math.isfinite(args.dice_smooth)):
-        ap.error(f"--dice-smooth {args.dice_smooth}: must be a finite number >= 0")
-    if args.clip_grad_norm is not None and not (args.clip_grad_norm > 0 and math.isfinite(args.clip_grad_norm)):
-        ap.error(f"--clip-grad-norm {args.clip_grad_norm}: must be a finite number > 0")
-    if args.max_consecutive_skips < 1:
-        ap.error(f"--max-consecutive-skips {args.max_consecutive_skips}: must be >= 1")
-    if args.ema_decay is None and (args.ema_warmup or args.ema_nets is not None):
-        ap.error("--ema-warmup / --ema-nets belong to --ema-decay, which is not given")
-    if args.ema_decay is not None and not 0.0 < args.ema_decay < 1.0:
-        ap.error(f"--ema-decay {args.ema_decay}: must lie inside (0, 1)")
-    for flag, value in (("--unlabelled-split", args.unlabelled_split), ("--st-threshold", args.st_threshold), ("--st-below", args.st_below),
-                        ("--st-weight", args.st_weight), ("--st-mix", args.st_mix or None), ("--st-mix-prob", args.st_mix_prob),
-                        ("--st-mix-min-pixels", args.st_mix_min_pixels)):
-        if value is not None and not args.self_training:
-            ap.error(f"{flag} belongs to --self-training, which is not given")
-    for flag, value in (("--st-mix-prob", args.st_mix_prob), ("--st-mix-min-pixels", args.st_mix_min_pixels)):
-        if value is not None and not args.st_mix:
-            ap.error(f"{flag} belongs to --st-mix, which is not given")
-    if args.self_training:
-        if args.ema_decay is None or args.ema_nets == "fusion":
-            ap.error("--self-training takes the weight average as its teacher: give --ema-decay with the segmentation net averaged "
-                     "(--ema-nets seg, the default, or both)")
-        if args.synthetic is None and args.unlabelled_split is None:
-            ap.error("--self-training needs --unlabelled-split NAME (or --synthetic N, which makes a stand-in set)")
-        if args.synthetic is not None and args.unlabelled_split is not None:
-            ap.error("--unlabelled-split names a split of --name-lists; --synthetic makes its own unlabelled stand-in set")
-        if args.st_threshold is not None and not 0.0 <= args.st_threshold <= 1.0:
-            ap.error(f"--st-threshold {args.st_threshold}: must lie in [0, 1]")
-        if args.st_weight is not None and not (args.st_weight > 0 and math.isfinite(args.st_weight)):
-            ap.error(f"--st-weight {args.st_weight}: must be a finite number > 0")
-        if args.st_mix_prob is not None and not 0.0 < args.st_mix_prob <= 1.0:
-            ap.error(f"--st-mix-prob {args.st_mix_prob}: must lie in (0, 1]")
-        if args.st_mix_min_pixels is not None and args.st_mix_min_pixels < 0:
-            ap.error(f"--st-mix-min-pixels {args.st_mix_min_pixels}: must be >= 0")
-    seg_pixels = max(1, args.samples_per_gpu // 2) * args.crop_size ** 2
-    if args.ohem_n_min is None:
-        args.ohem_n_min = max(1, seg_pixels // 16)
-    if args.seg_loss == "ohem" and not 1 <= args.ohem_n_min <= seg_pixels:
-        ap.error(f"--ohem-n-min {args.ohem_n_min}: outside 1..{seg_pixels}, the pixels of a segmentation batch")
-    if not torch.cuda.is_available():
-        raise RuntimeError("segmif_amd.train needs the MI355X device (the HIP path has no CPU fallback)")
-    if (args.synthetic is None) == (args.root is None):
-        ap.error("give either --root DIR --name-lists DIR or --synthetic N")
-    if args.fusion_loss is not None and args.fusion_loss not in fusion_loss_names():
-        ap.error(f"--fusion-loss {args.fusion_loss}: one of {', '.join(fusion_loss_names())}")
-    if args.backbone == "mit_b0":
-        ap.error("--backbone mit_b0: Fusion_Network3_ac takes 64/128-channel segmentation features, mit_b0 gives 32/64")
-    from .core import Fusion_Network3_ac, Network3
-    from .data import AugmentedBatches, ClassMix, DeviceDataset, PairFolder, RareClassSampler, synthetic_pairs
+LABEL_SLOT, PROBE_SLOT = "<class table, computed weights>", "<candidates and probabilities>"  # in a plan's say: _build_run's lines
 
+
+def make_plan(args):
+    """The host data of a run, from checked arguments with their defaults resolved; touches no device.  *_kw: keywords of the
+    optimizer makers, AugmentedBatches, RareClassSampler, ClassMix, SelfTrainingStep and its ClassMix (None: switched off).  say:
+    what the run announces before round 1, in order; _build_run fills the two slots and {unlabelled}, which take the data."""
+    def listed(kw):
+        return ", ".join(f"{k} {v}" for k, v in kw.items())
+
+    p = types.SimpleNamespace(batch=max(1, args.samples_per_gpu // 2), guarded=args.clip_grad_norm is not None or args.skip_nonfinite,
+                              ema_seg=args.ema_decay is not None and args.ema_nets in ("seg", "both"),
+                              ema_fus=args.ema_decay is not None and args.ema_nets in ("fusion", "both"), rcs_kw=None, rcs_phases=(),
+                              mix_kw=None, mix_phases=(), st_kw=None, st_mix_kw=None)
+    say, keeps_ce = [], "(segmentation phase only; the fusion phase's segmentation term keeps CE)"
+    if args.synthetic is not None:
+        say.append(f"[train] --synthetic {args.synthetic}: training on SYNTHETIC frames (segmif_amd.data.synthetic_pairs, seed {args.seed}, "
+                   f"{args.synthetic_size[0]} x {args.synthetic_size[1]}) - a run of the machinery, not of a data set; validation on "
+                   f"{max(2, args.synthetic // 4)} more of them")
+    if not args.pretrained:
+        say.append("[train] no --pretrained backbone weights: the segmentation net starts from SEEDED RANDOM weights "
+                   f"(torch.manual_seed({args.seed}))")
+    say.append(LABEL_SLOT)
+    if args.seg_loss != "ce" or args.label_smoothing:
+        say.append(f"[train] --seg-loss {args.seg_loss}" + (f" --label-smoothing {args.label_smoothing}" if args.label_smoothing else "")
+                   + ": NOT the reference's segmentation objective " + keeps_ce)
+    if args.seg_region is not None:
+        say.append(f"[train] --seg-region {args.seg_region} (weight {args.seg_region_weight}, classes {args.seg_region_classes}"
+                   + (f", smooth {args.dice_smooth}" if args.seg_region == "dice" else "")
+                   + "): a region term added to the segmentation objective, NOT the reference's objective " + keeps_ce)
+    sched = dict(weight_decay=args.weight_decay, betas=args.betas, max_iter=args.max_iters, warmup_ratio=args.warmup_ratio, power=args.power)
+    if p.guarded:
+        sched.update(max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite)
+        say.append("[train] " + " ".join(([f"--clip-grad-norm {args.clip_grad_norm}"] if args.clip_grad_norm is not None else [])
+                                         + (["--skip-nonfinite"] if args.skip_nonfinite else []))
+                   + ": this project's additions, NOT the reference's training (its train.py neither clips gradients nor skips a step)")
+    ema_kw = dict(ema_decay=args.ema_decay, ema_warmup=args.ema_warmup)
+    p.fusion_opt_kw = dict(lr=args.lr, **sched, **(ema_kw if p.ema_fus else {}))
+    p.seg_opt_kw = dict(lr=args.lr, warmup_iter=args.warmup_iter, **sched, **(ema_kw if p.ema_seg else {}))
+    if args.ema_decay is not None:
+        say.append(f"[train] --ema-decay {args.ema_decay}" + (" --ema-warmup" if args.ema_warmup else "") + f" --ema-nets {args.ema_nets}"
+                   ": this project's addition, NOT the reference's training (its train.py averages nothing).  "
+                   + ("Every validation runs on the AVERAGED segmentation weights and the segmentation checkpoint holds them; each phase "
+                      "starts from the best checkpoint so far, so it starts from averaged weights.  " if p.ema_seg else "")
+                   + ("The fusion checkpoint and the fused training frames come from the AVERAGED fusion weights; its training continues "
+                      "from the raw ones." if p.ema_fus else ""))
+    p.loader_kw = dict(batch=p.batch, crop_size=args.crop_size, rescale_range=tuple(args.rescale_range), fliplr=True)
+    if args.rare_class_sampling:
+        p.rcs_phases, p.rcs_kw = PHASES[args.rcs_phases], dict(temperature=args.rcs_temperature, min_pixels=args.rcs_min_pixels,
+                                                                min_crop_ratio=args.rcs_min_crop_ratio, fraction=args.rcs_fraction)
+        say += [f"[train] --rare-class-sampling ({listed(p.rcs_kw)}; phases {', '.join(p.rcs_phases)}): this project's addition, NOT the "
+                "reference's loader (its train.py walks the split front to back and crops by the 0.75 test alone)", PROBE_SLOT]
+    if args.class_mix:
+        p.mix_phases = PHASES[args.class_mix_phases]
+        p.mix_kw = dict(prob=args.class_mix_prob, classes=args.class_mix_classes, min_pixels=args.class_mix_min_pixels, n_class=N_CLASS)
+        say.append(f"[train] --class-mix ({listed(p.mix_kw)}; phases {', '.join(p.mix_phases)}): this project's addition, NOT the reference's "
+                   "loader (its train.py mixes nothing): classes of one crop of a batch are pasted into another, images and label alike")
+    if args.self_training:
+        p.st_kw = dict(tau=args.st_threshold, below=args.st_below, unsup_weight=args.st_weight)
+        if args.st_mix:
+            p.st_mix_kw = dict(prob=args.st_mix_prob, classes="half", min_pixels=args.st_mix_min_pixels, n_class=N_CLASS)
+        say.append(f"[train] --self-training ({listed(p.st_kw)}; {{unlabelled}} unlabelled frames"
+                   + (f"; --st-mix {listed(p.st_mix_kw)}" if args.st_mix else "") + "): this project's addition, NOT the reference's training "
+                   "(its train.py uses labelled frames only).  DAFormer-style: the weight average is the teacher, its argmax on an unlabelled "
+                   "batch the pseudo-label, the share of pixels above the threshold the weight of a mean-over-all-pixels CE added to the "
+                   "labelled loss; no feature-distance term, one domain, the teacher's BatchNorm buffers copied from the student.  "
+                   "Segmentation phase only.  Nothing here says what it does to mIoU: that takes a run on a data set")
+    if args.fusion_loss is not None:
+        say.append(f"[train] --fusion-loss {args.fusion_loss}: NOT the reference's schedule of objectives")
+    p.fusion_iters = [args.fusion_iters if args.fusion_iters is not None else (6000 if r == 1 else 4000) for r in range(1, args.rounds + 1)]
+    p.seg_iters, p.say = [args.seg_iters if args.seg_iters is not None else 10000] * args.rounds, say
+    return p
+
+
+def _build_run(args, plan):
+    """Data, nets and objectives on the device, then the plan's announcements with the lines that read the labels in their slots.
+    -> the run, the one object the phases share; its last line: what a phase leaves for the next."""
+    from .core import Fusion_Network3_ac, Network3
+    from .data import DeviceDataset, PairFolder, RareClassSampler, synthetic_pairs
     torch.manual_seed(args.seed)
+    unl_set = None
     if args.synthetic is not None:
         H, W = args.synthetic_size
-        print(f"[train] --synthetic {args.synthetic}: training on SYNTHETIC frames (segmif_amd.data.synthetic_pairs, seed {args.seed}, "
-              f"{H} x {W}) - a run of the machinery, not of a data set; validation on {max(2, args.synthetic // 4)} more of them")
         train_set = DeviceDataset.from_arrays(**synthetic_pairs(args.synthetic, H, W, args.seed))
         val_set = DeviceDataset.from_arrays(**synthetic_pairs(max(2, args.synthetic // 4), H, W, args.seed + 1))
         if args.self_training:  # a stand-in unlabelled set of the same size: other frames, the labels dropped
@@ -626,196 +461,173 @@ def main(argv=None):
             unl["label"][:] = 255
             unl_set = DeviceDataset.from_arrays(**unl)
     else:
-        if not args.name_lists:
-            ap.error("--root needs --name-lists")
         train_set = DeviceDataset.from_folder(PairFolder(args.root, args.name_lists, args.split))
         val_set = DeviceDataset.from_folder(PairFolder(args.root, args.name_lists, args.val_split))
         if args.self_training:
             unl_set = DeviceDataset.from_folder(PairFolder(args.root, args.name_lists, args.unlabelled_split, labelled=False))
     os.makedirs(args.out, exist_ok=True)
-    seg_path, fus_path = os.path.join(args.out, SEG_CKPT), os.path.join(args.out, FUSION_CKPT)
-    batch = max(1, args.samples_per_gpu // 2)
-    seg, fus = Network3(args.backbone, 9, pretrained=args.pretrained or None).cuda().train(), Fusion_Network3_ac().cuda().train()
-    if not args.pretrained:
-        print("[train] no --pretrained backbone weights: the segmentation net starts from SEEDED RANDOM weights "
-              f"(torch.manual_seed({args.seed}))")
+    seg, fus = Network3(args.backbone, N_CLASS, pretrained=args.pretrained or None).cuda().train(), Fusion_Network3_ac().cuda().train()
     seg_initial = {k: v.clone() for k, v in seg.state_dict().items()}
-    crit = torch.nn.CrossEntropyLoss(ignore_index=255)
-    stats = None
+    stats, slots = None, {LABEL_SLOT: [], PROBE_SLOT: []}
     if args.seg_class_weights_from is not None or args.rare_class_sampling:
-        stats = train_set.label_stats(n_class)  # (the fused set of the segmentation phase shares these labels)
-        print(f"[train] classes of the {args.split if args.synthetic is None else 'synthetic'} labels, counted on the device:")
-        for row in stats.table():
-            print("[train]   " + row)
+        stats = train_set.label_stats(N_CLASS)  # (the fused set of the segmentation phase shares these labels)
+        slots[LABEL_SLOT] = [f"[train] classes of the {args.split if args.synthetic is None else 'synthetic'} labels, counted on the device:"]
+        slots[LABEL_SLOT] += ["[train]   " + row for row in stats.table()]
     if args.seg_class_weights_from is not None:
         args.seg_class_weights = [float(v) for v in stats.class_weights(args.seg_class_weights_from)]
-        absent = [c for c in range(n_class) if stats.pixels[c] == 0]
-        print(f"[train] --seg-class-weights-from {args.seg_class_weights_from}: " + " ".join(f"{v:.6g}" for v in args.seg_class_weights)
-              + (f"; class{'es' if len(absent) > 1 else ''} {', '.join(map(str, absent))} without a pixel: weight 0" if absent else ""))
+        absent = [c for c in range(N_CLASS) if stats.pixels[c] == 0]
+        slots[LABEL_SLOT].append(
+            f"[train] --seg-class-weights-from {args.seg_class_weights_from}: " + " ".join(f"{v:.6g}" for v in args.seg_class_weights)
+            + (f"; class{'es' if len(absent) > 1 else ''} {', '.join(map(str, absent))} without a pixel: weight 0" if absent else ""))
     seg_crit = make_seg_loss(args.seg_loss, ohem_thresh=args.ohem_thresh, ohem_n_min=args.ohem_n_min if args.seg_loss == "ohem" else None,
                              focal_gamma=args.focal_gamma, label_smoothing=args.label_smoothing,
                              class_weights=args.seg_class_weights).cuda()
-    if args.seg_loss != "ce" or args.label_smoothing:
-        print(f"[train] --seg-loss {args.seg_loss}" + (f" --label-smoothing {args.label_smoothing}" if args.label_smoothing else "")
-              + ": NOT the reference's segmentation objective (segmentation phase only; the fusion phase's segmentation term keeps CE)")
     if args.seg_region is not None:
-        weight = 1.0 if args.seg_region_weight is None else args.seg_region_weight
-        seg_crit = make_seg_region(seg_crit, args.seg_region, weight, args.seg_region_classes or "present",
-                                   1.0 if args.dice_smooth is None else args.dice_smooth).cuda()
-        print(f"[train] --seg-region {args.seg_region} (weight {weight}, classes {args.seg_region_classes or 'present'}"
-              + (f", smooth {seg_crit.region.smooth}" if args.seg_region == "dice" else "") + "): a region term added to the "
-              "segmentation objective, NOT the reference's objective (segmentation phase only; the fusion phase's segmentation term "
-              "keeps CE)")
-    sched = dict(weight_decay=args.weight_decay, betas=args.betas, max_iter=args.max_iters, warmup_ratio=args.warmup_ratio, power=args.power)
-    guarded = args.clip_grad_norm is not None or args.skip_nonfinite
-    if guarded:
-        sched.update(max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite)
-        print("[train] " + " ".join(([f"--clip-grad-norm {args.clip_grad_norm}"] if args.clip_grad_norm is not None else [])
-                                    + (["--skip-nonfinite"] if args.skip_nonfinite else []))
-              + ": this project's additions, NOT the reference's training (its train.py neither clips gradients nor skips a step)")
-    ema_seg = args.ema_decay is not None and (args.ema_nets or "seg") in ("seg", "both")
-    ema_fus = args.ema_decay is not None and args.ema_nets in ("fusion", "both")
-    ema_kw = dict(ema_decay=args.ema_decay, ema_warmup=args.ema_warmup)
-    if args.ema_decay is not None:
-        from .utils.optimizer import ema_weights
-        print(f"[train] --ema-decay {args.ema_decay}" + (" --ema-warmup" if args.ema_warmup else "") + f" --ema-nets {args.ema_nets or 'seg'}"
-              ": this project's addition, NOT the reference's training (its train.py averages nothing).  "
-              + ("Every validation runs on the AVERAGED segmentation weights and the segmentation checkpoint holds them; each phase "
-                 "starts from the best checkpoint so far, so it starts from averaged weights.  " if ema_seg else "")
-              + ("The fusion checkpoint and the fused training frames come from the AVERAGED fusion weights; its training continues "
-                 "from the raw ones." if ema_fus else ""))
-
-    def averaged(on, optimizer, net):
-        return ema_weights(optimizer, net) if on else contextlib.nullcontext()
-
-    loader_kw = dict(batch=batch, crop_size=args.crop_size, rescale_range=tuple(args.rescale_range), fliplr=True)
-    rcs_kw, rcs_phases = None, ()
-    if args.rare_class_sampling:
-        rcs_kw = dict(temperature=0.01 if args.rcs_temperature is None else args.rcs_temperature,
-                      min_pixels=3000 if args.rcs_min_pixels is None else args.rcs_min_pixels,
-                      min_crop_ratio=0.5 if args.rcs_min_crop_ratio is None else args.rcs_min_crop_ratio,
-                      fraction=1.0 if args.rcs_fraction is None else args.rcs_fraction)
-        rcs_phases = {"seg": ("seg",), "fusion": ("fusion",), "both": ("seg", "fusion")}[args.rcs_phases or "seg"]
+        seg_crit = make_seg_region(seg_crit, args.seg_region, args.seg_region_weight, args.seg_region_classes, args.dice_smooth).cuda()
+    if plan.rcs_kw is not None:
         try:
-            probe = RareClassSampler(stats, range(len(train_set)), **rcs_kw)
+            probe = RareClassSampler(stats, range(len(train_set)), **plan.rcs_kw)
         except ValueError as e:
             raise SystemExit(f"[train] --rare-class-sampling: {e}")
-        print(f"[train] --rare-class-sampling ({', '.join(f'{k} {v}' for k, v in rcs_kw.items())}; phases {', '.join(rcs_phases)}): this "
-              "project's addition, NOT the reference's loader (its train.py walks the split front to back and crops by the 0.75 test "
-              "alone)")
-        print("[train]   candidate frames per class: " + " ".join(f"{c}:{len(f)}" for c, f in enumerate(probe.candidates))
-              + "; sampling probability: " + " ".join(f"{c}:{probe.prob[c]:.4f}" for c in probe.classes)
-              + (f"; dropped (no frame with more than {rcs_kw['min_pixels']} pixels): {', '.join(map(str, probe.dropped))}"
-                 if probe.dropped else "; no class dropped"))
-    mix_kw = None
-    if args.class_mix:
-        mix_kw = dict(prob=0.5 if args.class_mix_prob is None else args.class_mix_prob, classes=args.class_mix_classes or "half",
-                      min_pixels=0 if args.class_mix_min_pixels is None else args.class_mix_min_pixels, n_class=n_class)
-        print(f"[train] --class-mix ({', '.join(f'{k} {v}' for k, v in mix_kw.items())}; phases {', '.join(mix_phases)}): this "
-              "project's addition, NOT the reference's loader (its train.py mixes nothing): classes of one crop of a batch are pasted "
-              "into another, images and label alike")
+        slots[PROBE_SLOT] = [
+            "[train]   candidate frames per class: " + " ".join(f"{c}:{len(f)}" for c, f in enumerate(probe.candidates))
+            + "; sampling probability: " + " ".join(f"{c}:{probe.prob[c]:.4f}" for c in probe.classes)
+            + (f"; dropped (no frame with more than {plan.rcs_kw['min_pixels']} pixels): {', '.join(map(str, probe.dropped))}"
+               if probe.dropped else "; no class dropped")]
+    if unl_set is not None and len(unl_set) < plan.batch:
+        raise SystemExit(f"[train] --self-training: the unlabelled set holds {len(unl_set)} frames, fewer than one batch of {plan.batch}")
+    for line in plan.say:
+        for text in slots.get(line, [line.replace("{unlabelled}", str(len(unl_set or ())))]):
+            print(text)
+    return types.SimpleNamespace(
+        args=args, plan=plan, seg=seg, fus=fus, train_set=train_set, val_set=val_set, unl_set=unl_set, stats=stats, seg_crit=seg_crit,
+        crit=torch.nn.CrossEntropyLoss(ignore_index=255), fusion_loss=make_fusion_loss(args.fusion_loss) if args.fusion_loss else None,
+        seg_initial=seg_initial, seg_path=os.path.join(args.out, SEG_CKPT), fus_path=os.path.join(args.out, FUSION_CKPT),
+        best=None, wrote_seg=False, opt=None, seg_state=seg_initial, fused_set=None, fused_unl=None)
 
-    st_kw = None
-    if args.self_training:
+
+def _averaged(on, optimizer, net):
+    """`net` on the weight average that `optimizer` keeps, for the span of a `with` block - where `on`"""
+    if not on:
+        return contextlib.nullcontext()
+    from .utils.optimizer import ema_weights
+    return ema_weights(optimizer, net)
+
+
+def _loader(run, dataset, phase, seed, **kw):
+    """the batches of `phase` over `dataset`, with the plan's sampler and ClassMix where the phase has them"""
+    from .data import AugmentedBatches, ClassMix, RareClassSampler
+    sampler = RareClassSampler(run.stats, range(len(dataset)), seed=seed, **run.plan.rcs_kw) if phase in run.plan.rcs_phases else None
+    mix = ClassMix(seed=seed, **run.plan.mix_kw) if phase in run.plan.mix_phases else None
+    return AugmentedBatches(dataset, seed=seed, sampler=sampler, mix=mix, **run.plan.loader_kw, **kw)
+
+
+def _logger(run, optimizer, modules, batches, *first):
+    """-> log(prefix): print the prefix and what each part's line() adds - `first`, the guard's, the loader's two tallies - and stop
+    the run where the guard says so"""
+    guard = [_GuardLog(optimizer, modules, run.args.max_consecutive_skips)] if run.plan.guarded else []
+    parts = [*first, *guard, _TallyLog(" rcs drawn/hit ", batches.rcs_tally if batches.sampler is not None else None),
+             _TallyLog(" mix sel/px ", batches.mix_tally if batches.mix is not None else None)]
+
+    def log(prefix):
+        print(prefix + "".join(part.line() for part in parts))
+        for g in guard:
+            g.check()
+    return log
+
+
+def fusion_phase(run, iter_):
+    """Round iter_'s fusion phase (train.py:266-413): leaves the fusion checkpoint and the sets fused by it.  The segmentation net
+    it trains against holds the INITIAL weights until round 2 (train.py:307 loads the checkpoint only when iter_ > 2), afterwards
+    the BEST checkpoint if one was written - if none was, what the last segmentation phase left."""
+    from .data import DeviceDataset
+    args, plan, seg, fus, train_set = run.args, run.plan, run.seg, run.fus, run.train_set
+    print(f"[train] round {iter_}: fusion")
+    if iter_ <= 2:
+        seg.load_state_dict(run.seg_initial)
+    elif run.wrote_seg:
+        seg.load_state_dict(torch.load(run.seg_path, map_location="cuda"))
+    trainer = FusionTrainer(seg, fus, make_fusion_optimizer(fus, iter_, **plan.fusion_opt_kw), run.crit, iter_=iter_,
+                            fusion_loss=run.fusion_loss)
+    batches = _loader(run, train_set, "fusion", args.seed + 2 * iter_)
+    log = _logger(run, trainer.opt, [("fusion_net", fus)], batches)
+    n_fus = plan.fusion_iters[iter_ - 1]
+    for n in range(n_fus):
+        _, ir3, vis3, mask3, label = next(batches)
+        loss = trainer.step(ir3, vis3, mask3, label)
+        if (n + 1) % args.log_iters == 0 or n + 1 == n_fus:
+            log(f"[train] round {iter_} fusion iter {n + 1}/{n_fus}: loss {float(loss):.6f}")
+        if (n + 1) % 500 == 0:
+            with _averaged(plan.ema_fus, trainer.opt, fus):
+                torch.save(fus.state_dict(), run.fus_path)
+    with _averaged(plan.ema_fus, trainer.opt, fus):
+        torch.save(fus.state_dict(), run.fus_path)
+        fused = _fused_frames(seg, fus, train_set, plan.batch)
+        run.fused_unl = _fused_frames(seg, fus, run.unl_set, plan.batch) if run.unl_set is not None else None
+    run.fused_set = DeviceDataset(train_set.names, train_set.ir, fused, train_set.mask, train_set.label)
+
+
+def seg_phase(run, iter_):
+    """Round iter_'s segmentation phase (train.py:115-245) on the frames the fusion phase fused: validates, and writes the
+    segmentation checkpoint when the mIoU improved.  It starts from the BEST checkpoint if one was written and the round is above 1
+    (train.py:159-160), otherwise from the state the previous segmentation phase left (in round 1: the initial weights)."""
+    args, plan, seg, fus, unl = run.args, run.plan, run.seg, run.fus, run.unl_set
+    print(f"[train] round {iter_}: segmentation")
+    seg.load_state_dict(torch.load(run.seg_path, map_location="cuda") if (run.wrote_seg and iter_ > 1) else run.seg_state)
+    opt = run.opt = make_seg_optimizer(seg, iter_curr=(iter_ - 1) * 10000, **plan.seg_opt_kw)
+    if run.best is None:
+        with _averaged(plan.ema_seg, opt, seg):  # (no step yet: no average yet, the weights as they are)
+            run.best = _miou(seg, fus, run.val_set, plan.batch)
+        print(f"[train] initial mIoU {run.best:.4f}")
+    seed = args.seed + 2 * iter_ + 1
+    batches = _loader(run, run.fused_set, "seg", seed, photometric=())
+    st, unsup, first = None, None, []
+    if plan.st_kw is not None:  # the unlabelled frames, fused as the labelled ones are, walked by a loader of their own
+        from .data import AugmentedBatches, ClassMix, DeviceDataset
         from .selftrain import EmaTeacher, SelfTrainingStep
-        st_kw = dict(tau=0.968 if args.st_threshold is None else args.st_threshold, below=args.st_below or "keep",
-                     unsup_weight=1.0 if args.st_weight is None else args.st_weight)
-        st_mix_kw = dict(prob=1.0 if args.st_mix_prob is None else args.st_mix_prob, classes="half",
-                         min_pixels=0 if args.st_mix_min_pixels is None else args.st_mix_min_pixels, n_class=n_class) if args.st_mix else None
-        if len(unl_set) < batch:
-            raise SystemExit(f"[train] --self-training: the unlabelled set holds {len(unl_set)} frames, fewer than one batch of {batch}")
-        print(f"[train] --self-training ({', '.join(f'{k} {v}' for k, v in st_kw.items())}; {len(unl_set)} unlabelled frames"
-              + (f"; --st-mix {', '.join(f'{k} {v}' for k, v in st_mix_kw.items())}" if args.st_mix else "") + "): this project's addition, "
-              "NOT the reference's training (its train.py uses labelled frames only).  DAFormer-style: the weight average is the "
-              "teacher, its argmax on an unlabelled batch the pseudo-label, the share of pixels above the threshold the weight of a "
-              "mean-over-all-pixels CE added to the labelled loss; no feature-distance term, one domain, the teacher's BatchNorm "
-              "buffers copied from the student.  Segmentation phase only.  Nothing here says what it does to mIoU: that takes a run "
-              "on a data set")
+        unl_batches = AugmentedBatches(DeviceDataset(unl.names, unl.ir, run.fused_unl, unl.mask, unl.label), seed=seed + 7919,
+                                       photometric=(), **plan.loader_kw)
+        st = SelfTrainingStep(seg, EmaTeacher(opt, seg), opt, run.seg_crit,
+                              mix=ClassMix(seed=seed + 7919, **plan.st_mix_kw) if plan.st_mix_kw else None, **plan.st_kw)
+        first = [types.SimpleNamespace(line=lambda: f" unlabelled {float(unsup):.6f} confident {st.confident_share():.4f}")]
+    log = _logger(run, opt, [("seg_net", seg)], batches, *first)  # (`unsup`: the last step's, below)
+    n_seg = plan.seg_iters[iter_ - 1]
+    for n in range(n_seg):
+        _, _, fused3, _, label = next(batches)
+        if st is None:
+            loss = seg_train_step(seg, opt, fused3, label, run.seg_crit)
+        else:
+            loss, unsup = st.step(fused3, label, next(unl_batches)[2])
+        if (n + 1) % args.log_iters == 0 or n + 1 == n_seg:
+            log(f"[train] round {iter_} segmentation iter {n + 1}/{n_seg}: lr {opt.param_groups[0]['lr']:.3e} loss {float(loss):.6f}")
+        if (n + 1) % 1000 == 0 or n + 1 == n_seg:
+            with _averaged(plan.ema_seg, opt, seg):
+                miou = _miou(seg, fus, run.val_set, plan.batch)
+                if miou > run.best:  # (train.py:237: only an improvement is written)
+                    torch.save(seg.state_dict(), run.seg_path)
+                    run.best, run.wrote_seg = miou, True
+            print(f"[train] round {iter_} segmentation iter {n + 1}: mIoU {miou:.4f} (best {run.best:.4f})")
+    run.seg_state = {k: v.clone() for k, v in seg.state_dict().items()}
 
-    def loader(dataset, phase, seed, **kw):
-        sampler = RareClassSampler(stats, range(len(dataset)), seed=seed, **rcs_kw) if phase in rcs_phases else None
-        mix = ClassMix(seed=seed, **mix_kw) if phase in mix_phases else None
-        return AugmentedBatches(dataset, seed=seed, sampler=sampler, mix=mix, **loader_kw, **kw)
-    best, wrote_seg, opt = None, False, None
-    fusion_loss = make_fusion_loss(args.fusion_loss) if args.fusion_loss is not None else None
-    if fusion_loss is not None:
-        print(f"[train] --fusion-loss {args.fusion_loss}: NOT the reference's schedule of objectives")
+
+def main(argv=None):
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    check_args(args, ap.error)
+    resolve_defaults(args)
+    if not torch.cuda.is_available():
+        raise RuntimeError("segmif_amd.train needs the MI355X device (the HIP path has no CPU fallback)")
+    run = _build_run(args, make_plan(args))
     for iter_ in range(1, args.rounds + 1):
-        # ---- fusion phase (train.py:266-413).  Its segmentation net is a freshly built one until round 3 (:307: the checkpoint is
-        # loaded only when iter_ > 2), then the best checkpoint so far.
-        print(f"[train] round {iter_}: fusion")
-        seg_state = {k: v.clone() for k, v in seg.state_dict().items()}
-        if iter_ <= 2:
-            seg.load_state_dict(seg_initial)
-        elif wrote_seg:
-            seg.load_state_dict(torch.load(seg_path, map_location="cuda"))
-        trainer = FusionTrainer(seg, fus, make_fusion_optimizer(fus, iter_, lr=args.lr, **sched, **(ema_kw if ema_fus else {})), crit,
-                                iter_=iter_, fusion_loss=fusion_loss)
-        glog = _GuardLog(trainer.opt, [("fusion_net", fus)], args.max_consecutive_skips) if guarded else None
-        batches = loader(train_set, "fusion", args.seed + 2 * iter_)
-        rlog, mlog = _RcsLog(batches), _MixLog(batches)
-        n_fus = args.fusion_iters if args.fusion_iters is not None else (6000 if iter_ == 1 else 4000)
-        for n in range(n_fus):
-            _, ir3, vis3, mask3, label = next(batches)
-            loss = trainer.step(ir3, vis3, mask3, label)
-            if (n + 1) % args.log_iters == 0 or n + 1 == n_fus:
-                print(f"[train] round {iter_} fusion iter {n + 1}/{n_fus}: loss {float(loss):.6f}" + (glog.line() if guarded else "")
-                      + rlog.line() + mlog.line())
-                if guarded:
-                    glog.check()
-            if (n + 1) % 500 == 0:
-                with averaged(ema_fus, trainer.opt, fus):
-                    torch.save(fus.state_dict(), fus_path)
-        with averaged(ema_fus, trainer.opt, fus):
-            torch.save(fus.state_dict(), fus_path)
-            fused = _fused_frames(seg, fus, train_set, batch)
-            fused_unl = _fused_frames(seg, fus, unl_set, batch) if st_kw is not None else None
-        fused_set = DeviceDataset(train_set.names, train_set.ir, fused, train_set.mask, train_set.label)
-        # ---- segmentation phase (train.py:115-245) on the fused training frames, from the best checkpoint so far (:159-160)
-        print(f"[train] round {iter_}: segmentation")
-        seg.load_state_dict(torch.load(seg_path, map_location="cuda") if (wrote_seg and iter_ > 1) else seg_state)
-        opt = make_seg_optimizer(seg, iter_curr=(iter_ - 1) * 10000, lr=args.lr, warmup_iter=args.warmup_iter, **sched,
-                                 **(ema_kw if ema_seg else {}))
-        if best is None:
-            with averaged(ema_seg, opt, seg):  # (no step yet: no average yet, the weights as they are)
-                best = _miou(seg, fus, val_set, batch)
-            print(f"[train] initial mIoU {best:.4f}")
-        glog = _GuardLog(opt, [("seg_net", seg)], args.max_consecutive_skips) if guarded else None
-        batches = loader(fused_set, "seg", args.seed + 2 * iter_ + 1, photometric=())
-        rlog, mlog = _RcsLog(batches), _MixLog(batches)
-        st = None
-        if st_kw is not None:  # the unlabelled frames, fused as the labelled ones are, walked by a loader of their own
-            unl_batches = AugmentedBatches(DeviceDataset(unl_set.names, unl_set.ir, fused_unl, unl_set.mask, unl_set.label),
-                                           seed=args.seed + 2 * iter_ + 1 + 7919, photometric=(), **loader_kw)
-            st = SelfTrainingStep(seg, EmaTeacher(opt, seg), opt, seg_crit,
-                                  mix=ClassMix(seed=args.seed + 2 * iter_ + 1 + 7919, **st_mix_kw) if st_mix_kw else None, **st_kw)
-        n_seg = args.seg_iters if args.seg_iters is not None else 10000
-        for n in range(n_seg):
-            _, _, fused3, _, label = next(batches)
-            if st is None:
-                loss = seg_train_step(seg, opt, fused3, label, seg_crit)
-            else:
-                loss, loss_unsup = st.step(fused3, label, next(unl_batches)[2])
-            if (n + 1) % args.log_iters == 0 or n + 1 == n_seg:
-                print(f"[train] round {iter_} segmentation iter {n + 1}/{n_seg}: lr {opt.param_groups[0]['lr']:.3e} loss {float(loss):.6f}"
-                      + (f" unlabelled {float(loss_unsup):.6f} confident {st.confident_share():.4f}" if st is not None else "")
-                      + (glog.line() if guarded else "") + rlog.line() + mlog.line())
-                if guarded:
-                    glog.check()
-            if (n + 1) % 1000 == 0 or n + 1 == n_seg:
-                with averaged(ema_seg, opt, seg):
-                    miou = _miou(seg, fus, val_set, batch)
-                    if miou > best:  # (train.py:237: only an improvement is written)
-                        torch.save(seg.state_dict(), seg_path)
-                        best, wrote_seg = miou, True
-                print(f"[train] round {iter_} segmentation iter {n + 1}: mIoU {miou:.4f} (best {best:.4f})")
-    if not wrote_seg:
+        fusion_phase(run, iter_)
+        seg_phase(run, iter_)
+    if not run.wrote_seg:
         # no validation ever beat the initial mIoU: the reference would leave no segmentation checkpoint; the last state is written
         # here, after the last round, so that a run leaves both files and no round has loaded a state that was not an improvement
-        with averaged(ema_seg and opt is not None, opt, seg):  # the last AVERAGED state
-            torch.save(seg.state_dict(), seg_path)
-        print(f"[train] no segmentation state improved on the initial mIoU {best:.4f}: {seg_path} holds the LAST state, not a best one")
-    print(f"[train] wrote {seg_path} and {fus_path}")
+        with _averaged(run.plan.ema_seg and run.opt is not None, run.opt, run.seg):  # the last AVERAGED state
+            torch.save(run.seg.state_dict(), run.seg_path)
+        print(f"[train] no segmentation state improved on the initial mIoU {run.best:.4f}: {run.seg_path} holds the LAST state, not a best one")
+    print(f"[train] wrote {run.seg_path} and {run.fus_path}")
     return 0
 
 

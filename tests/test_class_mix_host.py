@@ -203,7 +203,10 @@ REFUSED = [(["--class-mix-prob", "0.5"], "--class-mix,"), (["--class-mix-min-pix
            (BASE + ["--class-mix-classes", "wanted", "--rare-class-sampling", "--class-mix-phases", "both"], "the fusion phase has no rare-class sampling"),
            (BASE + ["--class-mix-classes", "wanted", "--rare-class-sampling", "--rcs-phases", "fusion"], "the seg phase has no rare-class sampling"),
            (BASE + ["--class-mix-classes", "all"], "invalid choice"), (BASE + ["--class-mix-phases", "val"], "invalid choice"),
-           (BASE + ["--samples-per-gpu", "2"], "--samples-per-gpu 2: the loaders"), (BASE + ["--samples-per-gpu", "3"], "--samples-per-gpu 3: the loaders")]
+           (BASE + ["--samples-per-gpu", "2"], "--samples-per-gpu 2: the loaders"), (BASE + ["--samples-per-gpu", "3"], "--samples-per-gpu 3: the loaders"),
+           # (what needs no device is refused before the device check too)
+           (["--root", "somewhere"], "give either --root DIR --name-lists DIR or --synthetic N"),
+           (["--fusion-loss", "Nothing"], "--fusion-loss Nothing: one of Fusionloss"), (["--backbone", "mit_b0"], "--backbone mit_b0: Fusion_Network3_ac")]
 
 
 @pytest.mark.parametrize("argv,needle", REFUSED)
@@ -213,6 +216,14 @@ def test_train_refuses_before_the_device_check(argv, needle, capsys):
         train.main(["--synthetic", "4"] + argv)
     err = capsys.readouterr().err
     assert exc.value.code == 2 and "error:" in err and needle in err
+
+
+def test_train_refuses_a_root_without_name_lists_before_the_device_check(capsys):
+    """(the one refusal the cases above cannot reach: they all train on --synthetic frames)"""
+    from segmif_amd import train
+    with pytest.raises(SystemExit) as exc:
+        train.main(["--root", "somewhere"])
+    assert exc.value.code == 2 and "error: --root needs --name-lists" in capsys.readouterr().err
 
 
 def test_command_line_help_names_the_flags(capsys):
