@@ -741,6 +741,39 @@ int segmif_class_mix_apply_f32(const float* ir3, const float* vis3, const float*
                                const int32_t* sel, int B, int h, int w, int n_class, float* ir3_out, float* vis3_out,
                                float* mask3_out, int64_t* label_out, void* stream);
 
+/* Contour scores of a segmentation: the integer tables behind Boundary IoU (Cheng et al., CVPR 2021), the trimap-band mIoU
+ * (Kohli et al. 2009) and the boundary F-score (Csurka et al., BMVC 2013), in one pass over a prediction and its ground truth
+ * (csrc/boundary_stats.hip).  NOT the reference's evaluation, which reports the plain mIoU only.  The rule:
+ *
+ * Inputs: pred (B, H, W) int32, label (B, H, W) int64, K in 1..32 classes, the band half-width d in 1..32 and the contour
+ * tolerance theta in 0..31.  All distances are Chebyshev distances: every window is a square.
+ *   - g(y, x) = label(y, x) when that value lies in 0..K-1, compared on the full 64 bits; otherwise IGN.  255, -1, 256 and
+ *     2^40 + 3 are all IGN.
+ *   - p(y, x) = pred(y, x) when g(y, x) != IGN and pred(y, x) lies in 0..K-1; otherwise IGN: the prediction is blanked wherever
+ *     the ground truth is ignored.
+ *   - IGN is a value like any other when two positions are compared; a position that holds it is never counted.
+ *   - uniform_d(m; y, x) holds iff every (y', x') with |y' - y| <= d and |x' - x| <= d lies inside the frame and m(y', x') ==
+ *     m(y, x).  A window that leaves the frame is not uniform.
+ *   - band_d(m) = {(y, x) : m(y, x) != IGN and not uniform_d(m; y, x)}.  For a class c, band_d(m) intersected with {m == c} is
+ *     mask_c - erode(mask_c) with a 3 x 3 structuring element of ones, d iterations and the frame padded with zeros: the
+ *     mask_to_boundary of the Boundary IoU authors.
+ *   - contour(m) = {(y, x) : m(y, x) != IGN and some position INSIDE the frame within distance 1 holds a different value}.
+ *     Positions outside the frame are skipped: the frame's own border is not a contour.
+ *   - near_theta(S) = the positions that have a member of S within distance theta inside the frame.
+ * Outputs, per frame, both int64 and both zeroed by the call on `stream`:
+ *   cls (B, K, 8), row c: [0] g_band = |band_d(g) & {g = c}|, [1] p_band = |band_d(p) & {p = c}|, [2] band_inter = the size
+ *     of the intersection of those two sets, [3] g_contour = |GC_c| with GC_c = contour(g) & {g = c}, [4] p_contour = |PC_c|
+ *     with PC_c = contour(p) & {p = c}, [5] g_matched = |GC_c & near_theta(PC_c)|, [6] p_matched = |PC_c & near_theta(GC_c)|,
+ *     [7] reserved, 0.
+ *   trimap (B, K, K): trimap[t][q] = #{(y, x) in band_d(g) : g = t, p = q}; rows = ground truth, as segmif_confusion_i32 has them.
+ * Exact integers (LDS and global integer atomics, no floating point), so the tables are the same in every run; frame b's tables
+ * depend on frame b only.  One workgroup per SEGMIF_BOUNDARY_TILE x SEGMIF_BOUNDARY_TILE tile of a frame.  Any H, W >= 1,
+ * frames smaller than the window included; nothing is demanded of W.  SEGMIF_EINVAL before any launch: a null pointer, B, H or
+ * W < 1, K outside 1..32, d outside 1..32, theta outside 0..31, cls or trimap not 8-byte aligned (label: 8, pred: 4), more than 2^31 - 1 tiles in the batch. */
+#define SEGMIF_BOUNDARY_TILE 64
+int segmif_boundary_stats_i32(const int32_t* pred, const int64_t* label, int B, int H, int W, int K, int d, int theta,
+                              int64_t* cls, int64_t* trimap, void* stream);
+
 /* Pseudo-labels for self-training (the EMA teacher of DAFormer, Hoyer et al. 2022; mean teacher, Tarvainen & Valpola 2017), in one
  * pass from the teacher's NHWC logits x (B, IH, IW, C), pixel pitch ldx >= C, to full resolution (csrc/pseudo_label.hip).  NOT the
  * reference's training, which uses labelled frames only.  The (B, OH, OW, C) resized logits are never written.  The rule, per

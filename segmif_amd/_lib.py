@@ -209,6 +209,7 @@ SIGNATURES = {
                                              c_void_p, c_void_p, c_int, c_void_p]),
     "segmif_label_stats_u8": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p]),
     "segmif_label_stats_i64": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p]),
+    "segmif_boundary_stats_i32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "segmif_class_mix_select": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "segmif_class_mix_apply_f32": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p] * 5),
     "segmif_augment_apply_u8": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int]

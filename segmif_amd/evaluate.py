@@ -4,12 +4,16 @@
     python -m segmif_amd.evaluate --ir DIR --vis DIR --mask DIR [--label DIR] --out DIR [--backbone mit_b3]
         [--seg-ckpt F] [--fusion-ckpt F] [--batch N] [--json F] [--structural-scores]
         [--ms-scales S [S ...]] [--flip] [--size-divisor N]
+        [--boundary-scores [--boundary-width D] [--bf-tolerance T] [--boundary-ratio R] [--bf-ratio R]]
 
 reads the sorted file names of --vis (TaskFusion_dataset2.py:40-48) from every folder (.npy always, .png when PIL imports),
 and writes OUT/Fused/NAME, OUT/Seg/NAME (palette rendering) and a JSON of the results.  --structural-scores adds Qabf, SSIM and
 VIF (utils/fusion_metrics.structural_scores; images of at least 41 x 41) to the JSON and to the summary line.  --ms-scales and
 --flip (alone: scales 1.0) take the labels, and so the mIoU, from multi-scale + flip inference (segmif_amd.tta; the JSON then
-names the views under "tta"); the fused images and their scores do not change.
+names the views under "tta"); the fused images and their scores do not change.  --boundary-scores (with --label) adds the
+contour scores of the label maps: Boundary IoU, the trimap-band mIoU and the boundary F-score (utils/metrics.boundary_scores;
+the JSON names the widths under "boundary"); the widths follow the frame's diagonal unless --boundary-width / --bf-tolerance
+give them in pixels.
 """
 import argparse
 import json
@@ -24,7 +28,8 @@ from .pipeline import PairForward
 from .tta import TTA
 from .utils.fusion_metrics import (MFNET_PALETTE, SCORE_NAMES, STRUCTURAL_SCORE_NAMES, colorize, fusion_scores, fusion_stats,
                                    structural_scores, structural_stats)
-from .utils.metrics import _dev, _stream, compute_results, confusion_matrix
+from .utils.metrics import (_dev, _stream, boundary_scores, boundary_stats, boundary_widths, compute_results,
+                            confusion_matrix)
 
 
 def _dequantize(u8_nhwc):
@@ -44,9 +49,11 @@ class Evaluator:
     """Accumulates the evaluation of (infrared, visible, mask) uint8 batches through PairForward(uint8_roundtrip=True,
     return_u8=True): the min-max rescale of the fused image is per call = per batch, as the reference's is.  structural=True also
     gathers Qabf, SSIM and VIF (STRUCTURAL_SCORE_NAMES) of every pair.  tta: a segmif_amd.tta.TTA - the labels (and the mIoU)
-    come from multi-scale + flip inference (PairForward(tta=)); not with graph=True."""
+    come from multi-scale + flip inference (PairForward(tta=)); not with graph=True.  boundary: None, or a dict with any of d,
+    theta (widths in pixels) and ratio, bf_ratio (utils/metrics.boundary_widths; a width not given follows the frame's
+    diagonal) - the contour tables of utils/metrics.boundary_stats are then summed over every labelled batch."""
 
-    def __init__(self, seg_net, fusion_net, n_class=9, graph=False, structural=False, tta=None):
+    def __init__(self, seg_net, fusion_net, n_class=9, graph=False, structural=False, tta=None, boundary=None):
         if tta is not None and graph:
             raise NotImplementedError("Evaluator: graph=True cannot capture the multi-size forward (tta=)")
         self.pair = PairForward(seg_net, fusion_net, uint8_roundtrip=True, return_u8=True, tta=tta)
@@ -59,6 +66,27 @@ class Evaluator:
         self._scores = []
         self.structural = structural
         self._structural = []
+        if boundary is not None and set(boundary) - {"d", "theta", "ratio", "bf_ratio"}:
+            raise ValueError(f"Evaluator: boundary= takes d, theta, ratio and bf_ratio, got {sorted(boundary)}")
+        self.boundary = None if boundary is None else dict(boundary)
+        self._boundary = None        # (cls_total, trimap_total) on the device
+        self._boundary_doc = None    # {"d", "theta", "frame"} of the first labelled batch
+
+    def _boundary_update(self, labels, label):
+        H, W = (int(v) for v in labels.shape[1:])
+        d, theta = boundary_widths(H, W, self.boundary.get("ratio", 0.02), self.boundary.get("bf_ratio", 0.0075))
+        d = d if self.boundary.get("d") is None else int(self.boundary["d"])
+        theta = theta if self.boundary.get("theta") is None else int(self.boundary["theta"])
+        doc = {"d": d, "theta": theta, "frame": [H, W]}
+        if self._boundary_doc is None:
+            self._boundary_doc = doc
+            self._boundary = (torch.zeros((self.n_class, 8), device=labels.device, dtype=torch.int64),
+                              torch.zeros((self.n_class, self.n_class), device=labels.device, dtype=torch.int64))
+        elif doc != self._boundary_doc and (self.boundary.get("d") is None or self.boundary.get("theta") is None):
+            raise RuntimeError(f"Evaluator: a batch of {H} x {W} frames after {self._boundary_doc['frame'][0]} x "
+                               f"{self._boundary_doc['frame'][1]} ones, with boundary widths that follow the frame size: the scores would "
+                               "mix bands; fix both widths (boundary=dict(d=, theta=), --boundary-width and --bf-tolerance)")
+        boundary_stats(labels, label, self.n_class, d, theta, out=self._boundary)
 
     def update(self, ir_u8, vis_u8, mask_u8, label=None):
         """ir_u8 (B, H, W), vis_u8 (B, H, W, 3), mask_u8 (B, H, W) uint8 and optionally label (B, H, W) int64, all on the device
@@ -87,14 +115,18 @@ class Evaluator:
             if self.structural:
                 self._structural.append(structural_stats(fused_u8, vis_u8, ir_u8))
             if label is not None:
-                self._conf = confusion_matrix(labels, _dev(label, "label", torch.int64), self.n_class, out=self._conf)
+                label = _dev(label, "label", torch.int64)
+                self._conf = confusion_matrix(labels, label, self.n_class, out=self._conf)
+                if self.boundary is not None:
+                    self._boundary_update(labels.contiguous(), label.reshape(labels.shape))
         return fused_u8, labels
 
     def results(self):
         """-> dict: every score of SCORE_NAMES as a per-image float64 array, 'mean' (name -> NaN-ignoring mean over the images)
         and, when labels were given, 'precision' / 'recall' / 'iou' per class (compute_results) and 'mIoU' =
         mean(nan_to_num(iou)), the figure test_segmentation.py prints for data that lack a class.  With structural=True the
-        scores of STRUCTURAL_SCORE_NAMES are added in the same two places."""
+        scores of STRUCTURAL_SCORE_NAMES are added in the same two places; with boundary= and labels, the keys of
+        utils/metrics.boundary_scores."""
         per = [fusion_scores(s) for s in self._scores]
         names = SCORE_NAMES
         if self.structural:
@@ -105,12 +137,14 @@ class Evaluator:
         if self._conf is not None:
             precision, recall, iou = compute_results(self._conf)
             out.update(precision=precision, recall=recall, iou=iou, mIoU=float(np.mean(np.nan_to_num(iou))))
+        if self._boundary is not None:
+            out.update(boundary_scores(*self._boundary))
         return out
 
     def document(self, names, seeded_weights, res=None):
         """What the command line writes as JSON: the names, which networks ran on seeded weights, results() (or `res`, if the
-        caller has them) with arrays as lists and - only with tta - its settings and the views of the last batch's frame size
-        under "tta"."""
+        caller has them) with arrays as lists, - only with tta - its settings and the views of the last batch's frame size
+        under "tta" and - only with boundary= and labels - the widths and the frame size they were derived for under "boundary"."""
         doc = {"names": list(names), "seeded_weights": list(seeded_weights)}
         for k, v in (self.results() if res is None else res).items():
             doc[k] = v.tolist() if isinstance(v, np.ndarray) else v
@@ -118,6 +152,8 @@ class Evaluator:
             if self._frame is None:
                 raise RuntimeError("Evaluator.document: no batch has been evaluated, the views have no size yet")
             doc["tta"] = self.tta.describe(*self._frame)
+        if self._boundary_doc is not None:
+            doc["boundary"] = dict(self._boundary_doc)
         return doc
 
 
@@ -167,7 +203,19 @@ def parse_args(argv=None):
                     help="multi-scale inference: one forward per scale of the frame (SegFormer's protocol: 0.5 0.75 1.0 1.25 1.5 1.75)")
     ap.add_argument("--flip", action="store_true", help="also vote every scale's mirrored view (alone: scale 1.0)")
     ap.add_argument("--size-divisor", type=int, default=8, metavar="N", help="view sizes are rounded up to a multiple of N (default 8)")
+    ap.add_argument("--boundary-scores", action="store_true",
+                    help="also report Boundary IoU, the trimap-band mIoU and the boundary F-score of the label maps (needs --label)")
+    ap.add_argument("--boundary-width", type=int, metavar="D", help="band half-width in pixels, 1..32 (default: --boundary-ratio x the diagonal)")
+    ap.add_argument("--bf-tolerance", type=int, metavar="T", help="contour tolerance in pixels, 0..31 (default: --bf-ratio x the diagonal)")
+    ap.add_argument("--boundary-ratio", type=float, metavar="R", help="band half-width as a share of the frame's diagonal (default 0.02)")
+    ap.add_argument("--bf-ratio", type=float, metavar="R", help="contour tolerance as a share of the frame's diagonal (default 0.0075)")
     args = ap.parse_args(argv)
+    given = [f for f, v in (("--boundary-width", args.boundary_width), ("--bf-tolerance", args.bf_tolerance),
+                            ("--boundary-ratio", args.boundary_ratio), ("--bf-ratio", args.bf_ratio)) if v is not None]
+    if args.boundary_scores and not args.label:
+        ap.error("--boundary-scores compares the label maps with the ground truth: it needs --label")
+    if given and not args.boundary_scores:
+        ap.error(f"{', '.join(given)} only with --boundary-scores")
     tta = None
     if args.ms_scales is not None or args.flip:
         tta = TTA(tuple(args.ms_scales) if args.ms_scales is not None else (1.0,), args.flip, args.size_divisor)
@@ -176,6 +224,14 @@ def parse_args(argv=None):
         except ValueError as e:
             ap.error(str(e))
     return args, tta
+
+
+def boundary_settings(args):
+    """the Evaluator's boundary= for a parsed command line: None without --boundary-scores, else the flags that were given"""
+    if not args.boundary_scores:
+        return None
+    pairs = (("d", args.boundary_width), ("theta", args.bf_tolerance), ("ratio", args.boundary_ratio), ("bf_ratio", args.bf_ratio))
+    return {k: v for k, v in pairs if v is not None}
 
 
 def main(argv=None):
@@ -192,7 +248,7 @@ def main(argv=None):
         else:
             print(f"[evaluate] no checkpoint for the {what} network: running on SEEDED RANDOM weights (torch.manual_seed(0))")
     seg, fus = seg.cuda().eval(), fus.cuda().eval()
-    ev = Evaluator(seg, fus, structural=args.structural_scores, tta=tta)
+    ev = Evaluator(seg, fus, structural=args.structural_scores, tta=tta, boundary=boundary_settings(args))
     names = _names(args.vis)
     if not names:
         raise RuntimeError(f"no .npy / .png files in {args.vis}")
@@ -217,7 +273,8 @@ def main(argv=None):
     path = args.json or os.path.join(args.out, "results.json")
     with open(path, "w") as f:
         json.dump(doc, f, indent=1)
-    print("[evaluate] " + "  ".join(f"{k} {res['mean'][k]:.4f}" for k in res["mean"]) + (f"  mIoU {res['mIoU']:.4f}" if "mIoU" in res else ""))
+    print("[evaluate] " + "  ".join(f"{k} {res['mean'][k]:.4f}" for k in res["mean"]) + (f"  mIoU {res['mIoU']:.4f}" if "mIoU" in res else "")
+          + (f"  mBIoU {res['mBIoU']:.4f}  trimap {res['trimap_mIoU']:.4f}  mBF {res['mBF']:.4f}" if "mBIoU" in res else ""))
     print(f"[evaluate] wrote {path}")
     return 0
 
