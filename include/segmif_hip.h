@@ -795,6 +795,59 @@ int segmif_boundary_stats_i32(const int32_t* pred, const int64_t* label, int B, 
 int segmif_pseudo_label_f32(const float* x, int64_t* labels, float* conf_or_null, int64_t* count, int B, int IH, int IW, int OH,
                             int OW, int C, int ldx, float tau, int below_ignore, int ignore_index, void* stream);
 
+/* Strong augmentation of the student's unlabelled batch in self-training (DAFormer's strong_transform, Hoyer et al. 2022: colour
+ * jitter, then a Gaussian blur; csrc/strong_augment.hip).  NOT the reference's training.  The constants a policy draws are
+ * DAFormer's; the formulas are this project's and are stated here.  The rule:
+ *
+ * Input x (B, 3, h, w) fp32, contiguous, 16-byte aligned, w % 4 == 0, values nominally in [0, 1] (what segmif_augment_apply_u8 and
+ * segmif_class_mix_apply_f32 write, mean-colour padding included).  Output y, the same shape, a new tensor (out of place; y must
+ * not overlap x), and mean (B,) fp32.  One record per sample, 16 words; `reserved` is zero.
+ *
+ * Jitter (jitter_on != 0).  All arithmetic is float32, every product and sum rounded on its own (no fused multiply-add).
+ * Channels are r, g, b; clamp is to [0, 1]; luma(v) = (0.299 r + 0.587 g) + 0.114 b, its three constants rounded to float32 (they
+ * are part of the rule, as the record's factors and taps are).  Four operations in this fixed order
+ * (kornia's, which DAFormer uses), with torchvision's float formulas:
+ *   1. Brightness: v = clamp(fb v).
+ *   2. Contrast:   v = clamp(fc v + (1 - fc) m_b).  m_b is the sum of luma(v) over the h w pixels of the brightness-adjusted
+ *      sample, taken in double, divided by h w, rounded to float32.  The sum runs in one fixed order (a fixed walk per thread, a
+ *      shuffle tree per wave, the waves of a block and then the sample's segmif_strong_augment_blocks(h, w) blocks in index
+ *      order) and uses no float atomics: m_b is the same bits in every run and does not depend on the other samples of the
+ *      batch.  mean[b] = m_b, and 0 for a sample without jitter.
+ *   3. Saturation: v = clamp(fs v + (1 - fs) luma(v)).
+ *   4. Hue, RGB to HSV: mx, mn the max and min of the three channels; eq = (mx == mn), cr = mx - mn; s = cr / (eq ? 1 : mx),
+ *      d = eq ? 1 : cr; (rc, gc, bc) = (mx - (r, g, b)) / d; h = bc - gc where mx == r, (2 + rc) - bc where mx == g and mx != r,
+ *      (4 + gc) - rc otherwise; h = frac(h / 6 + 1), then h = frac(h + fh) with frac(t) = t - floor(t); V = mx.
+ *   5. Hue, HSV to RGB: i = floor(6 h) mod 6, f = 6 h - floor(6 h); p = clamp(V (1 - s)), q = clamp(V (1 - s f)),
+ *      t = clamp(V (1 - s (1 - f))); (r, g, b) = (V,t,p), (q,V,p), (p,V,t), (p,q,V), (t,p,V), (V,p,q) for i = 0..5.  A sample with
+ *      fh == 0 still goes through the conversion: one rule, no special case.
+ *
+ * Blur (radius in 1..8), after the jitter: every channel is filtered with the separable symmetric kernel w_k = taps[|k|],
+ * |k| <= radius, first along the rows, then along the columns, each pass rounded to float32 and summed as
+ * taps[0] v_0 + taps[1] (v_-1 + v_1) + ... + taps[radius] (v_-radius + v_radius), left to right.  The border is reflected without
+ * repeating the edge: index -i -> i and n - 1 + i -> n - 1 - i (torch's `reflect`, scipy's `mirror`).  A record whose radius lies
+ * outside 0..min(8, h - 1, w - 1) is treated as radius = 0: the kernel never indexes by an unchecked radius.
+ *
+ * A sample with jitter_on == 0 and an effective radius of 0 is copied bit for bit: NaN payloads and -0.0 survive.  Non-finite
+ * input is not special-cased: outputs that depend on it are unspecified, nothing else is affected and nothing faults.
+ *
+ * segmif_strong_augment_blocks(h, w): the partial sums per sample (1..32; SEGMIF_EINVAL for sizes the call refuses).
+ * segmif_strong_augment_f32: partial is a scratch of B * segmif_strong_augment_blocks(h, w) doubles.  Two launches on `stream` (the
+ * mean pass, then one workgroup per SEGMIF_STRONG_TILE_H x SEGMIF_STRONG_TILE_W output tile), no host synchronisation, no atomics.
+ * The factors live on the device and are not checked by the entry point.  SEGMIF_EINVAL before any launch: a null pointer, B < 1
+ * or B > 65535, h < 1, w < 4, w % 4 != 0, x or y not 16-byte aligned, partial not 8-byte aligned, rec or mean not 4-byte aligned. */
+#define SEGMIF_STRONG_TILE_H 32
+#define SEGMIF_STRONG_TILE_W 64
+typedef struct {
+  int32_t jitter_on;
+  float fb, fc, fs, fh;            /* brightness, contrast, saturation factors (>= 0) and the hue shift (|fh| <= 0.5) */
+  int32_t radius;                  /* 0: no blur */
+  float taps[9];                   /* taps[0..radius] */
+  int32_t reserved;                /* zero */
+} SegmifStrongAugRec;
+int segmif_strong_augment_blocks(int h, int w);
+int segmif_strong_augment_f32(const float* x, float* y, const SegmifStrongAugRec* rec, double* partial, float* mean, int B, int h, int w,
+                              void* stream);
+
 /* ----------------------------------------------------------------------------------------------
  * Training path (backward of the ops above; autograd in the reference: loss.backward() at
  * train.py:226, :384).  Contractions reuse segmif_igemm_f32 (input gradients, with transposed /

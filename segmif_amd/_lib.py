@@ -91,6 +91,11 @@ class SegmifAugmentRec(ctypes.Structure):
                 ("taps_x", c_int32), ("taps_y", c_int32), ("reserved", c_int32 * 2)]
 
 
+class SegmifStrongAugRec(ctypes.Structure):
+    _fields_ = [("jitter_on", c_int32), ("fb", c_float), ("fc", c_float), ("fs", c_float), ("fh", c_float), ("radius", c_int32),
+                ("taps", c_float * 9), ("reserved", c_int32)]
+
+
 class SegmifObjTerm(ctypes.Structure):
     _fields_ = [("op", c_int32), ("target", c_int32), ("weight", c_int32), ("rho", c_int32),
                 ("a_ir", c_float), ("a_vis", c_float), ("a_mask", c_float), ("mask_channels", c_int32)]
@@ -330,6 +335,8 @@ SIGNATURES = {
     "segmif_bilinear_argmax_i32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "segmif_pseudo_label_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
                                         c_int, c_int, c_void_p]),
+    "segmif_strong_augment_blocks": (c_int, [c_int, c_int]),
+    "segmif_strong_augment_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "segmif_tta_vote_f32": (c_int, [POINTER(SegmifTtaView), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "segmif_resize_flip_nchw_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
 }

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libsegmif_hip.so")
-SOURCES = ["igemm.hip", "conv3x3.hip", "conv3x3_split.hip", "conv3x3_planes.hip", "gemm_split.hip", "gemm_pairs.hip", "wgrad.hip", "backward.hip", "grad_guard.hip", "weight_ema.hip", "attention.hip", "attention_split.hip", "attention_bwd.hip", "rowops.hip", "tta.hip", "linattn.hip", "crosspath.hip", "metrics.hip", "fusion_stats.hip", "structural_stats.hip", "augment.hip", "label_stats.hip", "boundary_stats.hip", "class_mix.hip", "pseudo_label.hip", "losses.hip", "fusion_objective.hip", "seg_objective.hip", "region_objective.hip", "common.hip", "comm.hip", "mixffn.hip"]
+SOURCES = ["igemm.hip", "conv3x3.hip", "conv3x3_split.hip", "conv3x3_planes.hip", "gemm_split.hip", "gemm_pairs.hip", "wgrad.hip", "backward.hip", "grad_guard.hip", "weight_ema.hip", "attention.hip", "attention_split.hip", "attention_bwd.hip", "rowops.hip", "tta.hip", "linattn.hip", "crosspath.hip", "metrics.hip", "fusion_stats.hip", "structural_stats.hip", "augment.hip", "label_stats.hip", "boundary_stats.hip", "class_mix.hip", "pseudo_label.hip", "strong_augment.hip", "losses.hip", "fusion_objective.hip", "seg_objective.hip", "region_objective.hip", "common.hip", "comm.hip", "mixffn.hip"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I" + os.path.join(ROOT, "include")]
 

@@ -482,6 +482,47 @@ class ClassMix:
         return table
 
 
+class StrongAugment:
+    """The policy of the student's strong augmentation in self-training (DAFormer's strong_transform, Hoyer et al. 2022: colour
+    jitter, then a Gaussian blur) for SelfTrainingStep(strong=); NOT the reference's training.  The constants are DAFormer's:
+    jitter with probability 0.8, brightness, contrast and saturation factors in [1 - 0.2, 1 + 0.2], a hue shift in [-0.2, 0.2], a
+    blur with probability 0.5 whose sigma is uniform over [0.15, 1.15].  The formulas are this project's (include/segmif_hip.h,
+    segmif_strong_augment_f32): the four jitter operations in a fixed order, and taps from ops.strong_taps instead of a kernel
+    size that follows the image's.
+
+    draw(B) builds the table from a private random.Random seeded from (seed, rank); neither the global generators nor the
+    loaders' are touched.  Per sample, in order, all seven values are always drawn - a coin, fb, fc, fs ~ U(1 - strength,
+    1 + strength), fh ~ U(-hue, hue), a coin, sigma ~ U(sigma) - so the stream does not depend on the outcomes."""
+
+    def __init__(self, jitter_prob=0.8, strength=0.2, hue=0.2, blur_prob=0.5, sigma=(0.15, 1.15), seed=0, rank=0):
+        lo, hi = (float(s) for s in sigma)
+        if not (0.0 <= jitter_prob <= 1.0 and 0.0 <= blur_prob <= 1.0 and 0.0 <= strength <= 1.0 and 0.0 <= hue <= 0.5 and 0.0 < lo <= hi <= 2.0):
+            raise ValueError(f"StrongAugment: jitter_prob {jitter_prob} and blur_prob {blur_prob} in [0, 1], strength {strength} in [0, 1], "
+                             f"hue {hue} in [0, 0.5] and 0 < sigma {lo} <= {hi} <= 2 are required")
+        self.jitter_prob, self.strength, self.hue, self.blur_prob, self.sigma = float(jitter_prob), float(strength), float(hue), float(blur_prob), (lo, hi)
+        self.seed, self.rank = seed, rank
+        self._py = random.Random(f"StrongAugment {seed} {rank}")
+
+    def draw(self, B):
+        """-> (B,) records of ops.strong_rec_dtype(); a sample whose coins both fail is copied"""
+        from . import ops
+        if B < 1:
+            raise ValueError(f"StrongAugment: B {B} < 1")
+        table = np.zeros(B, dtype=ops.strong_rec_dtype())
+        u = self._py.uniform
+        for b in range(B):
+            jitter = self._py.random() < self.jitter_prob
+            fb, fc, fs = (u(1.0 - self.strength, 1.0 + self.strength) for _ in range(3))
+            fh = u(-self.hue, self.hue)
+            blur = self._py.random() < self.blur_prob
+            radius, taps = ops.strong_taps(u(*self.sigma))
+            table["jitter_on"][b] = int(jitter)
+            table["fb"][b], table["fc"][b], table["fs"][b], table["fh"][b] = (fb, fc, fs, fh) if jitter else (1.0, 1.0, 1.0, 0.0)
+            table["radius"][b] = radius if blur else 0
+            table["taps"][b] = taps if blur else [1.0] + [0.0] * ops.STRONG_MAX_RADIUS
+        return table
+
+
 # ------------------------------------------------------------------------------------------------------------------ iterator
 
 class AugmentedBatches:

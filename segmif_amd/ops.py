@@ -1663,3 +1663,86 @@ def class_mix(ir3, vis3, mask3, label, table, n_class=9, min_pixels=0, tally=Non
                                               sel.data_ptr(), B, h, w, n_class, *(t.data_ptr() for t in out), _stream()),
                "segmif_class_mix_apply_f32")
     return out + (sel, pasted)
+
+
+STRONG_MAX_RADIUS = 8
+STRONG_TILE = (32, 64)  # SEGMIF_STRONG_TILE_H, SEGMIF_STRONG_TILE_W
+STRONG_REC_WORDS = 16
+
+
+def strong_rec_dtype():
+    """numpy's view of SegmifStrongAugRec (64 bytes): what a host table of strong_augment is made of"""
+    import numpy as np
+    return np.dtype([("jitter_on", np.int32), ("fb", np.float32), ("fc", np.float32), ("fs", np.float32), ("fh", np.float32),
+                     ("radius", np.int32), ("taps", np.float32, (STRONG_MAX_RADIUS + 1,)), ("reserved", np.int32)])
+
+
+def strong_taps(sigma):
+    """The blur's taps for a Gaussian of standard deviation sigma in (0, 2]: R = min(8, ceil(4 sigma)),
+    w_k = exp(-k^2 / (2 sigma^2)) over -R..R normalised in double, rounded to float32 -> (R, taps (9,) float32, zero past R)."""
+    import math
+    import numpy as np
+    sigma = float(sigma)
+    if not 0.0 < sigma <= 2.0:  # (NaN fails too)
+        raise ValueError(f"strong_taps: sigma {sigma} outside (0, 2]")
+    R = min(STRONG_MAX_RADIUS, math.ceil(4.0 * sigma))
+    k = np.arange(-R, R + 1, dtype=np.float64)
+    wk = np.exp(-k * k / (2.0 * sigma * sigma))
+    wk /= wk.sum()
+    taps = np.zeros(STRONG_MAX_RADIUS + 1, dtype=np.float32)
+    taps[:R + 1] = wk[R:]
+    return R, taps
+
+
+def check_strong_table(table, B):
+    """Host-side check of a strong-augmentation table (it lives on the device when the kernels read it): (B,) records of
+    strong_rec_dtype() with fb, fc, fs finite and >= 0, |fh| <= 0.5, radius in 0..8, finite taps and reserved == 0
+    -> a contiguous (B,) array of that dtype."""
+    import numpy as np
+    dt = strong_rec_dtype()
+    t = np.asarray(table)
+    if B < 1 or t.dtype != dt or t.shape != (B,):
+        raise ValueError(f"strong_augment: the table must be ({B},) records of ops.strong_rec_dtype(), B >= 1, got {t.dtype} {t.shape}")
+    for name in ("fb", "fc", "fs"):
+        if not (np.isfinite(t[name]) & (t[name] >= 0)).all():
+            raise ValueError(f"strong_augment: {name} must be finite and >= 0, got {t[name].tolist()}")
+    if not (np.abs(t["fh"]) <= 0.5).all():  # (NaN fails too)
+        raise ValueError(f"strong_augment: |fh| <= 0.5 is required, got {t['fh'].tolist()}")
+    if ((t["radius"] < 0) | (t["radius"] > STRONG_MAX_RADIUS)).any():
+        raise ValueError(f"strong_augment: radius lies in 0..{STRONG_MAX_RADIUS}, got {t['radius'].tolist()}")
+    if not np.isfinite(t["taps"]).all():
+        raise ValueError("strong_augment: the taps must be finite")
+    if t["reserved"].any():
+        raise ValueError("strong_augment: reserved must be zero")
+    return np.ascontiguousarray(t)
+
+
+def strong_augment(x, table, return_mean=False):
+    """Colour jitter, then a Gaussian blur, per sample of a batch (the rule: include/segmif_hip.h, segmif_strong_augment_f32;
+    DAFormer's strong_transform for the student of self-training).  x (B, 3, h, w) fp32 in [0, 1], w % 4 == 0.  table: (B,)
+    records of strong_rec_dtype(), either a host array, which check_strong_table checks and this call uploads, or a (B, 16) int32
+    device tensor of the same bytes whose values the caller has checked.  Two launches on the current stream, no synchronisation.
+    No gradient is taken: an x that requires grad is refused.  -> y, a new tensor (with return_mean: (y, mean (B,) fp32), the
+    luma mean the contrast step used, 0 for a sample without jitter).  NOT the reference's training."""
+    _req_u8(x, "x", dtype=torch.float32)
+    if x.requires_grad:
+        raise RuntimeError("strong_augment: no gradient is taken through the augmentation; detach x")
+    if x.dim() != 4 or x.shape[1] != 3 or x.numel() < 1:
+        raise RuntimeError(f"strong_augment: x must be a non-empty (B, 3, h, w) fp32 tensor, got {tuple(x.shape)}")
+    B, _, h, w = x.shape
+    if w % 4:
+        raise RuntimeError(f"strong_augment: the width must be a multiple of 4 (16-byte accesses), got {w}")
+    if not isinstance(table, torch.Tensor) or not table.is_cuda:
+        import numpy as np
+        host = check_strong_table(table, B)
+        table = torch.from_numpy(host.view(np.int32).reshape(B, STRONG_REC_WORDS)).to(x.device)
+    _req_u8(table, "table", (B, STRONG_REC_WORDS), dtype=torch.int32)
+    lib = _lib.load()
+    n = lib.segmif_strong_augment_blocks(h, w)
+    if n < 1:
+        raise RuntimeError(f"strong_augment: segmif_strong_augment_blocks({h}, {w}) failed with code {n}")
+    partial = torch.empty((B, n), device=x.device, dtype=torch.float64)
+    y, mean = torch.empty_like(x), torch.empty(B, device=x.device, dtype=torch.float32)
+    _lib.check(lib.segmif_strong_augment_f32(x.data_ptr(), y.data_ptr(), table.data_ptr(), partial.data_ptr(), mean.data_ptr(), B, h, w,
+                                             _stream()), "segmif_strong_augment_f32")
+    return (y, mean) if return_mean else y

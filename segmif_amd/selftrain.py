@@ -5,11 +5,17 @@ Valpola 2017; ClassMix, Olsson et al. 2021) - this project's addition, NOT the r
                     average's storage: nothing is copied per step
   cross_mix_table   the ClassMix table of a labelled half pasted into an unlabelled half
   cross_mix         that mix on the existing ops.class_mix, the confidence weight riding as a plane
-  SelfTrainingStep  teacher logits -> ops.pseudo_label (csrc/pseudo_label.hip) -> optional mix -> supervised loss + weighted
+  SelfTrainingStep  teacher logits -> ops.pseudo_label (csrc/pseudo_label.hip) -> optional mix -> optional strong augmentation of
+                    the student's input (ops.strong_augment, csrc/strong_augment.hip) -> supervised loss + weighted
                     mean-over-all-pixels CE on the pseudo-labels (csrc/seg_objective.hip's weighted entries) -> one optimizer step
 
 What differs from DAFormer: no feature-distance loss, one domain (the unlabelled frames are more frames of the same sensor pair),
-and the teacher's BatchNorm buffers are copied from the student rather than averaged.  Nothing here says what it does to mIoU."""
+and the teacher's BatchNorm buffers are copied from the student rather than averaged.  DAFormer trains its student on a strongly
+augmented copy of the (mixed) image while the teacher labels the clean one; here that is opt-in (strong=, a data.StrongAugment):
+without it the student sees the teacher's pixels, and with it the colour jitter's four operations run in one fixed order
+(brightness, contrast, saturation, hue; a random order is not built), the blur's support follows sigma (DAFormer's kernel size
+follows the image's), and neither the labelled batch nor the geometry of the student's input is touched.  Nothing here says
+what it does to mIoU."""
 import copy
 
 import numpy as np
@@ -103,6 +109,9 @@ class SelfTrainingStep:
         1. teacher logits of xU                             4. loss = criterion(student(xL), yL)
         2. ops.pseudo_label (tau, below) and q_b                     + unsup_weight * CE_mean_all(student(xM), yM; u)
         3. with mix (a data.ClassMix): cross_mix            5. one optimizer.step()   6. teacher.refresh()
+           with strong (a data.StrongAugment): the student's unlabelled input is ops.strong_augment(xM or xU, strong.draw(B)),
+           after the mix; labels, pixel weights and sample weights are unchanged and the teacher still sees the clean xU.
+           last_strong keeps the drawn table.  With strong=None the launches and the bits are what they are without it.
     The labelled term keeps whatever path `criterion` takes in seg_train_step.  The unlabelled term is cross entropy averaged over
     ALL pixels (SEGMIF_SEG_MEAN_ALL, what DAFormer computes: (loss * weight).mean()) with u = q_b per sample, or the mixed weight
     plane.  Two student forwards and backwards, gradients accumulated (under a reducer: one backward of the sum).  step() returns
@@ -110,7 +119,7 @@ class SelfTrainingStep:
     per log line.  Not graph-captured."""
 
     def __init__(self, student, teacher, optimizer, criterion, tau=0.968, below="keep", unsup_weight=1.0, mix=None, reducer=None,
-                 ignore_index=255):
+                 ignore_index=255, strong=None):
         if not 0.0 <= float(tau) <= 1.0:
             raise ValueError(f"SelfTrainingStep: tau {tau} outside [0, 1]")
         if below not in ops.PSEUDO_BELOW:
@@ -121,7 +130,8 @@ class SelfTrainingStep:
         self.tau, self.below, self.unsup_weight, self.mix, self.reducer = float(tau), below, float(unsup_weight), mix, reducer
         self.ignore_index = int(ignore_index)
         self.unsup = losses.SegObjective(reduction="mean_all", ignore_index=self.ignore_index)
-        self.last_count, self.last_pixels, self.last_table = None, 0, None
+        self.strong = strong
+        self.last_count, self.last_pixels, self.last_table, self.last_strong = None, 0, None, None
 
     def pseudo(self, xU):
         """-> (pseudo-labels (B, H, W) int64, q (B,) float32) of the teacher on xU; keeps the count"""
@@ -138,6 +148,9 @@ class SelfTrainingStep:
             self.last_table = cross_mix_table(xL.shape[0], self.mix)
             xM, yM, pixel_weight, _ = cross_mix(xL, yL, xU, yU, q, self.last_table, self.mix.n_class, self.mix.min_pixels)
             sample_weight = None
+        if self.strong is not None:
+            self.last_strong = self.strong.draw(xM.shape[0])
+            xM = ops.strong_augment(xM, self.last_strong)
         _zero_grads(self.opt, self.reducer)
         loss_sup = self.student._loss(xL, yL, self.crit)
         if self.reducer is None:  # one graph alive at a time; the gradients accumulate

@@ -376,7 +376,8 @@ LABEL_SLOT, PROBE_SLOT = "<class table, computed weights>", "<candidates and pro
 
 def make_plan(args):
     """The host data of a run, from checked arguments with their defaults resolved; touches no device.  *_kw: keywords of the
-    optimizer makers, AugmentedBatches, RareClassSampler, ClassMix, SelfTrainingStep and its ClassMix (None: switched off).  say:
+    optimizer makers, AugmentedBatches, RareClassSampler, ClassMix, SelfTrainingStep and its ClassMix (None: switched off); with
+    --st-strong, st_kw["strong_kw"] holds the keywords of the step's StrongAugment, which seg_phase takes out and builds.  say:
     what the run announces before round 1, in order; _build_run fills the two slots and {unlabelled}, which take the data."""
     def listed(kw):
         return ", ".join(f"{k} {v}" for k, v in kw.items())
@@ -432,8 +433,14 @@ def make_plan(args):
         p.st_kw = dict(tau=args.st_threshold, below=args.st_below, unsup_weight=args.st_weight)
         if args.st_mix:
             p.st_mix_kw = dict(prob=args.st_mix_prob, classes="half", min_pixels=args.st_mix_min_pixels, n_class=N_CLASS)
-        say.append(f"[train] --self-training ({listed(p.st_kw)}; {{unlabelled}} unlabelled frames"
-                   + (f"; --st-mix {listed(p.st_mix_kw)}" if args.st_mix else "") + "): this project's addition, NOT the reference's training "
+        st_said, strong_kw = listed(p.st_kw), None
+        if args.st_strong:
+            strong_kw = p.st_kw["strong_kw"] = dict(jitter_prob=args.st_jitter_prob, strength=args.st_jitter_strength, hue=args.st_jitter_hue,
+                                                    blur_prob=args.st_blur_prob, sigma=tuple(args.st_blur_sigma))
+        say.append(f"[train] --self-training ({st_said}; {{unlabelled}} unlabelled frames"
+                   + (f"; --st-mix {listed(p.st_mix_kw)}" if args.st_mix else "")
+                   + (f"; --st-strong {listed(strong_kw)}: the student's unlabelled input goes through a colour jitter and a Gaussian blur "
+                      "on the device, the teacher sees the clean frames" if strong_kw else "") + "): this project's addition, NOT the reference's training "
                    "(its train.py uses labelled frames only).  DAFormer-style: the weight average is the teacher, its argmax on an unlabelled "
                    "batch the pseudo-label, the share of pixels above the threshold the weight of a mean-over-all-pixels CE added to the "
                    "labelled loss; no feature-distance term, one domain, the teacher's BatchNorm buffers copied from the student.  "
@@ -583,12 +590,15 @@ def seg_phase(run, iter_):
     batches = _loader(run, run.fused_set, "seg", seed, photometric=())
     st, unsup, first = None, None, []
     if plan.st_kw is not None:  # the unlabelled frames, fused as the labelled ones are, walked by a loader of their own
-        from .data import AugmentedBatches, ClassMix, DeviceDataset
+        from .data import AugmentedBatches, ClassMix, DeviceDataset, StrongAugment
         from .selftrain import EmaTeacher, SelfTrainingStep
         unl_batches = AugmentedBatches(DeviceDataset(unl.names, unl.ir, run.fused_unl, unl.mask, unl.label), seed=seed + 7919,
                                        photometric=(), **plan.loader_kw)
+        st_kw = dict(plan.st_kw)
+        strong_kw = st_kw.pop("strong_kw", None)
         st = SelfTrainingStep(seg, EmaTeacher(opt, seg), opt, run.seg_crit,
-                              mix=ClassMix(seed=seed + 7919, **plan.st_mix_kw) if plan.st_mix_kw else None, **plan.st_kw)
+                              mix=ClassMix(seed=seed + 7919, **plan.st_mix_kw) if plan.st_mix_kw else None,
+                              strong=StrongAugment(seed=seed + 7919, **strong_kw) if strong_kw else None, **st_kw)
         first = [types.SimpleNamespace(line=lambda: f" unlabelled {float(unsup):.6f} confident {st.confident_share():.4f}")]
     log = _logger(run, opt, [("seg_net", seg)], batches, *first)  # (`unsup`: the last step's, below)
     n_seg = plan.seg_iters[iter_ - 1]

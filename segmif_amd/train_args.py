@@ -128,6 +128,20 @@ def build_parser():
                     "(default 1.0, DAFormer's)")
     ap.add_argument("--st-mix-min-pixels", type=int, metavar="N", help="with --st-mix: a class is present in a labelled crop when the "
                     "crop holds more than N pixels of it (default 0)")
+    ap.add_argument("--st-strong", action="store_true", help="with --self-training: the student's unlabelled input (after --st-mix) goes "
+                    "through a colour jitter (brightness, contrast, saturation, hue, in this order) and a Gaussian blur on the device "
+                    "(csrc/strong_augment.hip; DAFormer's strong augmentation with its constants, this project's formulas); labels and "
+                    "weights are unchanged and the teacher sees the clean frames")
+    ap.add_argument("--st-jitter-prob", type=float, metavar="P", help="with --st-strong: the probability that a sample is jittered, in "
+                    "[0, 1] (default 0.8, DAFormer's)")
+    ap.add_argument("--st-jitter-strength", type=float, metavar="S", help="with --st-strong: the brightness, contrast and saturation "
+                    "factors are uniform over [1 - S, 1 + S], S in [0, 1] (default 0.2, DAFormer's)")
+    ap.add_argument("--st-jitter-hue", type=float, metavar="H", help="with --st-strong: the hue shift is uniform over [-H, H], H in "
+                    "[0, 0.5] (default 0.2, DAFormer's)")
+    ap.add_argument("--st-blur-prob", type=float, metavar="P", help="with --st-strong: the probability that a sample is blurred, in "
+                    "[0, 1] (default 0.5, DAFormer's)")
+    ap.add_argument("--st-blur-sigma", type=float, nargs=2, metavar=("LO", "HI"), help="with --st-strong: the blur's sigma is uniform "
+                    "over [LO, HI], 0 < LO <= HI <= 2 (default 0.15 1.15, DAFormer's)")
     ap.add_argument("--log-iters", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     return ap
@@ -140,8 +154,10 @@ _BELONGS = (
     ("--rare-class-sampling", ("--rcs-temperature", "--rcs-min-pixels", "--rcs-min-crop-ratio", "--rcs-fraction", "--rcs-phases")),
     ("--class-mix", ("--class-mix-prob", "--class-mix-min-pixels", "--class-mix-classes", "--class-mix-phases")),
     ("--seg-region", ("--seg-region-weight", "--seg-region-classes", "--dice-smooth")),
-    ("--self-training", ("--unlabelled-split", "--st-threshold", "--st-below", "--st-weight", "--st-mix", "--st-mix-prob", "--st-mix-min-pixels")),
+    ("--self-training", ("--unlabelled-split", "--st-threshold", "--st-below", "--st-weight", "--st-mix", "--st-mix-prob", "--st-mix-min-pixels",
+                         "--st-strong")),
     ("--st-mix", ("--st-mix-prob", "--st-mix-min-pixels")),
+    ("--st-strong", ("--st-jitter-prob", "--st-jitter-strength", "--st-jitter-hue", "--st-blur-prob", "--st-blur-sigma")),
 )
 # A flag, what a given value of it must satisfy, and the refusal after "FLAG VALUE: ":
 _RANGES = (
@@ -161,6 +177,11 @@ _RANGES = (
     ("--st-weight", lambda v: v > 0 and math.isfinite(v), "must be a finite number > 0"),
     ("--st-mix-prob", lambda v: 0.0 < v <= 1.0, "must lie in (0, 1]"),
     ("--st-mix-min-pixels", lambda v: v >= 0, "must be >= 0"),
+    ("--st-jitter-prob", lambda v: 0.0 <= v <= 1.0, "must lie in [0, 1]"),
+    ("--st-jitter-strength", lambda v: 0.0 <= v <= 1.0, "must lie in [0, 1]"),
+    ("--st-jitter-hue", lambda v: 0.0 <= v <= 0.5, "must lie in [0, 0.5]"),
+    ("--st-blur-prob", lambda v: 0.0 <= v <= 1.0, "must lie in [0, 1]"),
+    ("--st-blur-sigma", lambda v: 0.0 < v[0] <= v[1] <= 2.0, "needs 0 < LO <= HI <= 2"),
 )
 # What a flag stands for that defaults to None so that _BELONGS can tell whether it was given (--ohem-n-min: resolve_defaults):
 _DEFAULTS = {
@@ -168,6 +189,7 @@ _DEFAULTS = {
     "--class-mix-prob": 0.5, "--class-mix-classes": "half", "--class-mix-min-pixels": 0, "--class-mix-phases": "seg",
     "--seg-region-weight": 1.0, "--seg-region-classes": "present", "--dice-smooth": 1.0, "--ema-nets": "seg",
     "--st-threshold": 0.968, "--st-below": "keep", "--st-weight": 1.0, "--st-mix-prob": 1.0, "--st-mix-min-pixels": 0,
+    "--st-jitter-prob": 0.8, "--st-jitter-strength": 0.2, "--st-jitter-hue": 0.2, "--st-blur-prob": 0.5, "--st-blur-sigma": (0.15, 1.15),
 }
 
 
