@@ -53,6 +53,8 @@ int segmif_device_name(char* buf, int len);
  *   dense, two sources (k < K1 from in, k >= K1 from in2 with pitch lda2) when in2 != NULL.
  * Wt is [N][Kp] row-major, Kp = K rounded up to 16 and zero-filled (see segmif_pack_conv_weight).
  * out pitch ldo (lets a conv write its channels in place into a concat buffer).
+ * A pitch covers what a row holds: lda >= Cin (conv) or K (dense; K1 and lda2 >= K - K1 with two sources), ldo >= N,
+ * ldr >= N; act is one of SEGMIF_ACT_*.  Anything else is SEGMIF_EINVAL.
  *
  * Replaces: nn.Conv2d / nn.Linear / F.conv2d call sites on the path —
  *   core/mix_transformer.py:47,51 (fc1/fc2), :96,102,112 (q/kv/proj), :100 (sr conv), :193 (patch
@@ -168,9 +170,11 @@ int segmif_amax_f32(const float* x, int64_t rows, int C, int ld, uint32_t* slots
 
 /*
  * Dense GEMM with bf16x6 arithmetic (csrc/gemm_split.hip): out = res + act(A W^T + bias), A (M, K) fp32 rows (pitch lda,
- * 16-byte aligned), K % 32 == 0, any M / N.  `w` is the segmif_gemm_split_pack image of the (N, K) weight (row pitch ldw
- * floats), segmif_gemm_split_weight_bytes(N, K) bytes.  fp32-class accuracy (three bf16 terms per operand, six products)
- * at 2.7x the fp32 MFMA rate: the MiT encoder's and SegFormer head's nn.Linear layers
+ * 16-byte aligned), K % 32 == 0, any M, N % 4 == 0; out / res rows of N floats with pitches ldo / ldr >= N (multiples of 4,
+ * 16-byte aligned); act one of SEGMIF_ACT_* (PRELU needs `prelu`); anything else is SEGMIF_EINVAL.
+ * `w` is the segmif_gemm_split_pack image of the (N, K) weight (row pitch ldw floats), segmif_gemm_split_weight_bytes(N, K)
+ * bytes.  fp32-class accuracy (three bf16 terms per operand, six products) at 2.7x the fp32 MFMA rate: the MiT encoder's and
+ * SegFormer head's nn.Linear layers
  * (core/mix_transformer.py:46-53, :94-115; core/segformer_head.py:23).
  */
 typedef struct SegmifGemmSplit {
@@ -197,7 +201,8 @@ int segmif_gemm_split_f32(const SegmifGemmSplit* desc, void* stream);
  * (:73-75, :98-101) for the tall problems of stages 2-4.  Range: the PRODUCER of A folds max |x| into the guard slots.
  *   lda_bytes: row pitch of A in bytes (>= 4 K, a multiple of 16); patch mode (patch_k > 0): A is a dense NHWC pairs image
  *   (B, patch_H, patch_W, patch_C), patch_C % 16 == 0, row m = (b, oy, ox) the k x k patch at (st oy - pad, st ox - pad) in
- *   (ky, kx, c) order, taps outside the image read as zeros, K = k k C;  tile_rows: 0 = chosen by size, 128 | 256 forces one.
+ *   (ky, kx, c) order, taps outside the image read as zeros, K = k k C;  tile_rows: 0 = chosen by size, 128 | 256 forces one,
+ *   any other value is SEGMIF_EINVAL, as are ldo or ldr < N (both multiples of 4) and an act outside SEGMIF_ACT_*.
  */
 typedef struct SegmifGemmPairs {
   const void* a; const void* w; const float* bias; const float* res; const float* prelu; float* out;
@@ -235,7 +240,7 @@ int segmif_sr_attention_bwd_f32(const float* q, const float* k, const float* v, 
  * segmif_layernorm_f32 / segmif_dwconv3x3_gelu_f32 / segmif_sr_attention_split16_f32; C % 16 == 0.  The LayerNorm's waves are
  * short and numerous: it takes amax_sub (a power of two) consecutive ROWS of slots, amax_pitch words apart (>= amax_images: the
  * guard's own image count, which differs from amax_images when the launch reports to column 0 only), and spreads its
- * reports over them (a slot access serialises on its memory channel). */
+ * reports over them (a slot access serialises on its memory channel).  Pitches as segmif_layernorm_f32: ldx, ldy >= C. */
 int segmif_layernorm_pairs_f32(const float* x, const float* gamma, const float* beta, void* y, int64_t rows, int C, int ldx,
                                int ldy, float eps, uint32_t* amax, int amax_images, int amax_sub, int amax_pitch, void* stream);
 int segmif_dwconv3x3_gelu_pairs_f32(const float* x, const float* w9, const float* bias, void* y, int B, int H, int W, int C,
@@ -273,7 +278,8 @@ int segmif_gemm_split16_f32(const SegmifGemmSplit* desc, uint32_t* amax, int ama
  * the kernel also evaluates   out1 = res + act1( W1 . [in(cin) | act(conv)(32)] + bias1 )   — a 1x1 conv with
  * 64 outputs over the input channels and the conv's own result (w1: segmif_planes_pack_weight(N = 64,
  * Cin = cin + 32, taps = 1)) — i.e. a whole DRDB tail (core/model_fusion.py:153-157: Dcov5, torch.cat,
- * conv 224 -> 64, ReLU, residual) in one launch, the concat never reaching HBM.
+ * conv 224 -> 64, ReLU, residual) in one launch, the concat never reaching HBM.  Pitches: ldo >= 32, ldo1 >= 64, ldr >= 64,
+ * multiples of 4; act1 NONE | RELU.  Every argument is checked before the runtime is asked for anything.
  * Replaces core/model_fusion.py:135-157 in inference.
  */
 typedef struct SegmifConvPlanes {
@@ -348,6 +354,7 @@ int segmif_conv3x3_planes_f16x3(const SegmifConvPlanes* desc, uint32_t* amax, in
  * other strides let attention backward write dK / dV in place).  `desc` describes the FORWARD problem
  * (in, lda, geometry, M, N, K; nz / in_zstride / out_zstride reused as batch count, input and dW batch
  * strides).  workspace: segmif_wgrad_workspace_size(M, N, K) * max(nz,1) floats.  accumulate: dw += .
+ * ldy >= N and lda >= Cin (conv) / K (dense), as in the forward; anything else is SEGMIF_EINVAL.
  * Backward of every nn.Conv2d / nn.Linear listed under segmif_igemm_f32.
  */
 int64_t segmif_wgrad_workspace_size(int64_t M, int N, int K);
@@ -361,11 +368,12 @@ int segmif_wgrad_f32(const SegmifIgemm* desc, const float* dy, int ldy, int64_t 
 int segmif_wgrad_batched2_f32(const SegmifIgemm* desc, const float* dy, int ldy, int64_t dy_zstride, int64_t dy_zstride2,
                               float* dw, int64_t dw_sn, int64_t dw_sk, float* workspace, int accumulate, void* stream);
 /* column sums of a rows x N matrix (bias gradients), two-pass, fp64 accumulation.
- * workspace: segmif_colsum_blocks(rows) * N doubles. */
+ * workspace: segmif_colsum_blocks(rows) * N doubles, 8-byte aligned. */
 int segmif_colsum_blocks(int64_t rows);
 int segmif_colsum_f32(const float* x, float* out, double* workspace, int64_t rows, int N, int ldx,
                       int accumulate, void* stream);
-/* dx = dy * act'(.): ref = activation OUTPUT for ReLU / PReLU (slope > 0), PRE-activation for GELU. */
+/* dx = dy * act'(.): ref = activation OUTPUT for ReLU / PReLU (slope > 0), PRE-activation for GELU.  act is one of SEGMIF_ACT_*
+ * (NONE copies), every pitch >= C; anything else is SEGMIF_EINVAL. */
 int segmif_act_bwd_f32(const float* dy, const float* ref, float* dx, int64_t rows, int C, int ldy, int ldr,
                        int ldx, int act, const float* slope, void* stream);
 /* the same with the activation output given as ref - ref2 (r4: a DRDB keeps x and x + relu(.) - the mask source is their
@@ -375,7 +383,7 @@ int segmif_act_bwd2_f32(const float* dy, const float* ref, const float* ref2, fl
 
 /*
  * LayerNorm over the last dimension: y = (x - mean) / sqrt(var + eps) * gamma + beta,
- * biased variance, two-pass in registers.  rows x C, pitches ldx/ldy. C % 4 == 0, C <= 1024.
+ * biased variance, two-pass in registers.  rows x C, pitches ldx/ldy >= C (multiples of 4). C % 4 == 0, C <= 1024.
  * Replaces nn.LayerNorm at core/mix_transformer.py:101,152-153,196,320,328,336,344 and
  * core/model_fusion.py:359-360 (eps 1e-6 / 1e-5: SURVEY F6).
  */
@@ -384,7 +392,8 @@ int segmif_layernorm_f32(const float* x, const float* gamma, const float* beta, 
 /* Residual form of the training path (r4; core/mix_transformer.py:171-177: x = x + drop_path(f(norm(x)))):
  *   sum = x + scale[row / rows_per_image] * branch  (scale NULL = 1: the per-sample stochastic-depth factor mask / keep)
  *   y   = LayerNorm(sum)
- * in one pass - the residual add, the DropPath multiply and the next LayerNorm were three. */
+ * in one pass - the residual add, the DropPath multiply and the next LayerNorm were three.  Every pitch (ldx, ldb, lds, ldy)
+ * is >= C and a multiple of 4. */
 int segmif_add_layernorm_f32(const float* x, const float* branch, const float* scale, int64_t rows_per_image,
                              const float* gamma, const float* beta, float* sum, float* y, int64_t rows, int C, int ldx,
                              int ldb, int lds, int ldy, float eps, void* stream);
@@ -431,6 +440,7 @@ int segmif_upsum_act_nhwc_f32(const float* base, int ldb, const float* x0, int i
  * materialising the N x Nk score matrix.  q: (B, N, ldq) with head h at columns [h*hd, (h+1)*hd);
  * k and v: (B, Nk, ldkv) (the kv Linear output: k = kv, v = kv + C); out: (B, N, ldo).
  * hd in {32, 64}.  QK^T and PV run on fp32 MFMA, softmax is per-lane (online, exact expf).
+ * ldq, ldo >= heads * hd and ldkv >= 2 * heads * hd (multiples of 4; the split entry points below: ldkv even), else SEGMIF_EINVAL.
  * Replaces core/mix_transformer.py:107-111.
  */
 int segmif_sr_attention_f32(const float* q, const float* k, const float* v, float* out,
@@ -463,6 +473,7 @@ int segmif_sr_attention_split16_f32(const float* q, const float* k, const float*
  * Step 2 (segmif_linattn_fold_f32) reduces the partials in fp64, applies
  * softmax over the k-index (dim=-2) of (K^T V)*scale, and folds the block-diagonal context into
  * the following end_proj weight:  Weff[b][n][kofs + h*d + i] = sum_j ctx[b][h][i][j] * Wend[n][wofs + h*d + j].
+ * Both folds need wofs, kofs >= 0, ldw >= wofs + C, ldweff >= kofs + C and `partial` 8-byte aligned (SEGMIF_EINVAL otherwise).
  * Replaces core/model_fusion.py:281-286 and :316-326 (ctx and q@ctx) together with the cat +
  * end_proj of :357-360, which becomes one dense igemm over [y3 | u_i] with per-image weights.
  */
@@ -505,6 +516,8 @@ int segmif_linattn_fold_bwd_f32(const double* ktv, const float* wend, int ldw, i
  *  - segmif_crosspath_tail_f32: out = LayerNorm_64(x_i + Weff_b . [ReLU(W3 x_3 + b3) | ReLU(Wi x_i + bi)] + bend):
  *    channel_proj halves, the context-folded end_proj (Weff: (B, 64, 128)), residual and norm in one pass over the
  *    tokens; optionally also emits out as planes chunks 0..3 (conv3x3_planes format, H * W == N) for the next DRDB.
+ *    ln_gamma and ln_beta are required (NULL is SEGMIF_EINVAL); segmif_crosspath_fold_f32's pitches and offsets follow
+ *    segmif_linattn_fold_f32's rule with C = 64.
  * Replaces core/model_fusion.py:351-360 together with :281-286 / :316-326 (the three kv Linears and K^T V).
  */
 typedef struct SegmifCrossTail {
@@ -563,7 +576,7 @@ int segmif_seg_normalize_f32(const float* x_nchw, float* y_nhwc, int B, int H, i
 int segmif_nchw_to_nhwc_f32(const float* x, float* y, int B, int C, int64_t HW, int ldo, void* stream);
 int segmif_nhwc_to_nchw_f32(const float* x, float* y, int B, int C, int64_t HW, int ldx, void* stream);
 int segmif_fuse_ycrcb_f32(const float* vis_nchw, const float* yf, float* out_nchw, int B, int64_t HW, void* stream);
-/* (r6) two-source pointwise pass over rows views (rows x C, pitches in floats, C % 4 == 0, 16-byte aligned) - the glue of the
+/* (r6) two-source pointwise pass over rows views (rows x C, pitches in floats and >= C, C % 4 == 0, 16-byte aligned) - the glue of the
  * reference's ablation networks: mode 0 y = a + b (Fusion_Network3_Add, core/model_fusion.py:745-752); mode 1
  * y = silu(a) + silu(b) (Fusion_Network3_Average's att_i(x) + att_j(seg): AttentionModule ends in sigmoid(z) * z, :769-770,
  * :807-813); mode 2 y = silu(a) (AttentionModule alone; b may be NULL) */
@@ -583,7 +596,8 @@ int segmif_color3_f32(const float* in, const float* ysrc, float* out, int B, int
 /* argmax over C of NHWC logits -> int32 labels (test_segmentation.py:174); ties -> lowest index */
 int segmif_argmax_nhwc_i32(const float* x, int32_t* labels, int64_t rows, int C, int ldx, void* stream);
 /* (r6) test_segmentation.py:169-174 in one pass: labels = argmax_c bilinear(x -> OH x OW) for NHWC logits x (B, IH, IW, C), pixel pitch
- * ldx (align_corners = False, segmif_bilinear_nhwc_f32's arithmetic; ties -> lowest index): the resized logits are never written. */
+ * ldx (align_corners = False, segmif_bilinear_nhwc_f32's arithmetic; ties -> lowest index): the resized logits are never written.
+ * OH and B <= 65535 (grid dimensions), as for segmif_bilinear_nhwc_f32. */
 int segmif_bilinear_argmax_i32(const float* x, int32_t* labels, int B, int IH, int IW, int OH, int OW, int C, int ldx, void* stream);
 /* Multi-scale + flip inference (the protocol SegFormer's tables are quoted under; the reference evaluates one view only,
  * test_segmentation.py:169-174), combined in one pass (csrc/tta.hip).  A view is the NHWC logits (B, ih, iw, C), pixel pitch
@@ -856,7 +870,8 @@ int segmif_strong_augment_f32(const float* x, float* y, const SegmifStrongAugRec
  * ---------------------------------------------------------------------------------------------- */
 
 /* LayerNorm backward: dx, plus per-block partial rows [dgamma | dbeta] (nblk x 2C floats) that the
- * caller sums with segmif_colsum_f32.  nblk = segmif_layernorm_bwd_blocks(rows, C). */
+ * caller sums with segmif_colsum_f32.  nblk = segmif_layernorm_bwd_blocks(rows, C).  Pitches (ldx, ldy, lddx; lddres / lddbr of the
+ * residual form when their pointer is given) are >= C and multiples of 4. */
 int segmif_layernorm_bwd_blocks(int64_t rows, int C);
 int segmif_layernorm_bwd_f32(const float* x, const float* dy, const float* gamma, float* dx, float* partial,
                              int64_t rows, int C, int ldx, int ldy, int lddx, float eps, void* stream);
@@ -869,7 +884,8 @@ int segmif_layernorm_bwd_add_f32(const float* x, const float* dy, const float* g
 
 /* Mix-FFN middle backward.  Part 1: z = dwconv(h)+b is recomputed, dz = dy * gelu'(z) is stored and
  * per-block partials [9 taps | bias][C] are written (segmif_dwconv_bwd_partial_rows rows x 10C floats;
- * sum with segmif_colsum_f32).  Part 2: dh = segmif_dwconv3x3_plain_f32(dz, taps flipped). C % 128 == 0. */
+ * sum with segmif_colsum_f32).  Part 2: dh = segmif_dwconv3x3_plain_f32(dz, taps flipped; C % 4 == 0, x / w9 / y 16-byte aligned).
+ * C % 128 == 0. */
 int64_t segmif_dwconv_bwd_partial_rows(int B, int H, int W);
 int segmif_dwconv3x3_gelu_bwd_f32(const float* h, const float* w9, const float* bias, const float* dy, float* dz,
                                   float* partial, int B, int H, int W, int C, void* stream);

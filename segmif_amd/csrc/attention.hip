@@ -160,6 +160,7 @@ extern "C" int segmif_sr_attention_f32(const float* q, const float* k, const flo
                                        int N, int Nk, int hd, int ldq, int ldkv, int ldo, float scale, void* stream) {
   if (!q || !k || !v || !out || B <= 0 || heads <= 0 || N <= 0 || Nk <= 0) return SEGMIF_EINVAL;
   if ((ldq | ldkv | ldo) & 3) return SEGMIF_EINVAL;
+  if (hd <= 0 || ldq < heads * hd || ldo < heads * hd || ldkv < 2 * heads * hd) return SEGMIF_EINVAL;  // q / out rows of heads * hd, kv rows of (k | v)
   if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) return SEGMIF_EINVAL;
   dim3 grid((unsigned)((N + 127) / 128), (unsigned)heads, (unsigned)B);
   hipStream_t s = (hipStream_t)stream;

@@ -361,6 +361,7 @@ static int sr_attention_split_impl(bool f16, const float* q, const float* k, con
                                    int amax_images, void* stream, int out_pairs = 0, uint32_t* out_amax = nullptr) {
   if (!q || !k || !v || !out || !workspace || B <= 0 || heads <= 0 || N <= 0 || Nk <= 0 || hd != 64) return SEGMIF_EINVAL;
   if ((ldq | ldo) & 3 || (ldkv & 1)) return SEGMIF_EINVAL;
+  if (ldq < heads * 64 || ldo < heads * 64 || ldkv < 2 * heads * 64) return SEGMIF_EINVAL;  // q / out rows of heads * 64, kv rows of (k | v)
   if (((uintptr_t)q | (uintptr_t)out | (uintptr_t)workspace) & 15) return SEGMIF_EINVAL;
   if (((uintptr_t)k | (uintptr_t)v) & 7) return SEGMIF_EINVAL;
   if (amax && amax_images != 1 && amax_images != B) return SEGMIF_EINVAL;

@@ -693,7 +693,7 @@ extern "C" int segmif_layernorm_bwd_blocks(int64_t rows, int C) {
 static int ln_bwd_dispatch(const float* x, const float* dy, const float* gamma, float* dx, float* partial, int64_t rows, int C,
                            int ldx, int ldy, int lddx, float eps, void* stream, const LnBwdAdd& a) {
   if (!x || !dy || !gamma || !dx || !partial || rows <= 0 || C <= 0 || (C & 3) || C > 1024 || (ldx & 3) || (ldy & 3) ||
-      (lddx & 3))
+      (lddx & 3) || ldx < C || ldy < C || lddx < C)
     return SEGMIF_EINVAL;
   if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)gamma) & 15) return SEGMIF_EINVAL;
   const int nblk = segmif_layernorm_bwd_blocks(rows, C);
@@ -724,7 +724,8 @@ extern "C" int segmif_layernorm_bwd_add_f32(const float* x, const float* dy, con
                                             const float* scale, int64_t rows_per_image, float* dx, float* dbranch, int lddbr,
                                             float* partial, int64_t rows, int C, int ldx, int ldy, int lddx, float eps,
                                             void* stream) {
-  if ((dres && ((lddres & 3) || ((uintptr_t)dres & 15))) || (dbranch && (!scale || (lddbr & 3) || ((uintptr_t)dbranch & 15))))
+  if ((dres && ((lddres & 3) || lddres < C || ((uintptr_t)dres & 15))) ||
+      (dbranch && (!scale || (lddbr & 3) || lddbr < C || ((uintptr_t)dbranch & 15))))
     return SEGMIF_EINVAL;
   if (scale && (rows_per_image <= 0 || rows % rows_per_image)) return SEGMIF_EINVAL;
   LnBwdAdd a;
@@ -761,6 +762,7 @@ extern "C" int segmif_dwconv3x3_bias_bwd_f32(const float* h, const float* w9, co
 extern "C" int segmif_dwconv3x3_plain_f32(const float* x, const float* w9, float* y, int B, int H, int W, int C,
                                           void* stream) {
   if (!x || !w9 || !y || B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3)) return SEGMIF_EINVAL;
+  if (((uintptr_t)x | (uintptr_t)w9 | (uintptr_t)y) & 15) return SEGMIF_EINVAL;  // 16-byte loads and stores
   const long long per_row = (long long)W * (C >> 2);
   dim3 grid((unsigned)((per_row + 255) / 256), (unsigned)((H + DWB_TY - 1) / DWB_TY), (unsigned)B);
   hipLaunchKernelGGL(dwconv3x3_plain_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, w9, y, H, W, C);

@@ -1115,15 +1115,29 @@ static int conv3x3_planes_impl(const SegmifConvPlanes* d, bool f16, uint32_t* am
   if (d->act == SEGMIF_ACT_PRELU && !d->prelu) return SEGMIF_EINVAL;
   const bool fuse = d->w1 != nullptr;
   if (!fuse && !d->out && !d->planes_out) return SEGMIF_EINVAL;
-  if (d->out && (d->ldo % 4 || ((uintptr_t)d->out & 15))) return SEGMIF_EINVAL;
+  if (d->out && (d->ldo % 4 || d->ldo < 32 || ((uintptr_t)d->out & 15))) return SEGMIF_EINVAL;
   if (d->bias && ((uintptr_t)d->bias & 15)) return SEGMIF_EINVAL;
+  if (fuse) {
+    if (!d->out1 || d->ldo1 % 4 || d->ldo1 < 64 || ((uintptr_t)d->out1 & 15) ||
+        (d->res && (d->ldr % 4 || d->ldr < 64 || ((uintptr_t)d->res & 15))) || (d->bias1 && ((uintptr_t)d->bias1 & 15)) ||
+        (d->act1 != SEGMIF_ACT_NONE && d->act1 != SEGMIF_ACT_RELU))
+      return SEGMIF_EINVAL;
+  }
+  if (d->cin / 16 > d->in_chunks) return SEGMIF_EINVAL;
+  if (d->planes_out && (d->out_chunk0 < 0 || d->out_chunk0 + 2 > d->out_chunks)) return SEGMIF_EINVAL;
+  if (d->planes_out && d->planes_out == d->planes_in && d->out_chunk0 < d->cin / 16) return SEGMIF_EINVAL;  // would overwrite its own input
+  if ((long long)planes_hp(d->H) * planes_wp(d->W) * (f16 ? PXH : PXB) >= (1ll << 32)) return SEGMIF_EINVAL;
+  // every argument is checked: only now the runtime is asked for anything
   PlanesConvK k;
   k.pin = (const unsigned char*)d->planes_in;
   k.pout = (unsigned char*)d->planes_out;
   k.wt = (const unsigned char*)d->wt;
   static segmif::PerDeviceValue<const float*> zero_bias_dev;  // a __device__ symbol has one address per device
   const float*& zero_bias = zero_bias_dev.here();
-  if (!zero_bias && hipGetSymbolAddress((void**)&zero_bias, HIP_SYMBOL(planes_zero_bias)) != hipSuccess) return SEGMIF_EINVAL;
+  if (!zero_bias) {
+    const hipError_t e = hipGetSymbolAddress((void**)&zero_bias, HIP_SYMBOL(planes_zero_bias));
+    if (e != hipSuccess || !zero_bias) return e != hipSuccess ? (int)e : SEGMIF_EINVAL;
+  }
   k.bias = d->bias ? d->bias : zero_bias;
   k.prelu = d->prelu;
   k.out = d->out;
@@ -1135,10 +1149,6 @@ static int conv3x3_planes_impl(const SegmifConvPlanes* d, bool f16, uint32_t* am
   k.out_total = d->out_chunks;
   k.out_chunk0 = d->out_chunk0;
   k.act = d->act;
-  if (k.nchunks > k.in_total) return SEGMIF_EINVAL;
-  if (k.pout && (k.out_chunk0 < 0 || k.out_chunk0 + 2 > k.out_total)) return SEGMIF_EINVAL;
-  if (k.pout && k.pout == k.pin && k.out_chunk0 < k.nchunks) return SEGMIF_EINVAL;  // would overwrite its own input
-  if ((long long)k.Hp * k.Wp * (f16 ? PXH : PXB) >= (1ll << 32)) return SEGMIF_EINVAL;
   k.amax = amax;
   k.amax_images = amax_images;
   k.wscale = reinterpret_cast<const float*>(k.wt + (long long)32 * d->cin * 9 * 6);  // f16x3 images end with the row scales
@@ -1149,11 +1159,6 @@ static int conv3x3_planes_impl(const SegmifConvPlanes* d, bool f16, uint32_t* am
   k.res_planes = (f16 && fuse && !d->res) ? d->res_from_planes : 0;
   k.out1 = d->out1;
   k.ldr = d->ldr; k.ldo1 = d->ldo1; k.act1 = d->act1;
-  if (fuse) {
-    if (!d->out1 || d->ldo1 % 4 || ((uintptr_t)d->out1 & 15) || (d->res && (d->ldr % 4 || ((uintptr_t)d->res & 15))) ||
-        (d->bias1 && ((uintptr_t)d->bias1 & 15)) || (d->act1 != SEGMIF_ACT_NONE && d->act1 != SEGMIF_ACT_RELU))
-      return SEGMIF_EINVAL;
-  }
   k.tiles_x = (d->W + TW - 1) / TW;
   k.tiles_y = (d->H + TH - 1) / TH;
   hipStream_t s = (hipStream_t)stream;

@@ -963,6 +963,7 @@ extern "C" int segmif_crosspath_fold_f32(const double* partial, int nblk, const 
                                          int Nout, int ldw, int wofs, int ldweff, int kofs, float scale, uint32_t* cond,
                                          void* stream) {
   if (!partial || !wkv || !wend || !weff || B <= 0 || nblk <= 0 || Nout <= 0) return SEGMIF_EINVAL;
+  if (wofs < 0 || kofs < 0 || ldw < wofs + 64 || ldweff < kofs + 64 || ((uintptr_t)partial & 7)) return SEGMIF_EINVAL;  // (as segmif_linattn_fold_f32)
   constexpr size_t smem = (size_t)(3 * 4096 + 2 * 512) * sizeof(double);
   static segmif::PerDeviceFlag raised_flag;
   bool& raised = raised_flag.here();
@@ -978,6 +979,7 @@ extern "C" int segmif_crosspath_fold_f32(const double* partial, int nblk, const 
 
 extern "C" int segmif_crosspath_tail_f32(const SegmifCrossTail* d, void* stream) {
   if (!d || !d->x3 || !d->xi || (!d->w3 && d->x3_ih <= 0) || !d->wi || !d->weff || (!d->out && !d->planes_out) || d->B <= 0 || d->N <= 0) return SEGMIF_EINVAL;  // (out may be NULL when the planes copy is the only consumer)
+  if (!d->ln_gamma || !d->ln_beta) return SEGMIF_EINVAL;  // the tail always ends in the LayerNorm
   if (d->ld3 < 64 || d->ldi < 64 || d->ldo < 64 || ((d->ld3 | d->ldi | d->ldo) & 3)) return SEGMIF_EINVAL;
   if (((uintptr_t)d->x3 | (uintptr_t)d->xi | (uintptr_t)d->w3 | (uintptr_t)d->wi | (uintptr_t)d->weff | (uintptr_t)d->out) & 15)
     return SEGMIF_EINVAL;

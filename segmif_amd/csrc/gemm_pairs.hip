@@ -456,8 +456,9 @@ extern "C" int segmif_gemm_pairs_f32(const SegmifGemmPairs* d, void* stream) {
     pow_ = (d->patch_W + 2 * pad - kk) / st + 1;
     if (d->M % ((long long)poh * pow_)) return SEGMIF_EINVAL;
   }
-  if (d->act == SEGMIF_ACT_PRELU && !d->prelu) return SEGMIF_EINVAL;
-  if (d->res && (d->ldr <= 0 || (d->ldr & 3) || ((uintptr_t)d->res & 15))) return SEGMIF_EINVAL;
+  if (d->act < SEGMIF_ACT_NONE || d->act > SEGMIF_ACT_GELU || (d->act == SEGMIF_ACT_PRELU && !d->prelu)) return SEGMIF_EINVAL;
+  if (d->tile_rows != 0 && d->tile_rows != 128 && d->tile_rows != 256) return SEGMIF_EINVAL;
+  if (d->res && (d->ldr < d->N || (d->ldr & 3) || ((uintptr_t)d->res & 15))) return SEGMIF_EINVAL;
   if ((d->N & 3) || (d->ldo & 3) || d->ldo < d->N || ((uintptr_t)d->out & 15) || ((uintptr_t)d->bias & 15)) return SEGMIF_EINVAL;
   // 64 zero bytes on this device (patch mode's out-of-image taps): a zero-initialised __device__ array - (r6) no
   // hipMalloc / null-stream hipMemset inside a launch function (unordered against a non-blocking stream, illegal under capture)

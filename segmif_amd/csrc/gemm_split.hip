@@ -392,9 +392,9 @@ static int gemm_split_impl(const SegmifGemmSplit* d, bool f16, uint32_t* amax, i
     pow_ = (d->patch_W + 2 * pad - kk) / st + 1;
     if (d->M % ((long long)poh * pow_)) return SEGMIF_EINVAL;
   }
-  if (d->act == SEGMIF_ACT_PRELU && !d->prelu) return SEGMIF_EINVAL;
-  if (d->res && (d->ldr <= 0 || (d->ldr & 3) || ((uintptr_t)d->res & 15))) return SEGMIF_EINVAL;
-  if ((d->N & 3) || (d->ldo & 3) || ((uintptr_t)d->out & 15) || ((uintptr_t)d->bias & 15)) return SEGMIF_EINVAL;  // float4 epilogue
+  if (d->act < SEGMIF_ACT_NONE || d->act > SEGMIF_ACT_GELU || (d->act == SEGMIF_ACT_PRELU && !d->prelu)) return SEGMIF_EINVAL;
+  if (d->res && (d->ldr < d->N || (d->ldr & 3) || ((uintptr_t)d->res & 15))) return SEGMIF_EINVAL;
+  if ((d->N & 3) || (d->ldo & 3) || d->ldo < d->N || ((uintptr_t)d->out & 15) || ((uintptr_t)d->bias & 15)) return SEGMIF_EINVAL;  // float4 epilogue
   GemmSplitK k;
   k.a = d->a; k.w = (const unsigned char*)d->w; k.bias = d->bias; k.res = d->res; k.prelu = d->prelu; k.out = d->out;
   k.M = d->M; k.N = d->N; k.K = d->K; k.lda = d->lda; k.ldo = d->ldo; k.ldr = d->ldr; k.act = d->act;

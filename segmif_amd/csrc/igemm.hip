@@ -666,6 +666,8 @@ extern "C" int segmif_igemm_f32(const SegmifIgemm* d, void* stream) {
 
 static int igemm_resolve(const SegmifIgemm* d, IgemmK& k, int& mode_out, int& tile_out, int& nz_out, bool& halo_out) {
   if (!d || !d->in || !d->wt || (!d->out && !d->planes_out) || d->M <= 0 || d->N <= 0 || d->K <= 0) return SEGMIF_EINVAL;  // (out may be NULL when the planes copy is the only consumer)
+  if (d->act < SEGMIF_ACT_NONE || d->act > SEGMIF_ACT_GELU) return SEGMIF_EINVAL;
+  if ((d->out && d->ldo < d->N) || (d->res && d->ldr < d->N)) return SEGMIF_EINVAL;  // rows of N outputs must not overlap
   halo_out = false;
   k.in = d->in; k.in2 = d->in2; k.wt = d->wt; k.bias = d->bias; k.res = d->res; k.prelu = d->prelu; k.out = d->out;
   k.M = d->M; k.N = d->N; k.K = d->K; k.Kp = (d->K + 15) / 16 * 16;
@@ -699,13 +701,15 @@ static int igemm_resolve(const SegmifIgemm* d, IgemmK& k, int& mode_out, int& ti
   if (!d->out && (!k.planes || nz > 1 || d->res)) return SEGMIF_EINVAL;  // planes-only output: the planes epilogue is the one that may skip the fp32 store
   if (k.planes) {
     int hp, wp;
-    if (!k.vec4 || (d->N & 15) || nz > 1 || k.ln_gamma || d->planes_chunk0 < 0 || d->planes_chunk0 + d->N / 16 > d->planes_chunks ||
+    if (!k.vec4 || (d->N & 15) || nz > 1 || k.ln_gamma || d->planes_chunk0 < 0 || d->planes_chunk0 + d->N / 16 > d->planes_chunks || d->OH <= 0 || d->OW <= 0 ||
         d->M % ((long long)d->OH * d->OW) || segmif_planes_dims(d->OH, d->OW, &hp, &wp) != 0 || ((uintptr_t)k.planes & 15))
       return SEGMIF_EINVAL;
     k.pl_Hp = hp; k.pl_Wp = wp; k.pl_chunks = d->planes_chunks; k.pl_chunk0 = d->planes_chunk0;
   }
 
   const bool is_conv = !(d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0);
+  // a row of A holds what the problem reads of it: Cin channels of a pixel, K (K1 / K - K1 with two sources) columns of a dense row
+  if (d->in2 ? (d->lda < d->K1 || d->lda2 < d->K - d->K1) : d->lda < (is_conv ? d->Cin : d->K)) return SEGMIF_EINVAL;
   int mode;
   if (d->in2) {
     if (is_conv || d->K1 % 32 != 0 || (d->K - d->K1) % 16 != 0 || d->lda % 4 || d->lda2 % 4) return SEGMIF_EINVAL;

@@ -322,6 +322,7 @@ extern "C" int segmif_linattn_fold_f32(const double* partial, const float* wend,
                                        int heads, int d, int Nout, int ldw, int wofs, int ldweff, int kofs, float scale,
                                        void* stream) {
   if (!partial || !wend || !weff || B <= 0 || nblk <= 0 || heads <= 0 || d <= 0 || d > 8 || heads * d > 64 || Nout <= 0) return SEGMIF_EINVAL;
+  if (wofs < 0 || kofs < 0 || ldw < wofs + heads * d || ldweff < kofs + heads * d || ((uintptr_t)partial & 7)) return SEGMIF_EINVAL;  // (as the backward checks them)
   hipLaunchKernelGGL(linattn_fold_kernel, dim3((unsigned)B), dim3(1024), 0, (hipStream_t)stream,
                      partial, wend, weff, nblk, Nout, ldw, wofs, ldweff, kofs, scale, heads, d);
   return (int)hipGetLastError();

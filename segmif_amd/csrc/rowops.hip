@@ -601,7 +601,7 @@ __global__ __launch_bounds__(256) void upsum_act_kernel(const float* __restrict_
 
 extern "C" int segmif_layernorm_f32(const float* x, const float* gamma, const float* beta, float* y, int64_t rows,
                                     int C, int ldx, int ldy, float eps, void* stream) {
-  if (!x || !gamma || !beta || !y || rows <= 0 || C <= 0 || (C & 3) || C > 1024 || (ldx & 3) || (ldy & 3))
+  if (!x || !gamma || !beta || !y || rows <= 0 || C <= 0 || (C & 3) || C > 1024 || (ldx & 3) || (ldy & 3) || ldx < C || ldy < C)
     return SEGMIF_EINVAL;
   if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta) & 15) return SEGMIF_EINVAL;
   hipStream_t s = (hipStream_t)stream;
@@ -616,7 +616,7 @@ extern "C" int segmif_layernorm_f32(const float* x, const float* gamma, const fl
 
 extern "C" int segmif_layernorm_pairs_f32(const float* x, const float* gamma, const float* beta, void* y, int64_t rows, int C, int ldx,
                                           int ldy, float eps, uint32_t* amax, int amax_images, int amax_sub, int amax_pitch, void* stream) {
-  if (!x || !gamma || !beta || !y || rows <= 0 || C <= 0 || (C & 15) || C > 1024 || (ldx & 3) || (ldy & 3) || ldy < C)
+  if (!x || !gamma || !beta || !y || rows <= 0 || C <= 0 || (C & 15) || C > 1024 || (ldx & 3) || (ldy & 3) || ldx < C || ldy < C)
     return SEGMIF_EINVAL;
   if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta) & 15) return SEGMIF_EINVAL;
   if (amax && (amax_images < 1 || rows % amax_images || amax_sub < 1 || (amax_sub & (amax_sub - 1)) || amax_pitch < amax_images))
@@ -639,7 +639,8 @@ extern "C" int segmif_layernorm_pairs_f32(const float* x, const float* gamma, co
 extern "C" int segmif_add_layernorm_f32(const float* x, const float* branch, const float* scale, int64_t rows_per_image,
                                         const float* gamma, const float* beta, float* sum, float* y, int64_t rows, int C, int ldx,
                                         int ldb, int lds, int ldy, float eps, void* stream) {
-  if (!x || !branch || !sum || !gamma || !beta || !y || rows <= 0 || C <= 0 || (C & 3) || C > 1024 || ((ldx | ldb | lds | ldy) & 3))
+  if (!x || !branch || !sum || !gamma || !beta || !y || rows <= 0 || C <= 0 || (C & 3) || C > 1024 || ((ldx | ldb | lds | ldy) & 3) || ldx < C ||
+      ldb < C || lds < C || ldy < C)
     return SEGMIF_EINVAL;
   if (scale && (rows_per_image <= 0 || rows % rows_per_image)) return SEGMIF_EINVAL;
   if (((uintptr_t)x | (uintptr_t)branch | (uintptr_t)sum | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta) & 15) return SEGMIF_EINVAL;
@@ -911,6 +912,7 @@ extern "C" int segmif_seg_normalize_f32(const float* x, float* y, int B, int H, 
 extern "C" int segmif_pointwise2_f32(const float* a, int lda, const float* b, int ldb, float* y, int ldy, int64_t rows, int C, int mode,
                                      void* stream) {
   if (!a || !y || rows <= 0 || C <= 0 || (C & 3) || mode < 0 || mode > 2 || (mode != 2 && !b)) return SEGMIF_EINVAL;
+  if (lda < C || ldy < C || (b && ldb < C)) return SEGMIF_EINVAL;
   if ((lda & 3) || (ldy & 3) || (b && (ldb & 3)) || (((uintptr_t)a | (uintptr_t)y | (uintptr_t)b) & 15)) return SEGMIF_EINVAL;
   const long long total = (long long)rows * (C / 4);
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
@@ -968,6 +970,7 @@ extern "C" int segmif_argmax_nhwc_i32(const float* x, int32_t* labels, int64_t r
 extern "C" int segmif_bilinear_argmax_i32(const float* x, int32_t* labels, int B, int IH, int IW, int OH, int OW, int C, int ldx,
                                           void* stream) {
   if (!x || !labels || B <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0 || C <= 0 || ldx < C) return SEGMIF_EINVAL;
+  if (OH > 65535 || B > 65535) return SEGMIF_EINVAL;  // (grid dimensions y / z)
   const float sy = (float)IH / (float)OH, sx = (float)IW / (float)OW;  // (as segmif_bilinear_nhwc_f32 forms them)
   dim3 grid((unsigned)((OW + 255) / 256), (unsigned)OH, (unsigned)B);
   hipLaunchKernelGGL(bilinear_argmax_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, labels, IH, IW, OH, OW, C, ldx, sy, sx);

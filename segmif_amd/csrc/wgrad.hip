@@ -1081,6 +1081,7 @@ static int wgrad_impl(const SegmifIgemm* d, const float* dy, int ldy, int64_t dy
   k.in_zs = d->in_zstride; k.dy_zs = dy_zstride;
   k.nz2 = nz2; k.in_zs2 = nz2 > 1 ? d->in_zstride2 : 0; k.dy_zs2 = nz2 > 1 ? dy_zstride2 : 0;
   const bool is_conv = !(d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0);
+  if (ldy < d->N || d->lda < (is_conv ? d->Cin : d->K)) return SEGMIF_EINVAL;  // rows of dY hold N columns, rows of the input what the forward read
   if (!is_conv) {
     if ((d->K % 4) || (d->lda % 4) || ((uintptr_t)d->in & 15) || (d->in_zstride % 4) || (k.in_zs2 % 4)) return SEGMIF_EINVAL;
     k.conv = 0;
@@ -1218,7 +1219,7 @@ extern "C" int segmif_colsum_blocks(int64_t rows) { return (int)((rows + cs_rows
 
 extern "C" int segmif_colsum_f32(const float* x, float* out, double* workspace, int64_t rows, int N, int ldx,
                                  int accumulate, void* stream) {
-  if (!x || !out || !workspace || rows <= 0 || N <= 0 || ldx < N) return SEGMIF_EINVAL;
+  if (!x || !out || !workspace || rows <= 0 || N <= 0 || ldx < N || ((uintptr_t)workspace & 7)) return SEGMIF_EINVAL;
   const int nblk = segmif_colsum_blocks(rows);
   hipStream_t s = (hipStream_t)stream;
   const bool vec = !(N & 3) && !(ldx & 3) && !((uintptr_t)x & 15);
@@ -1269,7 +1270,8 @@ __global__ __launch_bounds__(256) void act_bwd_vec_kernel(const float* __restric
 static int act_bwd_dispatch(const float* dy, const float* ref, const float* ref2, int ldr2, float* dx, int64_t rows, int C, int ldy,
                             int ldr, int ldx, int act, const float* slope, void* stream) {
   if (!dy || !ref || !dx || rows <= 0 || C <= 0) return SEGMIF_EINVAL;
-  if (act == SEGMIF_ACT_PRELU && !slope) return SEGMIF_EINVAL;
+  if (act < SEGMIF_ACT_NONE || act > SEGMIF_ACT_GELU || (act == SEGMIF_ACT_PRELU && !slope)) return SEGMIF_EINVAL;
+  if (ldy < C || ldr < C || ldx < C || (ref2 && ldr2 < C)) return SEGMIF_EINVAL;
   const long long total = (long long)rows * C;
   if (!((C | ldy | ldr | ldx | (ref2 ? ldr2 : 0)) & 3) &&
       !(((uintptr_t)dy | (uintptr_t)ref | (uintptr_t)dx | (uintptr_t)ref2) & 15) && rows < (1ll << 33)) {
