@@ -114,6 +114,10 @@ class SegmifRegionObjective(ctypes.Structure):
     _fields_ = [("kind", c_int32), ("classes", c_int32), ("ignore_index", c_int32), ("smooth", c_float), ("reserved", c_int32 * 4)]
 
 
+class SegmifDistill(ctypes.Structure):
+    _fields_ = [("temperature", c_float), ("mode", c_int32), ("reserved", c_int32 * 2)]
+
+
 class SegmifGradGuardRecord(ctypes.Structure):
     _fields_ = [("sumsq", c_double), ("norm", c_float), ("coef", c_float), ("nonfinite", ctypes.c_uint32),
                 ("skip_now", ctypes.c_uint32), ("attempts", ctypes.c_uint32), ("applied", ctypes.c_uint32),
@@ -341,6 +345,17 @@ SIGNATURES = {
     "segmif_resize_flip_nchw_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
 }
 
+# the distillation objectives: name -> (restype, argtypes); must list every symbol include/segmif_distill.h declares, and none that
+# include/segmif_hip.h does.  The same library exports them; segmif_abi_version() does not count them.
+DISTILL_PIXEL, DISTILL_CHANNEL = 0, 1
+DISTILL_SIGNATURES = {
+    "segmif_distill_workspace_bytes": (c_int64, [c_int64, c_int64, c_int, c_int]),
+    "segmif_distill_objective_f32": (c_int, [POINTER(SegmifDistill), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int,
+                                             c_int, c_int, c_void_p]),
+    "segmif_distill_objective_bwd_f32": (c_int, [POINTER(SegmifDistill), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                 c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
+}
+
 _lib = None
 
 
@@ -363,7 +378,7 @@ def load():
     # kernels' library came up on the system ROCm's runtime and its first launch failed with hipErrorNoDevice (r5).
     import torch  # noqa: F401
     lib = ctypes.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(DISTILL_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: loud by design
         fn.restype = res
         fn.argtypes = args

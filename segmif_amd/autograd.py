@@ -10,6 +10,7 @@ Backward building blocks
   the rest         : LayerNorm / dwconv+GELU / bilinear / row-softmax / cross-entropy kernels
 """
 import ctypes
+import math
 
 import torch
 
@@ -1609,6 +1610,81 @@ class RegionObjectiveFn(torch.autograd.Function):
                                                                ws.data_ptr(), rec.data_ptr(), up.data_ptr(), dlog.data_ptr(), rows, C,
                                                                ld, C, _stream()), "segmif_region_objective_bwd_f32")
         return dlog, None, None
+
+
+_DISTILL_MODES = {"pixel": _lib.DISTILL_PIXEL, "channel": _lib.DISTILL_CHANNEL}
+
+
+def distill_descriptor(kind="channel", temperature=4.0):
+    """The SegmifDistill of losses.DistillObjective's settings."""
+    d = _lib.SegmifDistill()
+    d.temperature, d.mode = temperature, _DISTILL_MODES[kind]
+    return d
+
+
+class DistillObjectiveFn(torch.autograd.Function):
+    """losses.DistillObjective on the device (csrc/distill_objective.hip; include/segmif_distill.h).  Forward: the KL term of the
+    mode - pixel: softmax over a row's classes; channel: over a sample's positions, from a (B, C) statistics table kept in the
+    workspace - summed in a fixed order, and a 4-float device record {loss, gradient scale, T, loss / T^2}.  Backward: one launch
+    that recomputes both softmaxes from the logits and writes dstudent already scaled by the record and the upstream gradient;
+    nothing full-size is kept from the forward.  The teacher is data: no gradient.  No host sync."""
+
+    @staticmethod
+    def forward(ctx, student, teacher, desc, rows_per_sample):
+        rows, C, lds = rows_view(student, "student logits")
+        _, _, ldt = rows_view(teacher, "teacher logits")
+        lib = _lib.load()
+        nbytes = lib.segmif_distill_workspace_bytes(rows, rows_per_sample, C, desc.mode)
+        if nbytes <= 0:
+            raise RuntimeError(f"segmif_distill_workspace_bytes refused rows = {rows}, rows_per_sample = {rows_per_sample}, C = {C}, "
+                               f"mode = {desc.mode}")
+        ws = torch.empty((nbytes,), device=student.device, dtype=torch.uint8)
+        rec = torch.empty((4,), device=student.device, dtype=torch.float32)
+        _lib.check(lib.segmif_distill_objective_f32(ctypes.byref(desc), student.data_ptr(), teacher.data_ptr(), ws.data_ptr(),
+                                                    rec.data_ptr(), rows, rows_per_sample, C, lds, ldt, _stream()),
+                   "segmif_distill_objective_f32")
+        ctx.save_for_backward(student, teacher, ws, rec)
+        ctx.desc, ctx.rows_per_sample = desc, rows_per_sample
+        return rec[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        student, teacher, ws, rec = ctx.saved_tensors
+        rows, C, lds = rows_view(student, "student logits")
+        _, _, ldt = rows_view(teacher, "teacher logits")
+        up = g.reshape(1).float().contiguous()
+        ds = torch.empty(student.shape, device=student.device, dtype=torch.float32)
+        _lib.check(_lib.load().segmif_distill_objective_bwd_f32(ctypes.byref(ctx.desc), student.data_ptr(), teacher.data_ptr(),
+                                                                ws.data_ptr(), rec.data_ptr(), up.data_ptr(), ds.data_ptr(), rows,
+                                                                ctx.rows_per_sample, C, lds, ldt, C, _stream()),
+                   "segmif_distill_objective_bwd_f32")
+        return ds, None, None, None
+
+
+def distill_objective(student_nhwc, teacher_nhwc, kind="channel", temperature=4.0):
+    """losses.DistillObjective's value for NHWC logits (B, h, w, C) of one shape - rows views, C <= 32; a channel slice of a wider
+    buffer is fine, the pitches are taken per tensor.  The teacher is data: one that requires grad is refused rather than silently
+    detached.  This project's addition, not the reference's objective."""
+    if kind not in _DISTILL_MODES:
+        raise ValueError(f"distill_objective: kind must be one of {', '.join(_DISTILL_MODES)}, got {kind!r}")
+    temperature = float(temperature)
+    if not (math.isfinite(temperature) and temperature > 0.0):
+        raise ValueError(f"distill_objective: the temperature must be finite and > 0, got {temperature}")
+    if not isinstance(student_nhwc, torch.Tensor) or not isinstance(teacher_nhwc, torch.Tensor):
+        raise TypeError("distill_objective: student and teacher logits must be tensors")
+    if student_nhwc.shape != teacher_nhwc.shape:
+        raise RuntimeError(f"distill_objective: student logits {tuple(student_nhwc.shape)} and teacher logits {tuple(teacher_nhwc.shape)} "
+                           "differ in shape (the two nets' outputs at the same resolution, the same classes)")
+    if student_nhwc.dim() != 4:
+        raise RuntimeError(f"distill_objective: logits must be (B, h, w, C), got {tuple(student_nhwc.shape)}")
+    if teacher_nhwc.requires_grad:
+        raise RuntimeError("distill_objective: the teacher logits require grad, but the teacher is data and receives no gradient; "
+                           "run it under no_grad (distill.FrozenTeacher) or detach it")
+    _req(student_nhwc, "student logits"), _req(teacher_nhwc, "teacher logits")  # (host-checkable faults first: they need no device)
+    B, h, w, C = student_nhwc.shape
+    if C > 32:
+        raise RuntimeError(f"the distillation kernel holds a row of at most 32 classes in registers, got {C}")
+    return DistillObjectiveFn.apply(student_nhwc, teacher_nhwc, distill_descriptor(kind, temperature), h * w)
 
 
 class NchwToNhwcFn(torch.autograd.Function):

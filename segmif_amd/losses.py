@@ -16,6 +16,9 @@ three reductions (mean over valid pixels, mean over all pixels, OHEM) of core/lo
 
 RegionObjective adds the region objectives - Lovasz-Softmax and soft Dice (csrc/region_objective.hip) - and SegLossSum adds one of
 them to a per-pixel criterion on the same logits.  Neither is the reference's.
+
+DistillObjective is the distillation term between a student's and a frozen teacher's logits - per-pixel KD or channel-wise
+distillation (csrc/distill_objective.hip) - that segmif_amd.distill.DistillStep adds to the supervised loss.  Not the reference's.
 """
 import math
 from typing import NamedTuple
@@ -388,3 +391,49 @@ class SegLossSum(nn.Module):
     def forward(self, logits, labels):
         from . import autograd as ag
         return self.forward_nhwc(ag.nhwc_rows_of(logits), labels)
+
+
+# ---- the distillation objectives (csrc/distill_objective.hip; include/segmif_distill.h) ------------------------------------------------
+DISTILL_KINDS = ("channel", "pixel")
+DISTILL_TEMPERATURES = {"channel": 4.0, "pixel": 1.0}  # this project's choice; the CWD paper's logit setting is quoted from memory
+
+
+class DistillObjective(nn.Module):
+    """The distillation term between a student's and a frozen teacher's logits at the same resolution, forward and backward in
+    csrc/distill_objective.hip; this project's addition, NOT the reference's objective.  With z = logits / T and lse the
+    log-sum-exp over the stated axis:
+        kind "pixel"    per-pixel KD (Hinton et al. 2015): softmax over the classes of a pixel,
+                        T^2 * mean over pixels of KL(softmax(zt) || softmax(zs))
+        kind "channel"  channel-wise distillation (CWD, Shu et al., ICCV 2021) on the logit maps: softmax over the h * w positions of
+                        a sample's class map, T^2 * sum of the (B, C) KL terms / (B C)
+    temperature None: 4.0 for "channel", 1.0 for "pixel" (this project's choice).  The teacher is data: it gets no gradient, and a
+    teacher tensor that requires grad is refused.  No weights, no ignore mask.  No host synchronisation.  Device float32 logits
+    only: there is no torch formulation of it in the package."""
+
+    def __init__(self, kind="channel", temperature=None):
+        super().__init__()
+        if kind not in DISTILL_KINDS:
+            raise ValueError(f"DistillObjective: kind must be one of {', '.join(DISTILL_KINDS)}, got {kind!r}")
+        temperature = DISTILL_TEMPERATURES[kind] if temperature is None else float(temperature)
+        if not (math.isfinite(temperature) and temperature > 0.0):
+            raise ValueError(f"DistillObjective: temperature must be finite and > 0, got {temperature}")
+        self.kind, self.temperature = kind, temperature
+
+    def extra_repr(self):
+        return f"kind={self.kind!r}, temperature={self.temperature}"
+
+    def forward_nhwc(self, student_nhwc, teacher_nhwc):
+        """(B, h, w, C) float32 device rows, the same shape for both (a channel slice of a wider buffer is fine)"""
+        from . import autograd as ag
+        return ag.distill_objective(student_nhwc, teacher_nhwc, kind=self.kind, temperature=self.temperature)
+
+    def forward(self, student, teacher):
+        """logical (B, C, h, w), contiguous or channels-last in memory; the student's gradient comes back in its layout"""
+        from . import autograd as ag
+        if isinstance(student, torch.Tensor) and isinstance(teacher, torch.Tensor):
+            if student.shape != teacher.shape:
+                raise RuntimeError(f"DistillObjective: student logits {tuple(student.shape)} and teacher logits {tuple(teacher.shape)} "
+                                   "differ in shape")
+            if teacher.requires_grad:
+                raise RuntimeError("DistillObjective: the teacher logits require grad, but the teacher is data and receives no gradient")
+        return self.forward_nhwc(ag.nhwc_rows_of(student), ag.nhwc_rows_of(teacher))

@@ -26,6 +26,8 @@ is one block in the parser, one row in each table, one entry in the plan and one
 writes the AVERAGED weights.  --class-mix pastes classes between the crops of a batch (ClassMix, csrc/class_mix.hip).
 --self-training adds an unlabelled split to the segmentation phase (segmif_amd.selftrain: the weight average as the teacher,
 pseudo-labels from csrc/pseudo_label.hip, a confidence-weighted CE on csrc/seg_objective.hip's weighted entries).
+--distill-from adds a frozen teacher to the segmentation phase (segmif_amd.distill: per-pixel KD or channel-wise distillation
+between the two nets' logits on csrc/distill_objective.hip).
 """
 import contextlib
 import math
@@ -376,7 +378,8 @@ LABEL_SLOT, PROBE_SLOT = "<class table, computed weights>", "<candidates and pro
 
 def make_plan(args):
     """The host data of a run, from checked arguments with their defaults resolved; touches no device.  *_kw: keywords of the
-    optimizer makers, AugmentedBatches, RareClassSampler, ClassMix, SelfTrainingStep and its ClassMix (None: switched off); with
+    optimizer makers, AugmentedBatches, RareClassSampler, ClassMix, SelfTrainingStep and its ClassMix (None: switched off; distill_kw,
+    the teacher's checkpoint and DistillStep's settings, exists only with --distill-from: read it with getattr); with
     --st-strong, st_kw["strong_kw"] holds the keywords of the step's StrongAugment, which seg_phase takes out and builds.  say:
     what the run announces before round 1, in order; _build_run fills the two slots and {unlabelled}, which take the data."""
     def listed(kw):
@@ -445,6 +448,16 @@ def make_plan(args):
                    "batch the pseudo-label, the share of pixels above the threshold the weight of a mean-over-all-pixels CE added to the "
                    "labelled loss; no feature-distance term, one domain, the teacher's BatchNorm buffers copied from the student.  "
                    "Segmentation phase only.  Nothing here says what it does to mIoU: that takes a run on a data set")
+    if args.distill_from is not None:  # (the plan gains this attribute only when distillation is on)
+        p.distill_kw = dict(path=args.distill_from, backbone=args.distill_backbone, kind=args.distill_kind,
+                            temperature=args.distill_temperature, weight=args.distill_weight)
+        say.append(f"[train] --distill-from {args.distill_from} ({listed({k: v for k, v in p.distill_kw.items() if k != 'path'})}): this "
+                   "project's addition, NOT the reference's training (its train.py trains one net on labels alone).  A frozen teacher sees "
+                   "every labelled batch of the segmentation phase, and " + ("channel-wise distillation (Shu et al. 2021: a softmax over "
+                   "the positions of every class map)" if args.distill_kind == "channel" else "per-pixel KD (Hinton et al. 2015: a softmax "
+                   "over the classes of every pixel)") + " between the two nets' quarter-resolution logits is added to the labelled loss; "
+                   "temperature and weight are this project's defaults, no feature-map term, no ignore mask.  Segmentation phase only.  "
+                   "Nothing here says what it does to mIoU: that takes a run on a data set")
     if args.fusion_loss is not None:
         say.append(f"[train] --fusion-loss {args.fusion_loss}: NOT the reference's schedule of objectives")
     p.fusion_iters = [args.fusion_iters if args.fusion_iters is not None else (6000 if r == 1 else 4000) for r in range(1, args.rounds + 1)]
@@ -501,6 +514,12 @@ def _build_run(args, plan):
             + "; sampling probability: " + " ".join(f"{c}:{probe.prob[c]:.4f}" for c in probe.classes)
             + (f"; dropped (no frame with more than {plan.rcs_kw['min_pixels']} pixels): {', '.join(map(str, probe.dropped))}"
                if probe.dropped else "; no class dropped")]
+    teacher, distill_kw = None, getattr(plan, "distill_kw", None)
+    if distill_kw is not None:  # built once, kept across rounds
+        from .distill import FrozenTeacher
+        net = Network3(distill_kw["backbone"], N_CLASS, pretrained=None)
+        net.load_state_dict(torch.load(distill_kw["path"], map_location="cpu"), strict=True)
+        teacher = FrozenTeacher(net.cuda())
     if unl_set is not None and len(unl_set) < plan.batch:
         raise SystemExit(f"[train] --self-training: the unlabelled set holds {len(unl_set)} frames, fewer than one batch of {plan.batch}")
     for line in plan.say:
@@ -510,7 +529,7 @@ def _build_run(args, plan):
         args=args, plan=plan, seg=seg, fus=fus, train_set=train_set, val_set=val_set, unl_set=unl_set, stats=stats, seg_crit=seg_crit,
         crit=torch.nn.CrossEntropyLoss(ignore_index=255), fusion_loss=make_fusion_loss(args.fusion_loss) if args.fusion_loss else None,
         seg_initial=seg_initial, seg_path=os.path.join(args.out, SEG_CKPT), fus_path=os.path.join(args.out, FUSION_CKPT),
-        best=None, wrote_seg=False, opt=None, seg_state=seg_initial, fused_set=None, fused_unl=None)
+        best=None, wrote_seg=False, opt=None, seg_state=seg_initial, fused_set=None, fused_unl=None, teacher=teacher)
 
 
 def _averaged(on, optimizer, net):
@@ -600,11 +619,19 @@ def seg_phase(run, iter_):
                               mix=ClassMix(seed=seed + 7919, **plan.st_mix_kw) if plan.st_mix_kw else None,
                               strong=StrongAugment(seed=seed + 7919, **strong_kw) if strong_kw else None, **st_kw)
         first = [types.SimpleNamespace(line=lambda: f" unlabelled {float(unsup):.6f} confident {st.confident_share():.4f}")]
+    kd, distill_kw = None, getattr(plan, "distill_kw", None)
+    if distill_kw is not None:  # the frozen teacher of _build_run on the same fused3 batch
+        from .distill import DistillStep
+        kd = DistillStep(seg, run.teacher, opt, run.seg_crit, losses.DistillObjective(distill_kw["kind"], distill_kw["temperature"]),
+                         weight=distill_kw["weight"])
+        first = [types.SimpleNamespace(line=lambda: f" distill {float(unsup):.6f}")]
     log = _logger(run, opt, [("seg_net", seg)], batches, *first)  # (`unsup`: the last step's, below)
     n_seg = plan.seg_iters[iter_ - 1]
     for n in range(n_seg):
         _, _, fused3, _, label = next(batches)
-        if st is None:
+        if kd is not None:
+            loss, unsup = kd.step(fused3, label)
+        elif st is None:
             loss = seg_train_step(seg, opt, fused3, label, run.seg_crit)
         else:
             loss, unsup = st.step(fused3, label, next(unl_batches)[2])

@@ -3,10 +3,14 @@ cannot mean together: the tables _BELONGS and _RANGES, then the rules that read 
 segmif_amd.train imports all of it; a new family of flags is one block in the parser and one row in each table."""
 import argparse
 import math
+import os
 
 SEG_CKPT, FUSION_CKPT = "model-fusion_add_final2.pth", "modelfusion-final2.pth"  # train.py:237-238, :403-407
 SEG_LOSSES = ("ce", "ohem", "focal", "normal", "weighted")
 SEG_REGIONS = ("lovasz", "dice")
+DISTILL_KINDS = ("channel", "pixel")
+DISTILL_TEMPERATURES = {"channel": 4.0, "pixel": 1.0}  # losses.DISTILL_TEMPERATURES, restated: this module imports no torch
+DISTILL_BACKBONES = ("mit_b1", "mit_b2", "mit_b3", "mit_b4", "mit_b5")
 
 
 def fusion_loss_names():
@@ -142,6 +146,20 @@ def build_parser():
                     "[0, 1] (default 0.5, DAFormer's)")
     ap.add_argument("--st-blur-sigma", type=float, nargs=2, metavar=("LO", "HI"), help="with --st-strong: the blur's sigma is uniform "
                     "over [LO, HI], 0 < LO <= HI <= 2 (default 0.15 1.15, DAFormer's)")
+    ap.add_argument("--distill-from", metavar="CKPT", help="knowledge distillation in the SEGMENTATION phase: a frozen teacher, the "
+                    f"Network3 state dict CKPT (a file as {SEG_CKPT}, loaded strictly) on --distill-backbone, sees every labelled batch "
+                    "the student sees, and the step adds --distill-weight times a distillation term between the two nets' "
+                    "quarter-resolution logits to the labelled loss (segmif_amd.distill, csrc/distill_objective.hip).  Off by default.  "
+                    "Excludes --self-training (not built).  This project's addition, NOT the reference's training; nothing here says "
+                    "what it does to mIoU")
+    ap.add_argument("--distill-backbone", metavar="NAME", help="with --distill-from, required: the teacher's backbone, mit_b1 .. mit_b5")
+    ap.add_argument("--distill-kind", choices=DISTILL_KINDS, help="with --distill-from: channel (default; channel-wise distillation, "
+                    "Shu et al. 2021: a softmax over the positions of every class map) or pixel (per-pixel KD, Hinton et al. 2015: a "
+                    "softmax over the classes of every pixel)")
+    ap.add_argument("--distill-temperature", type=float, metavar="T", help="with --distill-from: the temperature, > 0 (default 4.0 for "
+                    "channel, 1.0 for pixel; this project's choice)")
+    ap.add_argument("--distill-weight", type=float, metavar="W", help="with --distill-from: weight of the distillation term, > 0 "
+                    "(default 3.0; this project's choice)")
     ap.add_argument("--log-iters", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     return ap
@@ -158,6 +176,7 @@ _BELONGS = (
                          "--st-strong")),
     ("--st-mix", ("--st-mix-prob", "--st-mix-min-pixels")),
     ("--st-strong", ("--st-jitter-prob", "--st-jitter-strength", "--st-jitter-hue", "--st-blur-prob", "--st-blur-sigma")),
+    ("--distill-from", ("--distill-backbone", "--distill-kind", "--distill-temperature", "--distill-weight")),
 )
 # A flag, what a given value of it must satisfy, and the refusal after "FLAG VALUE: ":
 _RANGES = (
@@ -182,6 +201,8 @@ _RANGES = (
     ("--st-jitter-hue", lambda v: 0.0 <= v <= 0.5, "must lie in [0, 0.5]"),
     ("--st-blur-prob", lambda v: 0.0 <= v <= 1.0, "must lie in [0, 1]"),
     ("--st-blur-sigma", lambda v: 0.0 < v[0] <= v[1] <= 2.0, "needs 0 < LO <= HI <= 2"),
+    ("--distill-temperature", lambda v: v > 0 and math.isfinite(v), "must be a finite number > 0"),
+    ("--distill-weight", lambda v: v > 0 and math.isfinite(v), "must be a finite number > 0"),
 )
 # What a flag stands for that defaults to None so that _BELONGS can tell whether it was given (--ohem-n-min: resolve_defaults):
 _DEFAULTS = {
@@ -190,6 +211,7 @@ _DEFAULTS = {
     "--seg-region-weight": 1.0, "--seg-region-classes": "present", "--dice-smooth": 1.0, "--ema-nets": "seg",
     "--st-threshold": 0.968, "--st-below": "keep", "--st-weight": 1.0, "--st-mix-prob": 1.0, "--st-mix-min-pixels": 0,
     "--st-jitter-prob": 0.8, "--st-jitter-strength": 0.2, "--st-jitter-hue": 0.2, "--st-blur-prob": 0.5, "--st-blur-sigma": (0.15, 1.15),
+    "--distill-kind": "channel", "--distill-weight": 3.0,  # (--distill-temperature follows the kind: resolve_defaults)
 }
 
 
@@ -243,6 +265,15 @@ def check_args(args, fail):
         fail("--self-training needs --unlabelled-split NAME (or --synthetic N, which makes a stand-in set)")
     if args.self_training and args.synthetic is not None and args.unlabelled_split is not None:
         fail("--unlabelled-split names a split of --name-lists; --synthetic makes its own unlabelled stand-in set")
+    if args.distill_from is not None:
+        if args.distill_backbone is None:
+            fail("--distill-from needs --distill-backbone NAME: a state dict does not say which backbone it belongs to")
+        if args.distill_backbone == "mit_b0" or args.distill_backbone not in DISTILL_BACKBONES:
+            fail(f"--distill-backbone {args.distill_backbone}: one of {', '.join(DISTILL_BACKBONES)}")
+        if args.self_training:
+            fail("--distill-from with --self-training: distillation on the unlabelled split, or beside self-training, is not built")
+        if not os.path.isfile(args.distill_from):
+            fail(f"--distill-from {args.distill_from}: no such file")
     seg_pixels = max(1, args.samples_per_gpu // 2) * args.crop_size ** 2
     if args.seg_loss == "ohem" and args.ohem_n_min is not None and not 1 <= args.ohem_n_min <= seg_pixels:
         fail(f"--ohem-n-min {args.ohem_n_min}: outside 1..{seg_pixels}, the pixels of a segmentation batch")
@@ -261,5 +292,7 @@ def resolve_defaults(args):
     for flag, value in _DEFAULTS.items():
         if _given(args, flag) is None:
             setattr(args, flag[2:].replace("-", "_"), value)
+    if args.distill_from is not None and args.distill_temperature is None:
+        args.distill_temperature = DISTILL_TEMPERATURES[args.distill_kind]
     if args.ohem_n_min is None:
         args.ohem_n_min = max(1, max(1, args.samples_per_gpu // 2) * args.crop_size ** 2 // 16)
