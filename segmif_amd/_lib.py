@@ -118,6 +118,11 @@ class SegmifDistill(ctypes.Structure):
     _fields_ = [("temperature", c_float), ("mode", c_int32), ("reserved", c_int32 * 2)]
 
 
+class SegmifCalib(ctypes.Structure):
+    _fields_ = [("n_temperatures", c_int32), ("n_edges", c_int32), ("n_thresholds", c_int32), ("reserved0", c_int32),
+                ("temperatures", c_float * 16), ("edges", c_float * 32), ("thresholds", c_float * 8), ("reserved", c_int32 * 4)]
+
+
 class SegmifGradGuardRecord(ctypes.Structure):
     _fields_ = [("sumsq", c_double), ("norm", c_float), ("coef", c_float), ("nonfinite", ctypes.c_uint32),
                 ("skip_now", ctypes.c_uint32), ("attempts", ctypes.c_uint32), ("applied", ctypes.c_uint32),
@@ -356,6 +361,14 @@ DISTILL_SIGNATURES = {
                                                  c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
 }
 
+# the calibration statistics: name -> (restype, argtypes); must list every symbol include/segmif_calib.h declares, and none that
+# include/segmif_hip.h does.  The same library exports them; segmif_abi_version() does not count them.
+CALIB_MAX_TEMPERATURES, CALIB_MAX_EDGES, CALIB_MAX_THRESHOLDS = 16, 31, 8
+CALIB_SIGNATURES = {
+    "segmif_calibration_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
+    "segmif_calibration_stats_f32": (c_int, [POINTER(SegmifCalib)] + [c_void_p] * 9 + [c_int] * 7 + [c_void_p]),
+}
+
 _lib = None
 
 
@@ -378,7 +391,7 @@ def load():
     # kernels' library came up on the system ROCm's runtime and its first launch failed with hipErrorNoDevice (r5).
     import torch  # noqa: F401
     lib = ctypes.CDLL(path)
-    for name, (res, args) in list(SIGNATURES.items()) + list(DISTILL_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(DISTILL_SIGNATURES.items()) + list(CALIB_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: loud by design
         fn.restype = res
         fn.argtypes = args

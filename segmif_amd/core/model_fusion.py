@@ -826,11 +826,13 @@ class Network3(nn.Module):
     def forward(self, fused_seg1):
         return fused_seg1, fused_seg1, ops.as_nchw(self._segment_nhwc(fused_seg1))
 
-    def predict_labels(self, fused, size=None):
-        """test_segmentation.py:169-174 on device: logits -> bilinear to `size` -> argmax (int32, B,H,W)."""
+    def predict_labels(self, fused, size=None, return_logits=False):
+        """test_segmentation.py:169-174 on device: logits -> bilinear to `size` -> argmax (int32, B,H,W).  return_logits: ->
+        (labels, the quarter-resolution NHWC logits they were taken from) - what utils/calibration.calibration_stats reads."""
         seg = self._segment_nhwc(fused)
         H, W = size if size is not None else fused.shape[2:]
-        return ops.bilinear_argmax(seg, H, W)  # (r6: one pass - the resized logits, 708 MB per 64 images, are never written)
+        labels = ops.bilinear_argmax(seg, H, W)  # (r6: one pass - the resized logits, 708 MB per 64 images, are never written)
+        return (labels, seg) if return_logits else labels
 
     def predict_labels_tta(self, fused, size=None, tta=TTA(), return_probs=False, segment=None):
         """Multi-scale + flip inference: one forward per view of tta.plan(H, W) - the input resized (and mirrored) by

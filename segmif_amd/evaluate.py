@@ -5,6 +5,7 @@
         [--seg-ckpt F] [--fusion-ckpt F] [--batch N] [--json F] [--structural-scores]
         [--ms-scales S [S ...]] [--flip] [--size-divisor N]
         [--boundary-scores [--boundary-width D] [--bf-tolerance T] [--boundary-ratio R] [--bf-ratio R]]
+        [--calibration [--calibration-bins M] [--calibration-temperatures T [T ...]] [--calibration-thresholds TAU [TAU ...]]]
 
 reads the sorted file names of --vis (TaskFusion_dataset2.py:40-48) from every folder (.npy always, .png when PIL imports),
 and writes OUT/Fused/NAME, OUT/Seg/NAME (palette rendering) and a JSON of the results.  --structural-scores adds Qabf, SSIM and
@@ -13,7 +14,10 @@ VIF (utils/fusion_metrics.structural_scores; images of at least 41 x 41) to the 
 names the views under "tta"); the fused images and their scores do not change.  --boundary-scores (with --label) adds the
 contour scores of the label maps: Boundary IoU, the trimap-band mIoU and the boundary F-score (utils/metrics.boundary_scores;
 the JSON names the widths under "boundary"); the widths follow the frame's diagonal unless --boundary-width / --bf-tolerance
-give them in pixels.
+give them in pixels.  --calibration (with --label) scores the softmax confidence instead of the labels: reliability table, ECE,
+MCE, NLL and Brier score for a list of temperatures, coverage and precision above confidence thresholds, and the temperature of the
+list with the lowest NLL (utils/calibration.calibration_scores; the JSON names the settings under "calibration").  Not with
+--ms-scales / --flip.  On seeded weights the figures mean nothing.
 """
 import argparse
 import json
@@ -28,6 +32,7 @@ from .pipeline import PairForward
 from .tta import TTA
 from .utils.fusion_metrics import (MFNET_PALETTE, SCORE_NAMES, STRUCTURAL_SCORE_NAMES, colorize, fusion_scores, fusion_stats,
                                    structural_scores, structural_stats)
+from .utils.calibration import CalibrationTable, calibration_scores, calibration_stats, table_settings
 from .utils.metrics import (_dev, _stream, boundary_scores, boundary_stats, boundary_widths, compute_results,
                             confusion_matrix)
 
@@ -51,12 +56,26 @@ class Evaluator:
     gathers Qabf, SSIM and VIF (STRUCTURAL_SCORE_NAMES) of every pair.  tta: a segmif_amd.tta.TTA - the labels (and the mIoU)
     come from multi-scale + flip inference (PairForward(tta=)); not with graph=True.  boundary: None, or a dict with any of d,
     theta (widths in pixels) and ratio, bf_ratio (utils/metrics.boundary_widths; a width not given follows the frame's
-    diagonal) - the contour tables of utils/metrics.boundary_stats are then summed over every labelled batch."""
+    diagonal) - the contour tables of utils/metrics.boundary_stats are then summed over every labelled batch.  calibration: None, or a
+    dict with any of bins (default 15 equal ones), temperatures (default utils/calibration.DEFAULT_TEMPERATURES) and thresholds
+    (default (0.968,)) - one utils/calibration.CalibrationTable is then summed over every labelled batch on the device, from the
+    logits PairForward(return_logits=True) hands out; nothing is read back per batch.  Not with tta= (the vote's probabilities are
+    not logits: not built)."""
 
-    def __init__(self, seg_net, fusion_net, n_class=9, graph=False, structural=False, tta=None, boundary=None):
+    def __init__(self, seg_net, fusion_net, n_class=9, graph=False, structural=False, tta=None, boundary=None, calibration=None):
         if tta is not None and graph:
             raise NotImplementedError("Evaluator: graph=True cannot capture the multi-size forward (tta=)")
-        self.pair = PairForward(seg_net, fusion_net, uint8_roundtrip=True, return_u8=True, tta=tta)
+        if calibration is not None and tta is not None:
+            raise NotImplementedError("Evaluator: calibration= with tta=: the vote averages probabilities over views, which are not "
+                                      "logits; calibration of the voted probabilities is not built")
+        if calibration is not None and set(calibration) - {"bins", "temperatures", "thresholds"}:
+            raise ValueError(f"Evaluator: calibration= takes bins, temperatures and thresholds, got {sorted(calibration)}")
+        self.calibration = None if calibration is None else dict(calibration)
+        self._calibration = None     # the CalibrationTable on the device, from the first labelled batch on
+        if calibration is not None:  # (the settings' own checks, before any batch)
+            self._calibration_kw = table_settings(**self.calibration)
+            CalibrationTable.zeros("cpu", **self._calibration_kw)
+        self.pair = PairForward(seg_net, fusion_net, uint8_roundtrip=True, return_u8=True, tta=tta, return_logits=calibration is not None)
         self.tta = tta
         self._frame = None
         self.n_class = n_class
@@ -106,10 +125,14 @@ class Evaluator:
                     self._graph_shape = tuple(vis.shape)
                 if tuple(vis.shape) != self._graph_shape:
                     raise RuntimeError(f"the captured graph serves batches of shape {self._graph_shape}, got {tuple(vis.shape)}")
-                _, labels, fused_u8 = self.pair.replay(ir, vis, mask3)
+                out = self.pair.replay(ir, vis, mask3)
+                labels, fused_u8 = out[1], out[2]
                 fused_u8, labels = fused_u8.clone(), labels.clone()  # (the graph's output buffers are overwritten by the next replay)
+                logits = out[3].clone() if self.calibration is not None else None
             else:
-                _, labels, fused_u8 = self.pair.eager(ir, vis, mask3)
+                out = self.pair.eager(ir, vis, mask3)
+                labels, fused_u8 = out[1], out[2]
+                logits = out[3] if self.calibration is not None else None
             self._frame = tuple(vis.shape[2:])
             self._scores.append(fusion_stats(fused_u8, vis_u8, ir_u8))
             if self.structural:
@@ -119,6 +142,8 @@ class Evaluator:
                 self._conf = confusion_matrix(labels, label, self.n_class, out=self._conf)
                 if self.boundary is not None:
                     self._boundary_update(labels.contiguous(), label.reshape(labels.shape))
+                if self.calibration is not None:
+                    self._calibration = calibration_stats(logits, label.reshape(labels.shape), out=self._calibration, **self._calibration_kw)
         return fused_u8, labels
 
     def results(self):
@@ -126,7 +151,8 @@ class Evaluator:
         and, when labels were given, 'precision' / 'recall' / 'iou' per class (compute_results) and 'mIoU' =
         mean(nan_to_num(iou)), the figure test_segmentation.py prints for data that lack a class.  With structural=True the
         scores of STRUCTURAL_SCORE_NAMES are added in the same two places; with boundary= and labels, the keys of
-        utils/metrics.boundary_scores."""
+        utils/metrics.boundary_scores; with calibration= and labels, the keys of utils/calibration.calibration_scores (one
+        readback)."""
         per = [fusion_scores(s) for s in self._scores]
         names = SCORE_NAMES
         if self.structural:
@@ -139,12 +165,15 @@ class Evaluator:
             out.update(precision=precision, recall=recall, iou=iou, mIoU=float(np.mean(np.nan_to_num(iou))))
         if self._boundary is not None:
             out.update(boundary_scores(*self._boundary))
+        if self._calibration is not None:
+            out.update(calibration_scores(self._calibration))
         return out
 
     def document(self, names, seeded_weights, res=None):
         """What the command line writes as JSON: the names, which networks ran on seeded weights, results() (or `res`, if the
         caller has them) with arrays as lists, - only with tta - its settings and the views of the last batch's frame size
-        under "tta" and - only with boundary= and labels - the widths and the frame size they were derived for under "boundary"."""
+        under "tta", - only with boundary= and labels - the widths and the frame size they were derived for under "boundary" and
+        - only with calibration= and labels - the bins, temperatures and thresholds under "calibration"."""
         doc = {"names": list(names), "seeded_weights": list(seeded_weights)}
         for k, v in (self.results() if res is None else res).items():
             doc[k] = v.tolist() if isinstance(v, np.ndarray) else v
@@ -154,6 +183,8 @@ class Evaluator:
             doc["tta"] = self.tta.describe(*self._frame)
         if self._boundary_doc is not None:
             doc["boundary"] = dict(self._boundary_doc)
+        if self._calibration is not None:
+            doc["calibration"] = self._calibration.settings()
         return doc
 
 
@@ -209,7 +240,28 @@ def parse_args(argv=None):
     ap.add_argument("--bf-tolerance", type=int, metavar="T", help="contour tolerance in pixels, 0..31 (default: --bf-ratio x the diagonal)")
     ap.add_argument("--boundary-ratio", type=float, metavar="R", help="band half-width as a share of the frame's diagonal (default 0.02)")
     ap.add_argument("--bf-ratio", type=float, metavar="R", help="contour tolerance as a share of the frame's diagonal (default 0.0075)")
+    ap.add_argument("--calibration", action="store_true",
+                    help="also score the softmax confidence: reliability table, ECE, MCE, NLL, Brier score and the temperature of lowest "
+                         "NLL (needs --label; not with --ms-scales / --flip).  This project's addition, not the reference's evaluation")
+    ap.add_argument("--calibration-bins", type=int, metavar="M", help="equal confidence bins, 1..32 (default 15)")
+    ap.add_argument("--calibration-temperatures", type=float, nargs="+", metavar="T",
+                    help="the temperatures scored, at most 16, each finite and > 0 (default: 1.0 and 15 log-spaced values over [0.5, 4])")
+    ap.add_argument("--calibration-thresholds", type=float, nargs="+", metavar="TAU",
+                    help="coverage and precision are reported above each, at most 8 in [0, 1] (default 0.968, self-training's)")
     args = ap.parse_args(argv)
+    cal_given = [f for f, v in (("--calibration-bins", args.calibration_bins), ("--calibration-temperatures", args.calibration_temperatures),
+                                ("--calibration-thresholds", args.calibration_thresholds)) if v is not None]
+    if args.calibration and not args.label:
+        ap.error("--calibration compares the confidence with the ground truth: it needs --label")
+    if cal_given and not args.calibration:
+        ap.error(f"{', '.join(cal_given)} only with --calibration")
+    if args.calibration and (args.ms_scales is not None or args.flip):
+        ap.error("--calibration with --ms-scales / --flip: the vote's probabilities are not logits; their calibration is not built")
+    if args.calibration:
+        try:
+            CalibrationTable.zeros("cpu", **table_settings(**calibration_settings(args)))
+        except ValueError as e:
+            ap.error(str(e))
     given = [f for f, v in (("--boundary-width", args.boundary_width), ("--bf-tolerance", args.bf_tolerance),
                             ("--boundary-ratio", args.boundary_ratio), ("--bf-ratio", args.bf_ratio)) if v is not None]
     if args.boundary_scores and not args.label:
@@ -234,6 +286,15 @@ def boundary_settings(args):
     return {k: v for k, v in pairs if v is not None}
 
 
+def calibration_settings(args):
+    """the Evaluator's calibration= for a parsed command line: None without --calibration, else the flags that were given"""
+    if not args.calibration:
+        return None
+    pairs = (("bins", args.calibration_bins), ("temperatures", args.calibration_temperatures), ("thresholds", args.calibration_thresholds))
+    kw = {k: (v if k == "bins" else tuple(v)) for k, v in pairs if v is not None}
+    return kw
+
+
 def main(argv=None):
     args, tta = parse_args(argv)
     if not torch.cuda.is_available():
@@ -248,7 +309,7 @@ def main(argv=None):
         else:
             print(f"[evaluate] no checkpoint for the {what} network: running on SEEDED RANDOM weights (torch.manual_seed(0))")
     seg, fus = seg.cuda().eval(), fus.cuda().eval()
-    ev = Evaluator(seg, fus, structural=args.structural_scores, tta=tta, boundary=boundary_settings(args))
+    ev = Evaluator(seg, fus, structural=args.structural_scores, tta=tta, boundary=boundary_settings(args), calibration=calibration_settings(args))
     names = _names(args.vis)
     if not names:
         raise RuntimeError(f"no .npy / .png files in {args.vis}")
@@ -274,7 +335,9 @@ def main(argv=None):
     with open(path, "w") as f:
         json.dump(doc, f, indent=1)
     print("[evaluate] " + "  ".join(f"{k} {res['mean'][k]:.4f}" for k in res["mean"]) + (f"  mIoU {res['mIoU']:.4f}" if "mIoU" in res else "")
-          + (f"  mBIoU {res['mBIoU']:.4f}  trimap {res['trimap_mIoU']:.4f}  mBF {res['mBF']:.4f}" if "mBIoU" in res else ""))
+          + (f"  mBIoU {res['mBIoU']:.4f}  trimap {res['trimap_mIoU']:.4f}  mBF {res['mBF']:.4f}" if "mBIoU" in res else "")
+          + (f"  ECE {res['ece'][0]:.4f}  NLL {res['nll'][0]:.4f} (T {res['temperatures'][0]:g})  T* {res['best']['temperature']:.3f}"
+             if res.get("best") is not None else ""))
     print(f"[evaluate] wrote {path}")
     return 0
 

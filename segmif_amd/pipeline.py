@@ -10,7 +10,7 @@ from .utils.metrics import dequantize_fused, quantize_fused
 
 
 class PairForward:
-    def __init__(self, seg_net, fusion_net, commute_resize=True, uint8_roundtrip=False, return_u8=False, tta=None):
+    def __init__(self, seg_net, fusion_net, commute_resize=True, uint8_roundtrip=False, return_u8=False, tta=None, return_logits=False):
         """uint8_roundtrip: the reference's scripted flow hands the fused image from test_fusion.py to
         test_segmentation.py through uint8 PNG files (uint8(255 x), global min-max rescale over the batch, uint8 -
         test_fusion.py:112-120; read back as float32 / 255 - TaskFusion_dataset2.py:84-88).  True reproduces that
@@ -20,8 +20,14 @@ class PairForward:
         produced inside the body - the PNG pixels themselves (quantising the returned float again would truncate:
         uint8(255 (u / 255)) is not u for every u, and the min-max rescale would run twice).
         tta: a segmif_amd.tta.TTA - the labels are the multi-scale + flip vote Network3.predict_labels_tta forms from the
-        same fused image (`fused` and the uint8 image are unchanged); eager only, capture() refuses."""
+        same fused image (`fused` and the uint8 image are unchanged); eager only, capture() refuses.
+        return_logits: every call returns one more, LAST value, the segmentation net's quarter-resolution NHWC logits
+        (B, H/4, W/4, n_class) the labels were taken from (utils/calibration reads them); not with tta=, whose vote has no single
+        logit map.  With the default the tuples, the launches and the bits are what they are without the argument."""
         self.tta = tta
+        if return_logits and tta is not None:
+            raise ValueError("return_logits=True with tta=: the vote averages probabilities over views, there is no logit map to return")
+        self.return_logits = bool(return_logits)
         if return_u8 and not uint8_roundtrip:
             raise ValueError("return_u8=True needs uint8_roundtrip=True (there is no uint8 image otherwise)")
         self.return_u8 = return_u8
@@ -33,7 +39,7 @@ class PairForward:
         self._static = None
 
     def eager(self, ir, vis, mask3):
-        """-> (fused RGB (B,3,H,W), labels int32 (B,H,W)) [, fused uint8 (B,H,W,3) with return_u8].  One guarded scope around the whole pair forward: the encoder's
+        """-> (fused RGB (B,3,H,W), labels int32 (B,H,W)) [, fused uint8 (B,H,W,3) with return_u8] [, logits with return_logits].  One guarded scope around the whole pair forward: the encoder's
         tall GEMMs and the fusion net's 3x3 convs run on f16x3 operands, their range slots - one per pair - are read back once
         at the end and exactly the pairs whose activations left the half's exponent range are computed again on the bf16x6
         kernels (a pair's result does not depend on what else is in the batch); (r5) pairs whose CrossPath context softmax
@@ -49,6 +55,8 @@ class PairForward:
         out[1].index_copy_(0, idx, labels)
         if self.return_u8:
             out[2].index_copy_(0, idx, part[2])
+        if self.return_logits:
+            out[-1].index_copy_(0, idx, part[-1])
         return out
 
     def _eager_body(self, ir, vis, mask3):
@@ -64,6 +72,9 @@ class PairForward:
             fused = dequantize_fused(u8)
         if self.tta is not None:  # (the range guard's redo runs this body again for the flagged pairs: every view's forward too)
             labels = self.seg.predict_labels_tta(fused, vis.shape[2:], self.tta)
+        elif self.return_logits:
+            labels, logits = self.seg.predict_labels(fused, vis.shape[2:], return_logits=True)
+            return (fused, labels, u8, logits) if self.return_u8 else (fused, labels, logits)
         else:
             labels = self.seg.predict_labels(fused, vis.shape[2:])
         return (fused, labels, u8) if self.return_u8 else (fused, labels)

@@ -17,6 +17,7 @@ without it the student sees the teacher's pixels, and with it the colour jitter'
 follows the image's), and neither the labelled batch nor the geometry of the student's input is touched.  Nothing here says
 what it does to mIoU."""
 import copy
+import math
 
 import numpy as np
 import torch
@@ -116,10 +117,12 @@ class SelfTrainingStep:
     ALL pixels (SEGMIF_SEG_MEAN_ALL, what DAFormer computes: (loss * weight).mean()) with u = q_b per sample, or the mixed weight
     plane.  Two student forwards and backwards, gradients accumulated (under a reducer: one backward of the sum).  step() returns
     (loss_sup, loss_unsup) detached; the last count of confident pixels stays on the device: confident_share() reads it back, once
-    per log line.  Not graph-captured."""
+    per log line.  teacher_temperature T (utils/calibration.fit_temperature measures one): the teacher's logits are multiplied by
+    float32(1 / T) before ops.pseudo_label, so tau tests the softmax at temperature T; the argmax does not change.  Not
+    graph-captured."""
 
     def __init__(self, student, teacher, optimizer, criterion, tau=0.968, below="keep", unsup_weight=1.0, mix=None, reducer=None,
-                 ignore_index=255, strong=None):
+                 ignore_index=255, teacher_temperature=1.0, strong=None):
         if not 0.0 <= float(tau) <= 1.0:
             raise ValueError(f"SelfTrainingStep: tau {tau} outside [0, 1]")
         if below not in ops.PSEUDO_BELOW:
@@ -131,12 +134,18 @@ class SelfTrainingStep:
         self.ignore_index = int(ignore_index)
         self.unsup = losses.SegObjective(reduction="mean_all", ignore_index=self.ignore_index)
         self.strong = strong
+        self.teacher_temperature = float(teacher_temperature)
+        if not (math.isfinite(self.teacher_temperature) and self.teacher_temperature > 0.0):
+            raise ValueError(f"SelfTrainingStep: teacher_temperature {teacher_temperature} must be finite and > 0")
         self.last_count, self.last_pixels, self.last_table, self.last_strong = None, 0, None, None
 
     def pseudo(self, xU):
         """-> (pseudo-labels (B, H, W) int64, q (B,) float32) of the teacher on xU; keeps the count"""
         H, W = xU.shape[2:]
-        labels, count = ops.pseudo_label(self.teacher.logits(xU), H, W, tau=self.tau, below=self.below, ignore_index=self.ignore_index)
+        logits = self.teacher.logits(xU)
+        if self.teacher_temperature != 1.0:  # (at 1.0 no operation is added: the bits are what they were)
+            logits = logits * float(np.float32(1.0) / np.float32(self.teacher_temperature))
+        labels, count = ops.pseudo_label(logits, H, W, tau=self.tau, below=self.below, ignore_index=self.ignore_index)
         self.last_count, self.last_pixels = count, H * W
         return labels, ops.pseudo_weight(count, H, W)
 

@@ -434,6 +434,8 @@ def make_plan(args):
                    "loader (its train.py mixes nothing): classes of one crop of a batch are pasted into another, images and label alike")
     if args.self_training:
         p.st_kw = dict(tau=args.st_threshold, below=args.st_below, unsup_weight=args.st_weight)
+        if args.st_temperature != 1.0:  # (the keyword exists only when the flag changes something)
+            p.st_kw["teacher_temperature"] = args.st_temperature
         if args.st_mix:
             p.st_mix_kw = dict(prob=args.st_mix_prob, classes="half", min_pixels=args.st_mix_min_pixels, n_class=N_CLASS)
         st_said, strong_kw = listed(p.st_kw), None

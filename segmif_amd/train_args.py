@@ -126,6 +126,9 @@ def build_parser():
     ap.add_argument("--st-below", choices=("keep", "ignore"), help="with --self-training: keep the pseudo-label of a pixel that is not "
                     "confident (default; DAFormer: the per-image weight carries the confidence) or set it to the ignore value")
     ap.add_argument("--st-weight", type=float, metavar="W", help="with --self-training: weight of the unlabelled term, > 0 (default 1.0)")
+    ap.add_argument("--st-temperature", type=float, metavar="T", help="with --self-training: the teacher's logits are divided by T, "
+                    "finite and > 0, before the confidence test (default 1.0: nothing is added; python -m segmif_amd.evaluate --calibration "
+                    "reports the temperature of lowest NLL)")
     ap.add_argument("--st-mix", action="store_true", help="with --self-training: paste half of the classes of labelled sample i into "
                     "unlabelled sample i (DAFormer's cross-set ClassMix, on csrc/class_mix.hip); pasted pixels get weight 1")
     ap.add_argument("--st-mix-prob", type=float, metavar="P", help="with --st-mix: the probability that a sample is mixed, in (0, 1] "
@@ -173,7 +176,7 @@ _BELONGS = (
     ("--class-mix", ("--class-mix-prob", "--class-mix-min-pixels", "--class-mix-classes", "--class-mix-phases")),
     ("--seg-region", ("--seg-region-weight", "--seg-region-classes", "--dice-smooth")),
     ("--self-training", ("--unlabelled-split", "--st-threshold", "--st-below", "--st-weight", "--st-mix", "--st-mix-prob", "--st-mix-min-pixels",
-                         "--st-strong")),
+                         "--st-strong", "--st-temperature")),
     ("--st-mix", ("--st-mix-prob", "--st-mix-min-pixels")),
     ("--st-strong", ("--st-jitter-prob", "--st-jitter-strength", "--st-jitter-hue", "--st-blur-prob", "--st-blur-sigma")),
     ("--distill-from", ("--distill-backbone", "--distill-kind", "--distill-temperature", "--distill-weight")),
@@ -194,6 +197,7 @@ _RANGES = (
     ("--ema-decay", lambda v: 0.0 < v < 1.0, "must lie inside (0, 1)"),
     ("--st-threshold", lambda v: 0.0 <= v <= 1.0, "must lie in [0, 1]"),
     ("--st-weight", lambda v: v > 0 and math.isfinite(v), "must be a finite number > 0"),
+    ("--st-temperature", lambda v: v > 0 and math.isfinite(v), "must be a finite number > 0"),
     ("--st-mix-prob", lambda v: 0.0 < v <= 1.0, "must lie in (0, 1]"),
     ("--st-mix-min-pixels", lambda v: v >= 0, "must be >= 0"),
     ("--st-jitter-prob", lambda v: 0.0 <= v <= 1.0, "must lie in [0, 1]"),
@@ -209,7 +213,7 @@ _DEFAULTS = {
     "--rcs-temperature": 0.01, "--rcs-min-pixels": 3000, "--rcs-min-crop-ratio": 0.5, "--rcs-fraction": 1.0, "--rcs-phases": "seg",
     "--class-mix-prob": 0.5, "--class-mix-classes": "half", "--class-mix-min-pixels": 0, "--class-mix-phases": "seg",
     "--seg-region-weight": 1.0, "--seg-region-classes": "present", "--dice-smooth": 1.0, "--ema-nets": "seg",
-    "--st-threshold": 0.968, "--st-below": "keep", "--st-weight": 1.0, "--st-mix-prob": 1.0, "--st-mix-min-pixels": 0,
+    "--st-threshold": 0.968, "--st-below": "keep", "--st-weight": 1.0, "--st-temperature": 1.0, "--st-mix-prob": 1.0, "--st-mix-min-pixels": 0,
     "--st-jitter-prob": 0.8, "--st-jitter-strength": 0.2, "--st-jitter-hue": 0.2, "--st-blur-prob": 0.5, "--st-blur-sigma": (0.15, 1.15),
     "--distill-kind": "channel", "--distill-weight": 3.0,  # (--distill-temperature follows the kind: resolve_defaults)
 }
