@@ -123,6 +123,10 @@ class SegmifCalib(ctypes.Structure):
                 ("temperatures", c_float * 16), ("edges", c_float * 32), ("thresholds", c_float * 8), ("reserved", c_int32 * 4)]
 
 
+class SegmifObjects(ctypes.Structure):
+    _fields_ = [("connectivity", c_int32), ("n_edges", c_int32), ("edges", c_int64 * 4), ("reserved", c_int32 * 4)]
+
+
 class SegmifGradGuardRecord(ctypes.Structure):
     _fields_ = [("sumsq", c_double), ("norm", c_float), ("coef", c_float), ("nonfinite", ctypes.c_uint32),
                 ("skip_now", ctypes.c_uint32), ("attempts", ctypes.c_uint32), ("applied", ctypes.c_uint32),
@@ -369,6 +373,14 @@ CALIB_SIGNATURES = {
     "segmif_calibration_stats_f32": (c_int, [POINTER(SegmifCalib)] + [c_void_p] * 9 + [c_int] * 7 + [c_void_p]),
 }
 
+# the object-level statistics: name -> (restype, argtypes); must list every symbol include/segmif_objects.h declares, and none that
+# include/segmif_hip.h does.  The same library exports them; segmif_abi_version() does not count them.
+OBJECTS_MAX_EDGES, OBJECTS_DECILES, OBJECTS_MAX_FRAMES, OBJECTS_WORKSPACE_PER_PIXEL = 3, 11, 32767, 26
+OBJECT_SIGNATURES = {
+    "segmif_object_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "segmif_object_stats_i32": (c_int, [POINTER(SegmifObjects)] + [c_void_p] * 8 + [c_int] * 4 + [c_void_p]),
+}
+
 _lib = None
 
 
@@ -391,7 +403,8 @@ def load():
     # kernels' library came up on the system ROCm's runtime and its first launch failed with hipErrorNoDevice (r5).
     import torch  # noqa: F401
     lib = ctypes.CDLL(path)
-    for name, (res, args) in list(SIGNATURES.items()) + list(DISTILL_SIGNATURES.items()) + list(CALIB_SIGNATURES.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(DISTILL_SIGNATURES.items()) + list(CALIB_SIGNATURES.items())
+                               + list(OBJECT_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: loud by design
         fn.restype = res
         fn.argtypes = args

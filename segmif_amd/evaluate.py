@@ -6,6 +6,7 @@
         [--ms-scales S [S ...]] [--flip] [--size-divisor N]
         [--boundary-scores [--boundary-width D] [--bf-tolerance T] [--boundary-ratio R] [--bf-ratio R]]
         [--calibration [--calibration-bins M] [--calibration-temperatures T [T ...]] [--calibration-thresholds TAU [TAU ...]]]
+        [--object-scores [--object-connectivity {4,8}] [--object-size-edges A [B [C]]] [--object-coverage TAU]]
 
 reads the sorted file names of --vis (TaskFusion_dataset2.py:40-48) from every folder (.npy always, .png when PIL imports),
 and writes OUT/Fused/NAME, OUT/Seg/NAME (palette rendering) and a JSON of the results.  --structural-scores adds Qabf, SSIM and
@@ -17,7 +18,10 @@ the JSON names the widths under "boundary"); the widths follow the frame's diago
 give them in pixels.  --calibration (with --label) scores the softmax confidence instead of the labels: reliability table, ECE,
 MCE, NLL and Brier score for a list of temperatures, coverage and precision above confidence thresholds, and the temperature of the
 list with the lowest NLL (utils/calibration.calibration_scores; the JSON names the settings under "calibration").  Not with
---ms-scales / --flip.  On seeded weights the figures mean nothing.
+--ms-scales / --flip.  --object-scores (with --label) adds the object-level scores of the label maps: the share of the ground
+truth's connected components of each class that the prediction covers to at least --object-coverage (default 0.5), the share of the
+prediction's components that the ground truth covers, their F1, and the same by size bucket (utils/objects.object_scores; the JSON
+names the settings under "objects").  On seeded weights the figures mean nothing.
 """
 import argparse
 import json
@@ -33,6 +37,7 @@ from .tta import TTA
 from .utils.fusion_metrics import (MFNET_PALETTE, SCORE_NAMES, STRUCTURAL_SCORE_NAMES, colorize, fusion_scores, fusion_stats,
                                    structural_scores, structural_stats)
 from .utils.calibration import CalibrationTable, calibration_scores, calibration_stats, table_settings
+from .utils.objects import DEFAULT_SIZE_EDGES, ObjectTable, coverage_decile, object_scores, object_stats
 from .utils.metrics import (_dev, _stream, boundary_scores, boundary_stats, boundary_widths, compute_results,
                             confusion_matrix)
 
@@ -60,9 +65,12 @@ class Evaluator:
     dict with any of bins (default 15 equal ones), temperatures (default utils/calibration.DEFAULT_TEMPERATURES) and thresholds
     (default (0.968,)) - one utils/calibration.CalibrationTable is then summed over every labelled batch on the device, from the
     logits PairForward(return_logits=True) hands out; nothing is read back per batch.  Not with tta= (the vote's probabilities are
-    not logits: not built)."""
+    not logits: not built).  objects: None, or a dict with any of connectivity (default 8), size_edges (default
+    utils/objects.DEFAULT_SIZE_EDGES) and coverage (default 0.5) - one utils/objects.ObjectTable is then summed over every labelled
+    batch on the device; nothing is read back per batch.  It reads the label maps only, so it works with graph=True and tta= alike."""
 
-    def __init__(self, seg_net, fusion_net, n_class=9, graph=False, structural=False, tta=None, boundary=None, calibration=None):
+    def __init__(self, seg_net, fusion_net, n_class=9, graph=False, structural=False, tta=None, boundary=None, calibration=None,
+                 objects=None):
         if tta is not None and graph:
             raise NotImplementedError("Evaluator: graph=True cannot capture the multi-size forward (tta=)")
         if calibration is not None and tta is not None:
@@ -70,6 +78,16 @@ class Evaluator:
                                       "logits; calibration of the voted probabilities is not built")
         if calibration is not None and set(calibration) - {"bins", "temperatures", "thresholds"}:
             raise ValueError(f"Evaluator: calibration= takes bins, temperatures and thresholds, got {sorted(calibration)}")
+        if objects is not None and set(objects) - {"connectivity", "size_edges", "coverage"}:
+            raise ValueError(f"Evaluator: objects= takes connectivity, size_edges and coverage, got {sorted(objects)}")
+        self.objects = None if objects is None else dict(objects)
+        self._objects = None         # the ObjectTable of sums on the device, from the first labelled batch on
+        if objects is not None:      # (the settings' own checks, before any batch)
+            self._objects_kw = dict(n_class=n_class, connectivity=self.objects.get("connectivity", 8),
+                                    size_edges=tuple(self.objects.get("size_edges", DEFAULT_SIZE_EDGES)))
+            self._objects_coverage = float(self.objects.get("coverage", 0.5))
+            coverage_decile(self._objects_coverage)
+            ObjectTable.zeros("cpu", **self._objects_kw)
         self.calibration = None if calibration is None else dict(calibration)
         self._calibration = None     # the CalibrationTable on the device, from the first labelled batch on
         if calibration is not None:  # (the settings' own checks, before any batch)
@@ -144,6 +162,10 @@ class Evaluator:
                     self._boundary_update(labels.contiguous(), label.reshape(labels.shape))
                 if self.calibration is not None:
                     self._calibration = calibration_stats(logits, label.reshape(labels.shape), out=self._calibration, **self._calibration_kw)
+                if self.objects is not None:
+                    if self._objects is None:
+                        self._objects = ObjectTable.zeros(labels.device, **self._objects_kw)
+                    object_stats(labels.contiguous(), label.reshape(labels.shape), out=self._objects, **self._objects_kw)
         return fused_u8, labels
 
     def results(self):
@@ -152,7 +174,7 @@ class Evaluator:
         mean(nan_to_num(iou)), the figure test_segmentation.py prints for data that lack a class.  With structural=True the
         scores of STRUCTURAL_SCORE_NAMES are added in the same two places; with boundary= and labels, the keys of
         utils/metrics.boundary_scores; with calibration= and labels, the keys of utils/calibration.calibration_scores (one
-        readback)."""
+        readback); with objects= and labels, the keys of utils/objects.object_scores (one readback)."""
         per = [fusion_scores(s) for s in self._scores]
         names = SCORE_NAMES
         if self.structural:
@@ -167,13 +189,16 @@ class Evaluator:
             out.update(boundary_scores(*self._boundary))
         if self._calibration is not None:
             out.update(calibration_scores(self._calibration))
+        if self._objects is not None:
+            out.update(object_scores(self._objects, self._objects_coverage))
         return out
 
     def document(self, names, seeded_weights, res=None):
         """What the command line writes as JSON: the names, which networks ran on seeded weights, results() (or `res`, if the
         caller has them) with arrays as lists, - only with tta - its settings and the views of the last batch's frame size
         under "tta", - only with boundary= and labels - the widths and the frame size they were derived for under "boundary" and
-        - only with calibration= and labels - the bins, temperatures and thresholds under "calibration"."""
+        - only with calibration= and labels - the bins, temperatures and thresholds under "calibration" and - only with objects= and
+        labels - the connectivity, size edges and coverage under "objects"."""
         doc = {"names": list(names), "seeded_weights": list(seeded_weights)}
         for k, v in (self.results() if res is None else res).items():
             doc[k] = v.tolist() if isinstance(v, np.ndarray) else v
@@ -185,6 +210,8 @@ class Evaluator:
             doc["boundary"] = dict(self._boundary_doc)
         if self._calibration is not None:
             doc["calibration"] = self._calibration.settings()
+        if self._objects is not None:
+            doc["objects"] = dict(self._objects.settings(), coverage=self._objects_coverage)
         return doc
 
 
@@ -248,7 +275,28 @@ def parse_args(argv=None):
                     help="the temperatures scored, at most 16, each finite and > 0 (default: 1.0 and 15 log-spaced values over [0.5, 4])")
     ap.add_argument("--calibration-thresholds", type=float, nargs="+", metavar="TAU",
                     help="coverage and precision are reported above each, at most 8 in [0, 1] (default 0.968, self-training's)")
+    ap.add_argument("--object-scores", action="store_true",
+                    help="also report object-level recall, precision and F1 of the label maps' connected components, by class and by "
+                         "size (needs --label).  This project's addition, not the reference's evaluation")
+    ap.add_argument("--object-connectivity", type=int, choices=(4, 8), help="pixels join across edges (4) or edges and corners (8, the default)")
+    ap.add_argument("--object-size-edges", type=int, nargs="+", metavar="A",
+                    help="at most 3 ascending areas in pixels that separate the size buckets (default 1024 9216, COCO's)")
+    ap.add_argument("--object-coverage", type=float, metavar="TAU",
+                    help="an object counts as found when at least this share of it is covered: one of 0.1, 0.2 ... 1.0 (default 0.5)")
     args = ap.parse_args(argv)
+    obj_given = [f for f, v in (("--object-connectivity", args.object_connectivity), ("--object-size-edges", args.object_size_edges),
+                                ("--object-coverage", args.object_coverage)) if v is not None]
+    if args.object_scores and not args.label:
+        ap.error("--object-scores compares the label maps' objects with the ground truth's: it needs --label")
+    if obj_given and not args.object_scores:
+        ap.error(f"{', '.join(obj_given)} only with --object-scores")
+    if args.object_scores:
+        try:
+            kw = object_settings(args)
+            ObjectTable.zeros("cpu", 9, kw.get("connectivity", 8), kw.get("size_edges", DEFAULT_SIZE_EDGES))
+            coverage_decile(kw.get("coverage", 0.5))
+        except ValueError as e:
+            ap.error(str(e))
     cal_given = [f for f, v in (("--calibration-bins", args.calibration_bins), ("--calibration-temperatures", args.calibration_temperatures),
                                 ("--calibration-thresholds", args.calibration_thresholds)) if v is not None]
     if args.calibration and not args.label:
@@ -295,6 +343,14 @@ def calibration_settings(args):
     return kw
 
 
+def object_settings(args):
+    """the Evaluator's objects= for a parsed command line: None without --object-scores, else the flags that were given"""
+    if not args.object_scores:
+        return None
+    pairs = (("connectivity", args.object_connectivity), ("size_edges", args.object_size_edges), ("coverage", args.object_coverage))
+    return {k: (tuple(v) if k == "size_edges" else v) for k, v in pairs if v is not None}
+
+
 def main(argv=None):
     args, tta = parse_args(argv)
     if not torch.cuda.is_available():
@@ -309,7 +365,8 @@ def main(argv=None):
         else:
             print(f"[evaluate] no checkpoint for the {what} network: running on SEEDED RANDOM weights (torch.manual_seed(0))")
     seg, fus = seg.cuda().eval(), fus.cuda().eval()
-    ev = Evaluator(seg, fus, structural=args.structural_scores, tta=tta, boundary=boundary_settings(args), calibration=calibration_settings(args))
+    ev = Evaluator(seg, fus, structural=args.structural_scores, tta=tta, boundary=boundary_settings(args), calibration=calibration_settings(args),
+                   objects=object_settings(args))
     names = _names(args.vis)
     if not names:
         raise RuntimeError(f"no .npy / .png files in {args.vis}")
@@ -337,7 +394,8 @@ def main(argv=None):
     print("[evaluate] " + "  ".join(f"{k} {res['mean'][k]:.4f}" for k in res["mean"]) + (f"  mIoU {res['mIoU']:.4f}" if "mIoU" in res else "")
           + (f"  mBIoU {res['mBIoU']:.4f}  trimap {res['trimap_mIoU']:.4f}  mBF {res['mBF']:.4f}" if "mBIoU" in res else "")
           + (f"  ECE {res['ece'][0]:.4f}  NLL {res['nll'][0]:.4f} (T {res['temperatures'][0]:g})  T* {res['best']['temperature']:.3f}"
-             if res.get("best") is not None else ""))
+             if res.get("best") is not None else "")
+          + (f"  objR {res['mObjRecall']:.4f}  objP {res['mObjPrecision']:.4f}  objF1 {res['mObjF1']:.4f}" if "mObjF1" in res else ""))
     print(f"[evaluate] wrote {path}")
     return 0
 
