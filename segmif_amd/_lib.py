@@ -381,6 +381,18 @@ OBJECT_SIGNATURES = {
     "segmif_object_stats_i32": (c_int, [POINTER(SegmifObjects)] + [c_void_p] * 8 + [c_int] * 4 + [c_void_p]),
 }
 
+# instance copy-paste: name -> (restype, argtypes); must list every symbol include/segmif_paste.h declares, and none that
+# include/segmif_hip.h does.  The same library exports them; segmif_abi_version() does not count them.
+PASTE_RECORD_WORDS, PASTE_MAX_SLOTS, PASTE_MAX_SIZE, PASTE_MAX_STEP, PASTE_MAX_FRAMES, PASTE_WORKSPACE_PER_PIXEL = 8, 8, 4096, 1 << 24, 32767, 20
+PASTE_SIGNATURES = {
+    "segmif_object_boxes_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "segmif_object_boxes_i32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_uint32, c_int64, c_int64, c_int, c_void_p,
+                                        c_int64, c_void_p, c_void_p, c_void_p]),
+    "segmif_object_pack_u8": (c_int, [c_void_p, c_void_p, c_int64, c_int64] + [c_void_p] * 4 + [c_int] * 4 + [c_void_p, c_void_p]),
+    "segmif_copy_paste_f32": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p] * 3 + [c_int64, c_int64, c_void_p, c_int, c_int]
+                                      + [c_void_p] * 7),
+}
+
 _lib = None
 
 
@@ -404,7 +416,7 @@ def load():
     import torch  # noqa: F401
     lib = ctypes.CDLL(path)
     for name, (res, args) in (list(SIGNATURES.items()) + list(DISTILL_SIGNATURES.items()) + list(CALIB_SIGNATURES.items())
-                               + list(OBJECT_SIGNATURES.items())):
+                               + list(OBJECT_SIGNATURES.items()) + list(PASTE_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: loud by design
         fn.restype = res
         fn.argtypes = args

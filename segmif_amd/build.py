@@ -1,6 +1,7 @@
 """Builds libsegmif_hip.so (gfx950) in-tree with hipcc.  No torch cpp_extension, no hipify:
 the sources are native HIP and the library has a plain C ABI (include/segmif_hip.h; the distillation objectives: include/segmif_distill.h; the
-calibration statistics: include/segmif_calib.h; the object-level statistics: include/segmif_objects.h)."""
+calibration statistics: include/segmif_calib.h; the object-level statistics: include/segmif_objects.h; instance copy-paste:
+include/segmif_paste.h)."""
 import hashlib
 import os
 import shutil
@@ -13,7 +14,7 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libsegmif_hip.so")
-SOURCES = ["igemm.hip", "conv3x3.hip", "conv3x3_split.hip", "conv3x3_planes.hip", "gemm_split.hip", "gemm_pairs.hip", "wgrad.hip", "backward.hip", "grad_guard.hip", "weight_ema.hip", "attention.hip", "attention_split.hip", "attention_bwd.hip", "rowops.hip", "tta.hip", "linattn.hip", "crosspath.hip", "metrics.hip", "fusion_stats.hip", "structural_stats.hip", "augment.hip", "label_stats.hip", "boundary_stats.hip", "class_mix.hip", "pseudo_label.hip", "strong_augment.hip", "losses.hip", "fusion_objective.hip", "seg_objective.hip", "region_objective.hip", "distill_objective.hip", "calibration_stats.hip", "objects.hip", "common.hip", "comm.hip", "mixffn.hip"]
+SOURCES = ["igemm.hip", "conv3x3.hip", "conv3x3_split.hip", "conv3x3_planes.hip", "gemm_split.hip", "gemm_pairs.hip", "wgrad.hip", "backward.hip", "grad_guard.hip", "weight_ema.hip", "attention.hip", "attention_split.hip", "attention_bwd.hip", "rowops.hip", "tta.hip", "linattn.hip", "crosspath.hip", "metrics.hip", "fusion_stats.hip", "structural_stats.hip", "augment.hip", "label_stats.hip", "boundary_stats.hip", "class_mix.hip", "pseudo_label.hip", "strong_augment.hip", "losses.hip", "fusion_objective.hip", "seg_objective.hip", "region_objective.hip", "distill_objective.hip", "calibration_stats.hip", "objects.hip", "copy_paste.hip", "common.hip", "comm.hip", "mixffn.hip"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I" + os.path.join(ROOT, "include")]
 
@@ -27,7 +28,7 @@ def _hipcc():
 
 def _digest():
     h = hashlib.sha256(" ".join(FLAGS).replace(ROOT, ".").encode())  # (not the checkout's absolute path: the same tree on the GPU box is the same build)
-    for f in SOURCES + sorted(h for h in os.listdir(CSRC) if h.endswith(".h")) + [os.path.join(ROOT, "include", "segmif_hip.h"), os.path.join(ROOT, "include", "segmif_distill.h"), os.path.join(ROOT, "include", "segmif_calib.h"), os.path.join(ROOT, "include", "segmif_objects.h")]:
+    for f in SOURCES + sorted(h for h in os.listdir(CSRC) if h.endswith(".h")) + [os.path.join(ROOT, "include", "segmif_hip.h"), os.path.join(ROOT, "include", "segmif_distill.h"), os.path.join(ROOT, "include", "segmif_calib.h"), os.path.join(ROOT, "include", "segmif_objects.h"), os.path.join(ROOT, "include", "segmif_paste.h")]:
         p = f if os.path.isabs(f) else os.path.join(CSRC, f)
         with open(p, "rb") as fh:
             h.update(fh.read())

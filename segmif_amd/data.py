@@ -241,7 +241,7 @@ class DeviceDataset:
         stack_same_size(items)
         return cls.from_arrays([it[0] for it in items], *(np.stack([it[k] for it in items]) for k in (1, 2, 3, 4)), device=device)
 
-    def augment(self, rec, tab, crop_h, crop_w, pick=True, want=None, tally=None, mix=None):
+    def augment(self, rec, tab, crop_h, crop_w, pick=True, want=None, tally=None, mix=None, paste=None):
         """rec (B, REC_WORDS), tab: host int32 arrays of pack_records -> (ir3, vis3, mask3, label, rec_dev).  One pinned,
         asynchronous upload, then the two kernels on the current stream.
 
@@ -251,9 +251,17 @@ class DeviceDataset:
 
         mix: None, or (table, n_class, min_pixels, tally): a host ClassMix table (ops.check_mix_table) that travels in the same
         upload.  The batch returned is then the MIXED one (ops.class_mix after apply; NOT the reference's loader) and the result
-        ends with two more tensors, sel (B, 8) int32 and pasted (B,) int64; tally is class_mix's (n_class, 2) int64 or None."""
+        ends with two more tensors, sel (B, 8) int32 and pasted (B,) int64; tally is class_mix's (n_class, 2) int64 or None.
+
+        paste: None, or (table, bank, n_class, tally): a host copy-paste table (ops.check_paste_table) that travels in the same
+        upload, and the ObjectBank its slots index.  The batch returned then has the objects pasted in (ops.copy_paste, after apply
+        and after class_mix when both are on; NOT the reference's loader) and the result ends with one more tensor, the pasted
+        pixels (B,) int64; tally is copy_paste's (n_class, 2) int64 or None."""
         from . import ops
         B = rec.shape[0]
+        if paste is not None:
+            paste_table, paste_bank, paste_classes, paste_tally = paste
+            paste_table = ops.check_paste_table(paste_table, B)
         if mix is not None:
             mix_table, mix_classes, mix_min_pixels, mix_tally = mix
             mix_table = ops.check_mix_table(mix_table, B, mix_classes)
@@ -265,13 +273,18 @@ class DeviceDataset:
         mix_at = words
         if mix is not None:
             words += mix_table.size
+        paste_at = words
+        if paste is not None:
+            words += paste_table.size
         blob = self._staging(words)
         blob[:rec.size].copy_(torch.from_numpy(rec.reshape(-1)))
         blob[rec.size:rec.size + tab.size].copy_(torch.from_numpy(tab))
         if want is not None:
             blob[rec.size + tab.size:mix_at].copy_(torch.from_numpy(want.reshape(-1)))
         if mix is not None:
-            blob[mix_at:words].copy_(torch.from_numpy(mix_table.reshape(-1)))
+            blob[mix_at:paste_at].copy_(torch.from_numpy(mix_table.reshape(-1)))
+        if paste is not None:
+            blob[paste_at:words].copy_(torch.from_numpy(paste_table.reshape(-1)))
         dev = torch.empty(words, dtype=torch.int32, device=self.ir.device)
         dev.copy_(blob[:words], non_blocking=True)
         self._staged[self._turn][1].record()
@@ -282,10 +295,13 @@ class DeviceDataset:
         elif pick:
             ops.augment_pick(self.label, rec_d, tab_d, crop_h, crop_w)
         out = ops.augment_apply(self.ir, self.vis, self.mask, self.label, rec_d, tab_d, crop_h, crop_w)
-        if mix is None:
-            return out + extra
-        mixed = ops.class_mix(*out, dev[mix_at:].view(B, 2 + mix_classes), mix_classes, mix_min_pixels, mix_tally)
-        return mixed[:4] + extra + mixed[4:]
+        if mix is not None:
+            mixed = ops.class_mix(*out, dev[mix_at:paste_at].view(B, 2 + mix_classes), mix_classes, mix_min_pixels, mix_tally)
+            out, extra = mixed[:4], extra + mixed[4:]
+        if paste is not None:
+            done = ops.copy_paste(*out, paste_bank, dev[paste_at:words].view(paste_table.shape), paste_classes, paste_tally)
+            out, extra = done[:4], extra + done[4:]
+        return out + extra
 
     def label_stats(self, n_class=9, ignore_index=255):
         """-> LabelStats of the resident labels: one launch (csrc/label_stats.hip) and one readback, then cached.  Raises
@@ -523,6 +539,195 @@ class StrongAugment:
         return table
 
 
+# ---------------------------------------------------------------------------------------------------------------- copy-paste
+
+class ObjectBank:
+    """The objects of a resident set for instance copy-paste (Ghiasi et al. 2021; the rule: include/segmif_paste.h); NOT the
+    reference's loader.  An object is one connected component of one class in one frame.  The bank is
+      records_host  (M, 8) int32 rows {frame, root, cls, area, x0, y0, bw, bh}, sorted by (frame, root); records: the same on the device
+      offsets_host  (M + 1,) int64: the objects' first pixels in the store; offsets: the same on the device
+      patches       (offsets[M], 8) uint8 on the device: per pixel of an object's box {ir, v0, v1, v2, mask, alpha, 0, 0}
+      by_class      {class: indices of its objects, ascending}
+    and depends on the data alone: the kernels' append order is sorted away."""
+
+    def __init__(self, records, offsets, patches, n_class, shape, device_records=None, device_offsets=None):
+        self.records_host = np.ascontiguousarray(records, dtype=np.int32)
+        self.offsets_host = np.ascontiguousarray(offsets, dtype=np.int64)
+        M = len(self.records_host)
+        if self.records_host.ndim != 2 or self.records_host.shape[1] != 8 or M < 1 or self.offsets_host.shape != (M + 1,):
+            raise ValueError(f"ObjectBank: records {self.records_host.shape} and offsets {self.offsets_host.shape} do not describe a bank")
+        self.patches, self.n_class, self.shape = patches, int(n_class), tuple(shape)
+        self.records = device_records if device_records is not None else torch.from_numpy(self.records_host).to(patches.device)
+        self.offsets = device_offsets if device_offsets is not None else torch.from_numpy(self.offsets_host).to(patches.device)
+        cls = self.records_host[:, 2]
+        self.by_class = {int(c): np.flatnonzero(cls == c) for c in np.unique(cls)}
+
+    def __len__(self):
+        return len(self.records_host)
+
+    @property
+    def nbytes(self):
+        return int(self.patches.numel() + self.records.numel() * 4 + self.offsets.numel() * 8)
+
+    def table(self):
+        """-> printable rows: a header, then class, objects, their pixels (area) and their boxes' pixels (what the store holds)"""
+        rows = [f"{'class':>5} {'objects':>8} {'pixels':>12} {'box pixels':>12}  of {len(self)} objects, {self.nbytes} bytes on the device"]
+        box = self.records_host[:, 6].astype(np.int64) * self.records_host[:, 7]
+        for c, idx in sorted(self.by_class.items()):
+            rows.append(f"{c:>5} {len(idx):>8} {int(self.records_host[idx, 3].sum()):>12} {int(box[idx].sum()):>12}")
+        return rows
+
+    @classmethod
+    def build(cls, dataset, n_class=9, classes=None, connectivity=8, min_area=64, max_box=None, max_per_class=4096, max_bytes=1 << 30,
+              frames=None, max_workspace_bytes=256 << 20):
+        """Walks the resident labels of `frames` (None: all; else frame indices) in chunks bounded by the labeller's workspace,
+        labels them (utils.objects.connected_components), appends the boxes (ops.object_boxes) and, after ONE readback and the
+        sort by (frame, root), fills the patch store (ops.object_pack); the root maps are freed afterwards.
+        classes: None means 1..n_class-1 (class 0 is the background and is never banked by default).  min_area: least pixels of
+        an object.  max_box: most pixels of its box, None means H * W // 4.  A class with more than max_per_class objects keeps
+        every ceil(n / max_per_class)-th of the sorted order.  ValueError: an empty bank, or a store over max_bytes.
+        Peak device memory beside the data set: the chunking bounds the labeller's and the boxes' WORKSPACE only (at most
+        max_workspace_bytes, and 20 bytes per pixel of a chunk); the root maps of ALL the frames, 4 bytes per pixel, live from the
+        labelling to the pack, since the pack needs them after the sort (1.9 GB for 1 569 frames of 480 x 640), one chunk's int32
+        copy of its labels at a time beside them, then the record list and the store itself.
+        The defaults are this project's choices; Ghiasi et al. bank every annotated instance."""
+        from . import _lib, ops
+        from .utils.objects import connected_components
+        H, W = dataset.shape
+        K = int(n_class)
+        if not 1 <= K <= 32:
+            raise ValueError(f"ObjectBank: n_class {n_class}, the kernels take 1..32 (SEGMIF_EINVAL)")
+        wanted = sorted(set(int(c) for c in (range(1, K) if classes is None else classes)))
+        if not wanted or wanted[0] < 0 or wanted[-1] >= K:
+            raise ValueError(f"ObjectBank: classes {list(wanted)} must name at least one class in 0..{K - 1}")
+        max_box = H * W // 4 if max_box is None else int(max_box)
+        if min_area < 1 or max_box < 1 or max_per_class < 1:
+            raise ValueError(f"ObjectBank: min_area {min_area}, max_box {max_box} and max_per_class {max_per_class} must be >= 1")
+        idx = sorted(set(int(f) for f in (range(len(dataset)) if frames is None else frames)))
+        if not idx or idx[0] < 0 or idx[-1] >= len(dataset):
+            raise ValueError(f"ObjectBank: frames must name frames of the data set (0..{len(dataset) - 1})")
+        mask_bits = sum(1 << c for c in wanted)
+        per_frame = int(_lib.load().segmif_object_workspace_bytes(1, H, W))
+        step = max(1, min(int(max_workspace_bytes) // max(per_frame, 1), _lib.PASTE_MAX_FRAMES))
+        chunks, start = [], 0  # (first frame, frames): consecutive frames only, so that frame0 + index names the frame
+        for i in range(1, len(idx) + 1):
+            if i == len(idx) or idx[i] != idx[i - 1] + 1 or i - start == step:
+                chunks.append((idx[start], i - start))
+                start = i
+        dev = dataset.label.device
+        roots = [connected_components(dataset.label[f0:f0 + n].to(torch.int32), K, connectivity)[0] for f0, n in chunks]
+        capacity, count = 1 << 16, None
+        while count is None or count > capacity:
+            capacity = capacity if count is None else count
+            records, counter, work = torch.empty((capacity, 8), dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev), None
+            for (f0, n), root in zip(chunks, roots):
+                work = ops.object_boxes(root, dataset.label[f0:f0 + n], K, mask_bits, min_area, max_box, records, counter, frame0=f0,
+                                        workspace=work)
+            host = torch.cat([counter, records.reshape(-1)]).cpu().numpy()  # the one readback (repeated only after an overflow)
+            count = int(host[0])
+        rec = host[1:1 + 8 * count].reshape(count, 8)
+        rec = rec[np.lexsort((rec[:, 1], rec[:, 0]))]
+        keep = np.zeros(count, dtype=bool)
+        for c in np.unique(rec[:, 2]):
+            of_c = np.flatnonzero(rec[:, 2] == c)
+            keep[of_c[::-(-len(of_c) // int(max_per_class))]] = True  # every ceil(n / max_per_class)-th
+        rec = np.ascontiguousarray(rec[keep])
+        if not len(rec):
+            raise ValueError(f"ObjectBank: no object of classes {wanted} with at least {min_area} pixels and a box of at most {max_box} "
+                             f"in {len(idx)} frames: nothing to paste (min_area, max_box, classes)")
+        offsets = np.concatenate(([0], np.cumsum(rec[:, 6].astype(np.int64) * rec[:, 7]))).astype(np.int64)
+        nbytes = int(offsets[-1]) * 8
+        if nbytes > max_bytes:
+            raise ValueError(f"ObjectBank: the patch store of {len(rec)} objects holds {int(offsets[-1])} pixels = {nbytes} bytes, over "
+                             f"max_bytes {max_bytes}; raise min_area ({min_area}), lower max_box ({max_box}) or max_per_class "
+                             f"({max_per_class}), name fewer classes or frames, or raise max_bytes")
+        rec_d, off_d = torch.from_numpy(rec).to(dev), torch.from_numpy(offsets).to(dev)
+        patches = torch.empty((int(offsets[-1]), 8), dtype=torch.uint8, device=dev)
+        for (f0, n), root in zip(chunks, roots):
+            m0, m1 = (int(v) for v in np.searchsorted(rec[:, 0], [f0, f0 + n]))
+            if m1 > m0:  # (sorted by frame: a chunk's objects are consecutive)
+                ops.object_pack(rec_d[m0:m1], off_d[m0:m1 + 1], patches, root, dataset.ir[f0:f0 + n], dataset.vis[f0:f0 + n],
+                                dataset.mask[f0:f0 + n], frame0=f0)
+        return cls(rec, offsets, patches, K, (H, W), rec_d, off_d)
+
+
+class CopyPaste:
+    """The policy of instance copy-paste (Ghiasi et al. 2021, "Simple Copy-Paste") for AugmentedBatches(paste=); NOT the reference's
+    loader, which pastes nothing.  With probability `prob` a sample receives 1..max_objects objects of the bank, each of a drawn
+    class (uniform over the banked classes, or with stats= a LabelStats the rare-class sampler's P(c) ~ exp((1 - f_c) /
+    temperature)), uniform among that class's objects, scaled by a log-uniform factor in `scale` (nearest neighbour, the object
+    only), mirrored with probability 1 / 2 when flip, its centre uniform over the crop.  What differs from Ghiasi et al.: no
+    large-scale jitter of the receiver beyond the loader's own, no blending of the edge, objects from the whole resident set and
+    not from one other image.  Every default (prob 0.5, max_objects 3, scale (0.5, 2.0), temperature 0.01) is this project's choice.
+
+    draw(B, h, w) builds the table from a private random.Random seeded from (seed, rank); neither the global generators nor the
+    loader's crop generators are touched.  Per sample, in order, it draws the coin, the number of objects and per slot a class, an
+    object, a scale, a flip coin and two positions - all 2 + 6 * max_objects values always, each ONE call of random(), so the
+    stream does not depend on the outcomes."""
+
+    DRAWS_PER_SLOT = 6
+
+    def __init__(self, bank, prob=0.5, max_objects=3, scale=(0.5, 2.0), flip=True, stats=None, temperature=0.01, seed=0, rank=0):
+        from . import ops
+        lo, hi = (float(v) for v in scale)
+        if not 0.0 < prob <= 1.0 or not 1 <= max_objects <= ops.PASTE_MAX_SLOTS or not 0.0 < lo <= hi or not temperature > 0:
+            raise ValueError(f"CopyPaste: prob {prob} in (0, 1], max_objects {max_objects} in 1..{ops.PASTE_MAX_SLOTS}, 0 < scale {lo} <= {hi} "
+                             f"and temperature {temperature} > 0 are required")
+        self.bank, self.prob, self.max_objects, self.scale, self.flip = bank, float(prob), int(max_objects), (lo, hi), bool(flip)
+        self.temperature, self.seed, self.rank = float(temperature), seed, rank
+        self.classes = sorted(bank.by_class)
+        if stats is None:
+            p = np.full(len(self.classes), 1.0 / len(self.classes))
+        else:
+            if max(self.classes) >= stats.n_class:
+                raise ValueError(f"CopyPaste: the bank holds class {max(self.classes)}, the statistics {stats.n_class} classes")
+            z = (1.0 - stats.freq[self.classes].astype(np.float64)) / self.temperature
+            e = np.exp(z - z.max())
+            p = e / e.sum()
+        self.class_prob = dict(zip(self.classes, (float(v) for v in p)))
+        self._cum = np.cumsum(p)
+        self._py = random.Random(f"CopyPaste {seed} {rank}")
+
+    def draws_per_sample(self):
+        """calls of random() per sample, whatever the coins show"""
+        return 2 + self.DRAWS_PER_SLOT * self.max_objects
+
+    @staticmethod
+    def _pick(r, n):
+        """r in [0, 1) -> an index in 0..n-1"""
+        return min(int(r * n), n - 1)
+
+    def draw(self, B, h, w):
+        """-> (B, max_objects, 8) int32 slots (obj, dx, dy, ow, oh, sx, sy, flip); obj = -1 marks an empty slot"""
+        from . import ops
+        if B < 1 or h < 1 or w < 1:
+            raise ValueError(f"CopyPaste: B {B}, h {h} and w {w} must be >= 1")
+        table = np.zeros((B, self.max_objects, 8), dtype=np.int32)
+        table[:, :, 0] = -1
+        rnd, rec = self._py.random, self.bank.records_host
+        log_lo, log_hi = np.log(self.scale[0]), np.log(self.scale[1])
+        for b in range(B):
+            pastes = rnd() < self.prob
+            n = 1 + self._pick(rnd(), self.max_objects)
+            for k in range(self.max_objects):
+                r_cls, r_obj, r_s, r_flip, r_x, r_y = (rnd() for _ in range(self.DRAWS_PER_SLOT))
+                if not pastes or k >= n:
+                    continue
+                c = self.classes[min(int(np.searchsorted(self._cum, r_cls, side="right")), len(self.classes) - 1)]
+                of_c = self.bank.by_class[c]
+                obj = int(of_c[self._pick(r_obj, len(of_c))])
+                s = float(np.exp(log_lo + r_s * (log_hi - log_lo)))
+                bw, bh = int(rec[obj, 6]), int(rec[obj, 7])
+                ow = min(max(int(round(bw * s)), 1), ops.PASTE_MAX_SIZE)
+                oh = min(max(int(round(bh * s)), 1), ops.PASTE_MAX_SIZE)
+                sx = min(max((bw << 16) // ow, 1), ops.PASTE_MAX_STEP)
+                sy = min(max((bh << 16) // oh, 1), ops.PASTE_MAX_STEP)
+                dx = -(ow // 2) + self._pick(r_x, w - ow + 2 * (ow // 2) + 1)
+                dy = -(oh // 2) + self._pick(r_y, h - oh + 2 * (oh // 2) + 1)
+                table[b, k] = (obj, dx, dy, ow, oh, sx, sy, int(self.flip and r_flip < 0.5))
+        return table
+
+
 # ------------------------------------------------------------------------------------------------------------------ iterator
 
 class AugmentedBatches:
@@ -549,10 +754,15 @@ class AugmentedBatches:
     mix: None, or a ClassMix.  Every batch is then mixed after augment_apply (ops.class_mix: classes of one crop pasted into
     another of the same batch); the crops underneath are the ones the same seed gives without it, since the policy draws from
     a generator of its own.  last_params[i]["mix"] is (donor, force, keys), mix_tally() the device's count of samples and pixels
+    pasted per class.  NOT the reference's loader.  With None nothing changes: the random stream, the launches, the batches.
+
+    paste: None, or a CopyPaste.  Every batch then has banked objects pasted in (ops.copy_paste) after augment_apply, and after
+    class_mix when mix= is given too; the crops underneath are the ones the same seed gives without it, since the policy draws from
+    a generator of its own.  last_params[i]["paste"] is the sample's slots, paste_tally() the device's count of slots and pixels
     pasted per class.  NOT the reference's loader.  With None nothing changes: the random stream, the launches, the batches."""
 
     def __init__(self, dataset, batch, crop_size=512, rescale_range=(0.5, 2.0), fliplr=True, photometric=PHOTOMETRIC, seed=0,
-                 rank=0, world=1, aug=True, sampler=None, mix=None):
+                 rank=0, world=1, aug=True, sampler=None, mix=None, paste=None):
         unknown = [p for p in photometric if p not in PHOTOMETRIC]
         if unknown:
             raise ValueError(f"photometric: {unknown} not available; this loader applies {PHOTOMETRIC} only (saturation and hue go "
@@ -591,6 +801,13 @@ class AugmentedBatches:
             if mix.rank != rank:
                 raise ValueError(f"mix: the ClassMix was seeded for rank {mix.rank}, this iterator is rank {rank}")
             self._mix_tally = torch.zeros((mix.n_class, 2), dtype=torch.int64, device=dataset.label.device)
+        self.paste = paste
+        if paste is not None:
+            if not aug:
+                raise ValueError("paste: CopyPaste works on augmented crops, aug=False has none")
+            if paste.rank != rank:
+                raise ValueError(f"paste: the CopyPaste was seeded for rank {paste.rank}, this iterator is rank {rank}")
+            self._paste_tally = torch.zeros((paste.bank.n_class, 2), dtype=torch.int64, device=dataset.label.device)
 
     def __len__(self):
         """batches per pass (drop_last)"""
@@ -620,6 +837,22 @@ class AugmentedBatches:
             raise RuntimeError("mix_tally: this iterator has no ClassMix")
         return self._mix_tally.cpu().numpy()
 
+    def paste_tally(self):
+        """-> (n_class, 2) int64 numpy array: per class the non-empty slots drawn so far and the pixels pasted.  One readback of
+        the device tally."""
+        if self.paste is None:
+            raise RuntimeError("paste_tally: this iterator has no CopyPaste")
+        return self._paste_tally.cpu().numpy()
+
+    def _paste_arg(self, params):
+        """The augment(paste=) tuple of one batch, drawn from the policy's own generator; notes it in the samples' params."""
+        if self.paste is None:
+            return None
+        table = self.paste.draw(len(params), self.crop, self.crop)
+        for p, slots in zip(params, table):
+            p["paste"] = tuple(tuple(int(v) for v in slot) for slot in slots)
+        return table, self.paste.bank, self.paste.bank.n_class, self._paste_tally
+
     def _mix_arg(self, params, wanted=None):
         """The augment(mix=) tuple of one batch, drawn from the policy's own generator; notes it in the samples' params."""
         if self.mix is None:
@@ -642,7 +875,7 @@ class AugmentedBatches:
             p["want"] = (int(want[b, 0]), int(want[b, 1]))
         rec, tab = pack_records(idx, params, h, w)
         out = self.dataset.augment(rec, tab, self.crop, self.crop, pick=True, want=want, tally=self._tally,
-                                   mix=self._mix_arg(params, [c for _, c in drawn]))[:4]
+                                   mix=self._mix_arg(params, [c for _, c in drawn]), paste=self._paste_arg(params))[:4]
         return (tuple(self.dataset.names[i] for i in idx),) + tuple(out)
 
     def __next__(self):
@@ -659,4 +892,4 @@ class AugmentedBatches:
         h, w = self.dataset.shape
         rec, tab = pack_records(idx, params, h, w)
         ch, cw = (self.crop, self.crop) if self.aug else (h, w)
-        return self.dataset.augment(rec, tab, ch, cw, pick=self.aug, mix=self._mix_arg(params))[:4]
+        return self.dataset.augment(rec, tab, ch, cw, pick=self.aug, mix=self._mix_arg(params), paste=self._paste_arg(params))[:4]

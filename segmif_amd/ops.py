@@ -1746,3 +1746,126 @@ def strong_augment(x, table, return_mean=False):
     _lib.check(lib.segmif_strong_augment_f32(x.data_ptr(), y.data_ptr(), table.data_ptr(), partial.data_ptr(), mean.data_ptr(), B, h, w,
                                              _stream()), "segmif_strong_augment_f32")
     return (y, mean) if return_mean else y
+
+
+PASTE_WORDS, PASTE_MAX_SLOTS, PASTE_MAX_SIZE, PASTE_MAX_STEP = (_lib.PASTE_RECORD_WORDS, _lib.PASTE_MAX_SLOTS, _lib.PASTE_MAX_SIZE,
+                                                                  _lib.PASTE_MAX_STEP)
+
+
+def object_boxes(root, label, n_class, class_mask, min_area, max_box, records, counter, frame0=0, workspace=None):
+    """segmif_object_boxes_i32 (the rule: include/segmif_paste.h): appends one record {frame0 + frame, root, cls, area, x0, y0, bw, bh}
+    per connected component of `root` (n, H, W) int32 (utils.objects.connected_components' roots of `label` (n, H, W) uint8) whose
+    class is below n_class and in the 32-bit class_mask, whose area is >= min_area and whose tight box holds <= max_box pixels.
+    records (capacity, 8) int32 and counter (1,) int32 are device tensors: the caller zeroes the counter, which rises past the
+    capacity when the list is too short (those records are not written).  The append order is arrival order: sort by (frame, root).
+    Three launches, no synchronisation.  -> the workspace used (pass it back to spare the allocation)."""
+    _req_u8(root, "root", dtype=torch.int32)
+    if root.dim() != 3 or root.numel() < 1:
+        raise RuntimeError(f"object_boxes: root must be a non-empty (n, H, W) int32 tensor, got {tuple(root.shape)}")
+    n, H, W = (int(v) for v in root.shape)
+    _req_u8(label, "label", (n, H, W))
+    _req_u8(records, "records", dtype=torch.int32)
+    _req_u8(counter, "counter", (1,), dtype=torch.int32)
+    if records.dim() != 2 or records.shape[1] != PASTE_WORDS:
+        raise RuntimeError(f"object_boxes: records must be (capacity, {PASTE_WORDS}) int32, got {tuple(records.shape)}")
+    if not 1 <= n_class <= 32 or min_area < 1 or max_box < 1 or frame0 < 0 or not 0 <= class_mask < 2 ** 32:
+        raise ValueError(f"object_boxes: n_class {n_class} in 1..32, min_area {min_area} >= 1, max_box {max_box} >= 1, frame0 {frame0} >= 0 "
+                         f"and a 32-bit class_mask are required (SEGMIF_EINVAL)")
+    lib = _lib.load()
+    need = int(lib.segmif_object_boxes_workspace_bytes(n, H, W))
+    if need <= 0:
+        raise ValueError(f"object_boxes: at most {_lib.PASTE_MAX_FRAMES} frames of fewer than 2^31 pixels, got {tuple(root.shape)} (SEGMIF_EINVAL)")
+    if workspace is None or workspace.numel() * 4 < need:
+        workspace = torch.empty(need // 4, device=root.device, dtype=torch.int32)
+    _lib.check(lib.segmif_object_boxes_i32(root.data_ptr(), label.data_ptr(), n, H, W, int(n_class), int(class_mask), int(min_area),
+                                           int(max_box), int(frame0), records.data_ptr() if records.shape[0] else None,
+                                           records.shape[0], counter.data_ptr(), workspace.data_ptr(), _stream()),
+               "segmif_object_boxes_i32")
+    return workspace
+
+
+def object_pack(records, offsets, patches, root, ir, vis, mask, frame0=0):
+    """segmif_object_pack_u8: fills the patch store of the objects among `records` (M, 8) int32 (sorted, on the device) that lie in
+    frames frame0 .. frame0 + n - 1, whose root maps `root` (n, H, W) int32 and uint8 frames ir, mask (n, H, W), vis (n, H, W, 3) are
+    given.  offsets (M + 1,) int64: the objects' first pixels in patches (store_pixels, 8) uint8.  A pixel of an object's box is
+    {ir, v0, v1, v2, mask, 1, 0, 0} where the frame's root is the object's, else eight zero bytes.  One launch."""
+    _req_u8(records, "records", dtype=torch.int32)
+    if records.dim() != 2 or records.shape[1] != PASTE_WORDS or records.shape[0] < 1:
+        raise RuntimeError(f"object_pack: records must be (M, {PASTE_WORDS}) int32 with M >= 1, got {tuple(records.shape)}")
+    M = records.shape[0]
+    _req_u8(offsets, "offsets", (M + 1,), dtype=torch.int64)
+    _req_u8(patches, "patches")
+    if patches.dim() != 2 or patches.shape[1] != PASTE_WORDS:
+        raise RuntimeError(f"object_pack: patches must be (pixels, {PASTE_WORDS}) uint8, got {tuple(patches.shape)}")
+    _req_u8(root, "root", dtype=torch.int32)
+    if root.dim() != 3 or root.numel() < 1:
+        raise RuntimeError(f"object_pack: root must be a non-empty (n, H, W) int32 tensor, got {tuple(root.shape)}")
+    n, H, W = (int(v) for v in root.shape)
+    _req_u8(ir, "ir", (n, H, W)), _req_u8(mask, "mask", (n, H, W)), _req_u8(vis, "vis", (n, H, W, 3))
+    _lib.check(_lib.load().segmif_object_pack_u8(records.data_ptr(), offsets.data_ptr(), M, patches.shape[0], root.data_ptr(),
+                                                 ir.data_ptr(), vis.data_ptr(), mask.data_ptr(), int(frame0), n, H, W, patches.data_ptr(),
+                                                 _stream()), "segmif_object_pack_u8")
+    return patches
+
+
+def check_paste_table(table, B, P=None):
+    """Host-side check of a copy-paste table (it lives on the device when the kernel reads it): (B, P, 8) integers that fit int32,
+    P in 0..8 (and equal to P when given) -> (B, P, 8) int32 numpy array.  The VALUES are not checked: a slot outside the kernel's
+    domain is an empty slot by the rule."""
+    import numpy as np
+    t = np.asarray(table)
+    if t.ndim != 3 or t.shape[0] != B or B < 1 or t.shape[2] != PASTE_WORDS or t.dtype.kind not in "iu":
+        raise ValueError(f"copy_paste: the table must be ({B}, P, {PASTE_WORDS}) integers (obj, dx, dy, ow, oh, sx, sy, flip), got {t.dtype} {t.shape}")
+    if t.shape[1] > PASTE_MAX_SLOTS or (P is not None and t.shape[1] != P):
+        raise ValueError(f"copy_paste: P = {t.shape[1]} slots per sample, the kernel takes 0..{PASTE_MAX_SLOTS}" + (f" and {P} were announced" if P is not None else "")
+                         + " (SEGMIF_EINVAL)")
+    if t.size and ((t > 2 ** 31 - 1).any() or (t < -2 ** 31).any()):
+        raise ValueError("copy_paste: a table value does not fit int32")
+    return np.ascontiguousarray(t, dtype=np.int32)
+
+
+def copy_paste(ir3, vis3, mask3, label, bank, table, n_class=9, tally=None):
+    """Instance copy-paste on an augmented batch (the rule: include/segmif_paste.h, segmif_copy_paste_f32): every pixel takes the values
+    of the LAST slot of its sample's table whose rectangle covers it and whose patch pixel belongs to the object (alpha = 1) - ir and
+    mask in all three channels, vis per channel, each byte / 255 as augment_apply forms it WITHOUT photometric distortion, the label
+    the object's class - and is the receiver's, bit for bit, where no slot does.  ir3, vis3, mask3 (B, 3, h, w) fp32, label (B, h, w)
+    int64, w % 4 == 0.  bank: an object with records (M, 8) int32, offsets (M + 1,) int64 and patches (pixels, 8) uint8 device tensors
+    (data.ObjectBank).  table: (B, P, 8) slots (obj, dx, dy, ow, oh, sx, sy, flip), either a host array / list, which is checked
+    and uploaded here, or an int32 device tensor.  tally: None or an (n_class, 2) int64 device tensor that accumulates (non-empty
+    slots, pixels pasted) per class.  One launch on the current stream, no synchronisation.  -> (ir3', vis3', mask3', label',
+    pasted (B,) int64), new tensors.  NOT the reference's loader."""
+    _req_u8(label, "label", dtype=torch.int64)
+    if label.dim() != 3 or label.numel() < 1:
+        raise RuntimeError(f"copy_paste: label must be a non-empty (B, h, w) int64 tensor, got {tuple(label.shape)}")
+    B, h, w = label.shape
+    if w % 4:
+        raise RuntimeError(f"copy_paste: the width must be a multiple of 4 (16-byte accesses), got {w}")
+    if not 1 <= n_class <= 255:
+        raise ValueError(f"copy_paste: n_class {n_class} outside 1..255 (SEGMIF_EINVAL)")
+    for t, name in ((ir3, "ir3"), (vis3, "vis3"), (mask3, "mask3")):
+        _req_u8(t, name, (B, 3, h, w), dtype=torch.float32)
+    if not isinstance(table, torch.Tensor) or not table.is_cuda:
+        table = torch.from_numpy(check_paste_table(table.numpy() if isinstance(table, torch.Tensor) else table, B)).to(label.device)
+    _req_u8(table, "table", dtype=torch.int32)
+    if table.dim() != 3 or table.shape[0] != B or table.shape[2] != PASTE_WORDS or table.shape[1] > PASTE_MAX_SLOTS:
+        raise RuntimeError(f"copy_paste: table must be ({B}, P <= {PASTE_MAX_SLOTS}, {PASTE_WORDS}) int32, got {tuple(table.shape)}")
+    records, offsets, patches = bank.records, bank.offsets, bank.patches
+    _req_u8(records, "bank.records", dtype=torch.int32)
+    M = records.shape[0]
+    if records.dim() != 2 or records.shape[1] != PASTE_WORDS or M < 1:
+        raise RuntimeError(f"copy_paste: bank.records must be (M, {PASTE_WORDS}) int32 with M >= 1, got {tuple(records.shape)}")
+    _req_u8(offsets, "bank.offsets", (M + 1,), dtype=torch.int64)
+    _req_u8(patches, "bank.patches")
+    if patches.dim() != 2 or patches.shape[1] != PASTE_WORDS or patches.shape[0] < 1:
+        raise RuntimeError(f"copy_paste: bank.patches must be (pixels >= 1, {PASTE_WORDS}) uint8, got {tuple(patches.shape)}")
+    if tally is not None:
+        _req_u8(tally, "tally", (n_class, 2), dtype=torch.int64)
+    P = table.shape[1]
+    out = tuple(torch.empty_like(t) for t in (ir3, vis3, mask3, label))
+    pasted = torch.empty(B, device=label.device, dtype=torch.int64)
+    _lib.check(_lib.load().segmif_copy_paste_f32(ir3.data_ptr(), vis3.data_ptr(), mask3.data_ptr(), label.data_ptr(), B, h, w,
+                                                 records.data_ptr(), offsets.data_ptr(), patches.data_ptr(), M, patches.shape[0],
+                                                 table.data_ptr() if P else None, P, n_class, *(t.data_ptr() for t in out),
+                                                 pasted.data_ptr(), tally.data_ptr() if tally is not None else None, _stream()),
+               "segmif_copy_paste_f32")
+    return out + (pasted,)

@@ -24,6 +24,7 @@ is one block in the parser, one row in each table, one entry in the plan and one
 --seg-region adds a region term to it (make_seg_region): Lovasz-Softmax or soft Dice on csrc/region_objective.hip.
 --ema-decay keeps an exponential moving average of the weights in the optimizer step (csrc/weight_ema.hip) and validates and
 writes the AVERAGED weights.  --class-mix pastes classes between the crops of a batch (ClassMix, csrc/class_mix.hip).
+--copy-paste banks the connected components of the training labels and pastes them into the crops (csrc/copy_paste.hip).
 --self-training adds an unlabelled split to the segmentation phase (segmif_amd.selftrain: the weight average as the teacher,
 pseudo-labels from csrc/pseudo_label.hip, a confidence-weighted CE on csrc/seg_objective.hip's weighted entries).
 --distill-from adds a frozen teacher to the segmentation phase (segmif_amd.distill: per-pixel KD or channel-wise distillation
@@ -432,6 +433,16 @@ def make_plan(args):
         p.mix_kw = dict(prob=args.class_mix_prob, classes=args.class_mix_classes, min_pixels=args.class_mix_min_pixels, n_class=N_CLASS)
         say.append(f"[train] --class-mix ({listed(p.mix_kw)}; phases {', '.join(p.mix_phases)}): this project's addition, NOT the reference's "
                    "loader (its train.py mixes nothing): classes of one crop of a batch are pasted into another, images and label alike")
+    if args.copy_paste:  # (the plan gains these attributes only when copy-paste is on)
+        p.paste_phases = PHASES[args.copy_paste_phases]
+        p.paste_bank_kw = dict(n_class=N_CLASS, classes=args.copy_paste_classes, min_area=args.copy_paste_min_area)
+        p.paste_kw = dict(prob=args.copy_paste_prob, max_objects=args.copy_paste_max_objects, scale=tuple(args.copy_paste_scale),
+                          temperature=args.copy_paste_temperature)
+        say.append(f"[train] --copy-paste ({listed(p.paste_kw)}; bank: {listed(p.paste_bank_kw)}; phases {', '.join(p.paste_phases)}): this "
+                   "project's addition, NOT the reference's loader (its train.py pastes nothing).  Instance copy-paste (Ghiasi et al. "
+                   "2021): connected components of the training labels are banked on the device and pasted, scaled by nearest "
+                   "neighbour and mirrored, into the crops - infrared, visible, mask and label alike; no blending of the edge, the "
+                   "defaults are this project's choices.  Nothing here says what it does to mIoU: that takes a run on a data set")
     if args.self_training:
         p.st_kw = dict(tau=args.st_threshold, below=args.st_below, unsup_weight=args.st_weight)
         if args.st_temperature != 1.0:  # (the keyword exists only when the flag changes something)
@@ -531,7 +542,7 @@ def _build_run(args, plan):
         args=args, plan=plan, seg=seg, fus=fus, train_set=train_set, val_set=val_set, unl_set=unl_set, stats=stats, seg_crit=seg_crit,
         crit=torch.nn.CrossEntropyLoss(ignore_index=255), fusion_loss=make_fusion_loss(args.fusion_loss) if args.fusion_loss else None,
         seg_initial=seg_initial, seg_path=os.path.join(args.out, SEG_CKPT), fus_path=os.path.join(args.out, FUSION_CKPT),
-        best=None, wrote_seg=False, opt=None, seg_state=seg_initial, fused_set=None, fused_unl=None, teacher=teacher)
+        best=None, wrote_seg=False, opt=None, seg_state=seg_initial, fused_set=None, fused_unl=None, teacher=teacher, paste_banks={})
 
 
 def _averaged(on, optimizer, net):
@@ -547,7 +558,32 @@ def _loader(run, dataset, phase, seed, **kw):
     from .data import AugmentedBatches, ClassMix, RareClassSampler
     sampler = RareClassSampler(run.stats, range(len(dataset)), seed=seed, **run.plan.rcs_kw) if phase in run.plan.rcs_phases else None
     mix = ClassMix(seed=seed, **run.plan.mix_kw) if phase in run.plan.mix_phases else None
-    return AugmentedBatches(dataset, seed=seed, sampler=sampler, mix=mix, **run.plan.loader_kw, **kw)
+    paste = _copy_paste(run, dataset, phase, seed) if phase in getattr(run.plan, "paste_phases", ()) else None
+    return AugmentedBatches(dataset, seed=seed, sampler=sampler, mix=mix, paste=paste, **run.plan.loader_kw, **kw)
+
+
+def _copy_paste(run, dataset, phase, seed):
+    """The CopyPaste of `phase` over `dataset`: the bank is built once per set a phase trains on (the training split for the fusion
+    phase, each round's fused set for the segmentation phase: its visible frames differ from round to round, its records do not) and
+    its table printed; the class draw follows --copy-paste-temperature.  A bank that cannot be built ends the run with the flags that
+    change it."""
+    from .data import CopyPaste, ObjectBank
+    if run.paste_banks.get(phase, (None, None))[0] is not dataset:
+        try:
+            bank = ObjectBank.build(dataset, **run.plan.paste_bank_kw)
+        except ValueError as e:
+            raise SystemExit(f"[train] --copy-paste: {e}\n[train] --copy-paste: on the command line the bank follows --copy-paste-min-area "
+                             f"(now {run.plan.paste_bank_kw['min_area']}: a larger value banks fewer and larger objects, a smaller one more) and "
+                             "--copy-paste-classes (fewer classes, a smaller bank); the other limits are arguments of data.ObjectBank.build")
+        run.paste_banks[phase] = (dataset, bank)
+        print(f"[train] --copy-paste: the object bank of the {phase} phase's frames:")
+        for row in bank.table():
+            print("[train]   " + row)
+    kw = dict(run.plan.paste_kw)
+    temperature = kw.pop("temperature")
+    if temperature is not None:
+        kw.update(stats=run.train_set.label_stats(N_CLASS), temperature=temperature)
+    return CopyPaste(run.paste_banks[phase][1], seed=seed, **kw)
 
 
 def _logger(run, optimizer, modules, batches, *first):
@@ -555,7 +591,8 @@ def _logger(run, optimizer, modules, batches, *first):
     the run where the guard says so"""
     guard = [_GuardLog(optimizer, modules, run.args.max_consecutive_skips)] if run.plan.guarded else []
     parts = [*first, *guard, _TallyLog(" rcs drawn/hit ", batches.rcs_tally if batches.sampler is not None else None),
-             _TallyLog(" mix sel/px ", batches.mix_tally if batches.mix is not None else None)]
+             _TallyLog(" mix sel/px ", batches.mix_tally if batches.mix is not None else None),
+             _TallyLog(" paste obj/px ", batches.paste_tally if batches.paste is not None else None)]
 
     def log(prefix):
         print(prefix + "".join(part.line() for part in parts))

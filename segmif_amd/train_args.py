@@ -94,6 +94,26 @@ def build_parser():
                     "classes (default), or the one class --rare-class-sampling drew the donor for")
     ap.add_argument("--class-mix-phases", choices=("seg", "fusion", "both"), help="with --class-mix: the phases whose batches are "
                     "mixed (default seg)")
+    ap.add_argument("--copy-paste", action="store_true", help="instance copy-paste (Ghiasi et al. 2021, Simple Copy-Paste): the "
+                    "connected components of the training split's labels are banked on the device once, and with probability P a "
+                    "sample receives up to N of them, scaled (nearest neighbour), mirrored and placed at random, in every image and in "
+                    "the label.  Off by default.  This project's addition, NOT the reference's loader; every default below is this "
+                    "project's choice")
+    ap.add_argument("--copy-paste-prob", type=float, metavar="P", help="with --copy-paste: the probability that a sample is pasted into, "
+                    "in (0, 1] (default 0.5, this project's choice)")
+    ap.add_argument("--copy-paste-max-objects", type=int, metavar="N", help="with --copy-paste: a sample receives 1..N objects, N in 1..8 "
+                    "(default 3, this project's choice)")
+    ap.add_argument("--copy-paste-classes", type=int, nargs="+", metavar="C", help="with --copy-paste: the classes that are banked "
+                    "(default 1..8: class 0 is the background)")
+    ap.add_argument("--copy-paste-min-area", type=int, metavar="A", help="with --copy-paste: an object is banked when it holds at least A "
+                    "pixels (default 64, this project's choice)")
+    ap.add_argument("--copy-paste-scale", type=float, nargs=2, metavar=("LO", "HI"), help="with --copy-paste: an object is scaled by a "
+                    "log-uniform factor in [LO, HI], 0 < LO <= HI (default 0.5 2.0, this project's choice)")
+    ap.add_argument("--copy-paste-temperature", type=float, metavar="T", help="with --copy-paste: draw an object's class with probability "
+                    "proportional to exp((1 - frequency_c) / T) from the training split's class frequencies, T > 0, as "
+                    "--rare-class-sampling does (default: uniform over the banked classes)")
+    ap.add_argument("--copy-paste-phases", choices=("seg", "fusion", "both"), help="with --copy-paste: the phases whose batches are "
+                    "pasted into (default seg); the unlabelled loader of --self-training never is")
     ap.add_argument("--seg-region", choices=SEG_REGIONS, help="add a region objective to whatever --seg-loss builds, for the "
                     "SEGMENTATION phase only: lovasz is Lovasz-Softmax (the convex surrogate of the Jaccard index, the batch as one set), "
                     "dice the soft Dice loss.  This project's addition, NOT the reference's objective: its train.py trains on CE alone")
@@ -174,6 +194,8 @@ PHASES = {"seg": ("seg",), "fusion": ("fusion",), "both": ("seg", "fusion")}  # 
 _BELONGS = (
     ("--rare-class-sampling", ("--rcs-temperature", "--rcs-min-pixels", "--rcs-min-crop-ratio", "--rcs-fraction", "--rcs-phases")),
     ("--class-mix", ("--class-mix-prob", "--class-mix-min-pixels", "--class-mix-classes", "--class-mix-phases")),
+    ("--copy-paste", ("--copy-paste-prob", "--copy-paste-max-objects", "--copy-paste-classes", "--copy-paste-min-area", "--copy-paste-scale",
+                      "--copy-paste-temperature", "--copy-paste-phases")),
     ("--seg-region", ("--seg-region-weight", "--seg-region-classes", "--dice-smooth")),
     ("--self-training", ("--unlabelled-split", "--st-threshold", "--st-below", "--st-weight", "--st-mix", "--st-mix-prob", "--st-mix-min-pixels",
                          "--st-strong", "--st-temperature")),
@@ -189,6 +211,12 @@ _RANGES = (
     ("--rcs-fraction", lambda v: 0.0 < v <= 1.0, "must lie in (0, 1]"),
     ("--class-mix-prob", lambda v: 0.0 < v <= 1.0, "must lie in (0, 1]"),
     ("--class-mix-min-pixels", lambda v: v >= 0, "must be >= 0"),
+    ("--copy-paste-prob", lambda v: 0.0 < v <= 1.0, "must lie in (0, 1]"),
+    ("--copy-paste-max-objects", lambda v: 1 <= v <= 8, "must lie in 1..8"),
+    ("--copy-paste-classes", lambda v: all(0 <= c < N_CLASS for c in v), f"names classes in 0..{N_CLASS - 1}"),
+    ("--copy-paste-min-area", lambda v: v >= 1, "must be >= 1"),
+    ("--copy-paste-scale", lambda v: 0.0 < v[0] <= v[1] and math.isfinite(v[1]), "needs 0 < LO <= HI"),
+    ("--copy-paste-temperature", lambda v: v > 0 and math.isfinite(v), "must be a finite number > 0"),
     ("--label-smoothing", lambda v: 0.0 <= v < 1.0, "must lie in [0, 1)"),
     ("--seg-region-weight", lambda v: v > 0 and math.isfinite(v), "must be a finite number > 0"),
     ("--dice-smooth", lambda v: v >= 0 and math.isfinite(v), "must be a finite number >= 0"),
@@ -212,6 +240,8 @@ _RANGES = (
 _DEFAULTS = {
     "--rcs-temperature": 0.01, "--rcs-min-pixels": 3000, "--rcs-min-crop-ratio": 0.5, "--rcs-fraction": 1.0, "--rcs-phases": "seg",
     "--class-mix-prob": 0.5, "--class-mix-classes": "half", "--class-mix-min-pixels": 0, "--class-mix-phases": "seg",
+    "--copy-paste-prob": 0.5, "--copy-paste-max-objects": 3, "--copy-paste-min-area": 64, "--copy-paste-scale": (0.5, 2.0),
+    "--copy-paste-phases": "seg",  # (--copy-paste-classes and --copy-paste-temperature stay None: all classes, a uniform draw)
     "--seg-region-weight": 1.0, "--seg-region-classes": "present", "--dice-smooth": 1.0, "--ema-nets": "seg",
     "--st-threshold": 0.968, "--st-below": "keep", "--st-weight": 1.0, "--st-temperature": 1.0, "--st-mix-prob": 1.0, "--st-mix-min-pixels": 0,
     "--st-jitter-prob": 0.8, "--st-jitter-strength": 0.2, "--st-jitter-hue": 0.2, "--st-blur-prob": 0.5, "--st-blur-sigma": (0.15, 1.15),
