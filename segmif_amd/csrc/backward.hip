@@ -432,7 +432,9 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
     }
     const bool valid = lab != ignore_index && lab >= 0 && lab < C;
     if (valid) {
-      loss = (double)(logf(sum) + mx - x[lab]);
+      // (mx - x[lab]) first: both are logits, their difference is exact up to one rounding; log sum + mx would be rounded at
+      // |mx|'s size (logits around -16384: 1e-3 of a loss of order 1)
+      loss = (double)(logf(sum) + (mx - x[lab]));
       cnt = 1.0;
     }
     if (dlogits) {
