@@ -393,6 +393,11 @@ PASTE_SIGNATURES = {
                                       + [c_void_p] * 7),
 }
 
+# every public header under include/ -> the table that binds what it declares.  load() binds them all; a header without a table, a
+# declared symbol without a signature or a symbol in two tables fails tests/test_abi_and_host.py.
+HEADERS = {"segmif_hip.h": SIGNATURES, "segmif_distill.h": DISTILL_SIGNATURES, "segmif_calib.h": CALIB_SIGNATURES,
+           "segmif_objects.h": OBJECT_SIGNATURES, "segmif_paste.h": PASTE_SIGNATURES}
+
 _lib = None
 
 
@@ -415,11 +420,11 @@ def load():
     # kernels' library came up on the system ROCm's runtime and its first launch failed with hipErrorNoDevice (r5).
     import torch  # noqa: F401
     lib = ctypes.CDLL(path)
-    for name, (res, args) in (list(SIGNATURES.items()) + list(DISTILL_SIGNATURES.items()) + list(CALIB_SIGNATURES.items())
-                               + list(OBJECT_SIGNATURES.items()) + list(PASTE_SIGNATURES.items())):
-        fn = getattr(lib, name)  # AttributeError if the symbol is missing: loud by design
-        fn.restype = res
-        fn.argtypes = args
+    for signatures in HEADERS.values():
+        for name, (res, args) in signatures.items():
+            fn = getattr(lib, name)  # AttributeError if the symbol is missing: loud by design
+            fn.restype = res
+            fn.argtypes = args
     if lib.segmif_abi_version() != 4:
         raise HipLibraryMissing("libsegmif_hip.so ABI version mismatch; rebuild")
     _lib = lib

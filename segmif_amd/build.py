@@ -1,7 +1,5 @@
 """Builds libsegmif_hip.so (gfx950) in-tree with hipcc.  No torch cpp_extension, no hipify:
-the sources are native HIP and the library has a plain C ABI (include/segmif_hip.h; the distillation objectives: include/segmif_distill.h; the
-calibration statistics: include/segmif_calib.h; the object-level statistics: include/segmif_objects.h; instance copy-paste:
-include/segmif_paste.h)."""
+the sources are native HIP and the library has a plain C ABI (the headers under include/; segmif_amd/_lib.py's HEADERS names each)."""
 import hashlib
 import os
 import shutil
@@ -28,8 +26,10 @@ def _hipcc():
 
 def _digest():
     h = hashlib.sha256(" ".join(FLAGS).replace(ROOT, ".").encode())  # (not the checkout's absolute path: the same tree on the GPU box is the same build)
-    for f in SOURCES + sorted(h for h in os.listdir(CSRC) if h.endswith(".h")) + [os.path.join(ROOT, "include", "segmif_hip.h"), os.path.join(ROOT, "include", "segmif_distill.h"), os.path.join(ROOT, "include", "segmif_calib.h"), os.path.join(ROOT, "include", "segmif_objects.h"), os.path.join(ROOT, "include", "segmif_paste.h")]:
-        p = f if os.path.isabs(f) else os.path.join(CSRC, f)
+    def headers(d):  # every *.h of a directory, sorted: a new public header is hashed without being named here
+        return [os.path.join(d, f) for f in sorted(os.listdir(d)) if f.endswith(".h")]
+
+    for p in [os.path.join(CSRC, f) for f in SOURCES] + headers(CSRC) + headers(os.path.join(ROOT, "include")):
         with open(p, "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()

@@ -78,9 +78,10 @@ def main():
             if i < first:
                 continue
             values = entry.baseline()
-            same = values[arg] is None if value is None else values[arg] == value
-            assert not same, (entry.key, label)  # a mutation, never the baseline
-            values[arg] = value
+            for a, v in zip(arg, value) if isinstance(arg, tuple) else [(arg, value)]:  # (a tuple of names: a rule about them together)
+                same = values[a] is None if v is None else values[a] == v
+                assert not same, (entry.key, label)  # a mutation, never the baseline
+                values[a] = v
             keep = []
             emit({"begin": i})
             try:

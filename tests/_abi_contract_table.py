@@ -1,5 +1,5 @@
-"""The rejection contract of the C ABI (include/segmif_hip.h) as a table: for every entry point one VALID baseline argument set
-and a list of single-argument mutations of it, each of which the entry point must refuse with SEGMIF_EINVAL (-22) before it
+"""The rejection contract of the C ABI (every header under include/) as a table: for every entry point one VALID baseline argument
+set and a list of single-argument mutations of it, each of which the entry point must refuse with SEGMIF_EINVAL (-22) before it
 launches or calls into the HIP runtime.  tests/_abi_contract_child.py sends the mutations (never a baseline) in a process that
 sees no GPU; tests/test_abi_contract_host.py reads its records.
 
@@ -14,8 +14,13 @@ An argument carries a tag that says what it is; the tag generates the generic mu
     N(v)            a count:                                                  0 and -1
     LD(v, w)        a pitch in floats over rows of width w:                   w - 4;  with vec=True also v + 2 (no multiple of 4)
     V(v)            any other value:                                          -
-`rows` adds the mutations that are particular to the entry point, each with the header sentence or the code line behind it."""
+    A(vals, fill)   an array field of a descriptor, its count another field:  -   (`fill` holds a legal value for every slot and
+                    `vals` go in front of it, so a row that mutates the count changes nothing else)
+A descriptor entry (`struct`) also gets the row "desc=NULL": the first parameter itself.
+`rows` adds the mutations that are particular to the entry point, each with the header sentence or the code line behind it.  A
+row's argument may be a tuple of names with a tuple of values: a rule about two arguments together (H * W >= 2^31)."""
 import ctypes
+import functools
 
 from segmif_amd import _lib as L
 
@@ -34,6 +39,7 @@ def N(v): return {"kind": "count", "v": v}
 def LD(v, w, vec=False): return {"kind": "pitch", "v": v, "w": w, "vec": vec}
 def V(v): return {"kind": "val", "v": v}
 def HOST(vals): return {"kind": "host", "v": list(vals)}
+def A(vals, fill): return {"kind": "array", "v": tuple(vals), "fill": tuple(fill)}
 
 
 GENERIC = {
@@ -51,18 +57,18 @@ class Entry:
     def __init__(self, name, args, rows=(), struct=None, tail=(), variant=""):
         self.name, self.args, self.struct, self.tail, self.variant = name, list(args), struct, list(tail), variant
         self.extra = [tuple(r) for r in rows]
-        names = [a for a, _ in self.args + self.tail]
+        names = [a for a, _ in self.args + self.tail] + (["desc"] if struct is not None else [])
         assert len(names) == len(set(names)), (name, names)
         for arg, _, _ in self.extra:
-            assert arg in names, (name, arg)
+            assert all(a in names for a in (arg if isinstance(arg, tuple) else (arg,))), (name, arg)
 
     @property
     def key(self):
         return self.name + ("#" + self.variant if self.variant else "")
 
     def baseline(self):
-        """{name: value}; pointers get distinct fake addresses by position"""
-        out = {}
+        """{name: value}; pointers get distinct fake addresses by position; "desc" stands for the descriptor itself (None = NULL)"""
+        out = {} if self.struct is None else {"desc": "given"}
         for i, (a, t) in enumerate(self.args + self.tail):
             k = t["kind"]
             out[a] = (0x10000000 + 0x100000 * (i + 1)) if k == "ptr" else None if k == "null" else t["v"]
@@ -71,6 +77,8 @@ class Entry:
     def mutations(self):
         """[(label, arg, value, reason)]"""
         base, out = self.baseline(), []
+        if self.struct is not None:
+            out.append(("desc=NULL", "desc", None, GENERIC["null"]))
         for a, t in self.args + self.tail:
             k = t["kind"]
             if k == "ptr":
@@ -87,7 +95,7 @@ class Entry:
                     out.append((f"{a}={t['v'] + 2}", a, t["v"] + 2, GENERIC["pitch4"]))
         for a, v, why in self.extra:
             shown = "NULL" if v is None else (hex(v) if isinstance(v, int) and v > 1 << 20 else v)
-            out.append((f"{a}={shown}", a, v, why))
+            out.append((f"{','.join(a) if isinstance(a, tuple) else a}={shown}", a, v, why))
         labels = [m[0] for m in out]
         assert len(labels) == len(set(labels)), (self.key, labels)
         return out
@@ -110,11 +118,17 @@ class Entry:
         tail = [conv(t, values[a], c) for (a, t), c in zip(flat, types)]
         if self.struct is None:
             return fn(*tail)
+        if values["desc"] is None:
+            return fn(None, *tail)
         d = self.struct()
         keep.append(d)
         assert [a for a, _ in self.args] == [f[0] for f in self.struct._fields_], self.key
         for a, t in self.args:
-            setattr(d, a, values[a] if values[a] is not None else (None if t["kind"] in ("ptr", "null") else 0))
+            if t["kind"] == "array":  # (a tuple cannot be assigned to a ctypes array field)
+                for i, x in enumerate(tuple(values[a]) + t["fill"][len(values[a]):]):
+                    getattr(d, a)[i] = x
+            else:
+                setattr(d, a, values[a] if values[a] is not None else (None if t["kind"] in ("ptr", "null") else 0))
         return fn(ctypes.byref(d), *tail)
 
 
@@ -525,6 +539,78 @@ add("segmif_comm_world", [("comm", P()), ("world", P()), ("rank", P())])
 add("segmif_comm_allreduce_f32", [("comm", P()), ("send", P()), ("recv", P()), ("count", N(16)), ("average", V(0)), S])
 add("segmif_comm_destroy", [("comm", P())])
 
+# ------------------------------------------------------------------------------ distill_objective.hip (include/segmif_distill.h)
+_DS = [("temperature", V(2.0)), ("mode", V(1)), ("reserved", A((), (0, 0)))]
+_DS_T = "segmif_distill.h: 'T not finite or <= 0'"
+_DS_ROWS = [("temperature", 0.0, _DS_T), ("temperature", -1.0, _DS_T), ("temperature", float("inf"), _DS_T), ("temperature", float("nan"), _DS_T),
+            ("mode", 2, "segmif_distill.h: 'an unknown mode'"), ("mode", -1, "segmif_distill.h: 'an unknown mode'"),
+            ("C", 33, "segmif_distill.h: 'C outside 1..32'"), ("lds", 8, "segmif_distill.h: 'lds, ldt (backward: ldd) below C'"),
+            ("ldt", 8, "segmif_distill.h: 'lds, ldt (backward: ldd) below C'"), ("rows", -512, "segmif_distill.h: 'rows < 1'"),
+            ("rows_per_sample", -256, "segmif_distill.h: 'rows_per_sample < 1'"), ("rows_per_sample", 255, "segmif_distill.h: 'rows % rows_per_sample != 0'"),
+            ("rows", 65536 * 256, "segmif_distill.h: 'in channel mode B = rows / rows_per_sample > 65535 (the grid's second dimension)'")]
+_DS_DIMS = [("rows", N(512)), ("rows_per_sample", N(256)), ("C", N(9)), ("lds", LD(9, 9)), ("ldt", LD(9, 9))]
+add("segmif_distill_objective_f32", _DS, struct=L.SegmifDistill, rows=_DS_ROWS,
+    tail=[("student", P()), ("teacher", P()), ("workspace", P()), ("record4", P())] + _DS_DIMS + [S])
+add("segmif_distill_objective_bwd_f32", _DS, struct=L.SegmifDistill, rows=_DS_ROWS + [("ldd", 8, "segmif_distill.h: 'lds, ldt (backward: ldd) below C'")],
+    tail=[("student", P()), ("teacher", P()), ("workspace", P()), ("record4", P()), ("upstream", P()), ("dstudent", P())] + _DS_DIMS + [("ldd", LD(9, 9)), S])
+
+# ------------------------------------------------------------------------------- calibration_stats.hip (include/segmif_calib.h)
+_CB_T, _CB_E = "segmif_calib.h: 'a temperature that is not finite or <= 0'", "segmif_calib.h: 'edges that are not strictly ascending or not inside the open interval (0, 1) (NaN included)'"
+_CB_K, _CB_G = "segmif_calib.h: 'a threshold outside [0, 1] (NaN included)'", "segmif_calib.h: 'B or OH above SEGMIF_CALIB_MAX_GRID (the grid's dimensions)'"
+_CB_X = "segmif_calib.h: 'B, IH, IW, OH or OW below 1'"
+add("segmif_calibration_stats_f32", struct=L.SegmifCalib, args=[
+    ("n_temperatures", N(2)), ("n_edges", V(3)), ("n_thresholds", V(2)), ("reserved0", V(0)),
+    ("temperatures", A((1.0, 2.0), [1.0 + i for i in range(16)])), ("edges", A((0.25, 0.5, 0.75), [(i + 1) / 64.0 for i in range(32)])),
+    ("thresholds", A((0.9, 0.968), [0.5] * 8)), ("reserved", A((), [0] * 4))],
+    tail=[("x", P()), ("label", P()), ("counts", P()), ("above", P()), ("totals", P()), ("sums", P()), ("workspace", P()), ("conf", O()), ("pred", O()),
+          ("B", N(2)), ("IH", N(3)), ("IW", N(5)), ("OH", N(11)), ("OW", N(19)), ("C", N(9)), ("ldx", LD(9, 9)), S], rows=[
+    ("C", 33, "segmif_calib.h: 'C outside 1..32'"), ("ldx", 8, "segmif_calib.h: 'ldx < C'"),
+    ("n_temperatures", 17, "segmif_calib.h: 'NT outside 1..16'"), ("n_edges", -1, "segmif_calib.h: 'NE outside 0..31'"),
+    ("n_edges", 32, "segmif_calib.h: 'NE outside 0..31'"), ("n_thresholds", -1, "segmif_calib.h: 'NK outside 0..8'"),
+    ("n_thresholds", 9, "segmif_calib.h: 'NK outside 0..8'"),
+    ("temperatures", (1.0, 0.0), _CB_T), ("temperatures", (-1.0, 2.0), _CB_T), ("temperatures", (float("inf"), 2.0), _CB_T),
+    ("temperatures", (1.0, float("nan")), _CB_T),
+    ("edges", (0.25, 0.25, 0.75), _CB_E), ("edges", (0.5, 0.25, 0.75), _CB_E), ("edges", (0.0, 0.5, 0.75), _CB_E), ("edges", (0.25, 0.5, 1.0), _CB_E),
+    ("edges", (-0.5, 0.5, 0.75), _CB_E), ("edges", (0.25, float("nan"), 0.75), _CB_E),
+    ("thresholds", (0.9, 1.5), _CB_K), ("thresholds", (-0.1, 0.968), _CB_K), ("thresholds", (float("nan"), 0.968), _CB_K),
+    ("B", -2, _CB_X), ("OW", -19, _CB_X), ("B", 65536, _CB_G), ("OH", 65536, _CB_G)])  # above = NULL: 'a NULL above with NK > 0' (NK = 2)
+
+# --------------------------------------------------------------------------------------- objects.hip (include/segmif_objects.h)
+_OB_C, _OB_E = "segmif_objects.h: 'connectivity other than 4 or 8'", "segmif_objects.h: 'edges not strictly ascending or below 1'"
+_HW = [(65536, 32768), (46341, 46341), (2, 2 ** 30)]  # H * W >= 2^31
+add("segmif_object_stats_i32", struct=L.SegmifObjects, args=[
+    ("connectivity", V(8)), ("n_edges", V(2)), ("edges", A((1024, 9216), [10 ** (5 + i) for i in range(4)])), ("reserved", A((), [0] * 4))],
+    tail=[("pred", P()), ("label", P()), ("obj", P()), ("mass", P()), ("status", P()), ("workspace", P()), ("root_g", O()), ("root_p", O()),
+          ("B", N(2)), ("H", N(37)), ("W", N(53)), ("K", N(9)), S], rows=[
+    ("K", 33, "segmif_objects.h: 'K outside 1..32'"), ("connectivity", 0, _OB_C), ("connectivity", 6, _OB_C), ("connectivity", -8, _OB_C),
+    ("connectivity", 16, _OB_C), ("n_edges", -1, "segmif_objects.h: 'n_edges outside 0..3'"), ("n_edges", 4, "segmif_objects.h: 'n_edges outside 0..3'"),
+    ("edges", (1024, 1024), _OB_E), ("edges", (9216, 1024), _OB_E), ("edges", (0, 9216), _OB_E), ("edges", (-5, 9216), _OB_E),
+    ("B", -2, "segmif_objects.h: 'B, H or W below 1'"), ("H", -37, "segmif_objects.h: 'B, H or W below 1'"), ("W", -53, "segmif_objects.h: 'B, H or W below 1'"),
+    ("B", 32768, "segmif_objects.h: 'B above SEGMIF_OBJECTS_MAX_FRAMES: the grid's z holds 2 B'")]
+    + [(("H", "W"), hw, "segmif_objects.h: 'H * W >= 2^31'") for hw in _HW])
+
+# ------------------------------------------------------------------------------------- copy_paste.hip (include/segmif_paste.h)
+_PA_N, _PA_HW = "segmif_paste.h, boxes: 'n above SEGMIF_PASTE_MAX_FRAMES' (pack: 'n, H, W as above')", "segmif_paste.h, boxes: 'H * W >= 2^31' (pack: 'n, H, W as above')"
+add("segmif_object_boxes_i32", [("root", P()), ("label", P()), ("n", N(2)), ("H", N(37)), ("W", N(53)), ("K", N(9)), ("class_mask", V(0x1fe)), ("min_area", V(64)),
+                                ("max_box", V(500)), ("frame0", V(0)), ("records", P16()), ("capacity", V(16)), ("counter", P()), ("workspace", P()), S], rows=[
+    ("K", 33, "segmif_paste.h, boxes: 'K outside 1..32'"), ("min_area", 0, "segmif_paste.h, boxes: 'min_area or max_box below 1'"),
+    ("min_area", -3, "segmif_paste.h, boxes: 'min_area or max_box below 1'"), ("max_box", 0, "segmif_paste.h, boxes: 'min_area or max_box below 1'"),
+    ("capacity", -1, "segmif_paste.h, boxes: 'capacity or frame0 below 0'"), ("frame0", -1, "segmif_paste.h, boxes: 'capacity or frame0 below 0'"),
+    ("frame0", 2 ** 31 - 2, "segmif_paste.h, boxes: 'frame0 + n > 2^31 - 1'"), ("n", -2, "segmif_paste.h, boxes: 'n, H or W below 1'"), ("n", 32768, _PA_N),
+    ("W", -53, "segmif_paste.h, boxes: 'n, H or W below 1'")] + [(("H", "W"), hw, _PA_HW) for hw in _HW[:2]])  # records = NULL: 'NULL records with capacity > 0'
+add("segmif_object_pack_u8", [("records", P()), ("offsets", P8()), ("M", N(3)), ("store_pixels", V(100)), ("root", P()), ("ir", P()), ("vis", P()), ("mask", P()),
+                              ("frame0", V(0)), ("n", N(2)), ("H", N(37)), ("W", N(53)), ("patches", P8()), S], rows=[
+    ("store_pixels", -1, "segmif_paste.h, pack: 'store_pixels below 0'"), ("frame0", -1, "segmif_paste.h, pack: 'frame0 below 0'"), ("n", 32768, _PA_N),
+    (("H", "W"), _HW[0], _PA_HW)])
+_P16 = "segmif_paste.h, paste: 'one of the eight tensors not 16-byte aligned'"
+add("segmif_copy_paste_f32", [("ir3", P16()), ("vis3", P16()), ("mask3", P16()), ("label", P16()), ("B", N(2)), ("h", N(8)), ("w", N(12)), ("records", P()), ("offsets", P8()),
+                              ("patches", P8()), ("M", N(3)), ("store_pixels", N(100)), ("table", P()), ("P", V(3)), ("n_class", N(9)), ("ir3_out", P16()),
+                              ("vis3_out", P16()), ("mask3_out", P16()), ("label_out", P16()), ("pasted", P8()), ("tally", O8()), S], rows=[
+    ("P", 9, "segmif_paste.h, paste: 'P outside 0..8'"), ("P", -1, "segmif_paste.h, paste: 'P outside 0..8'"), ("w", 10, "segmif_paste.h, paste: 'w % 4'"),
+    ("w", 13, "segmif_paste.h, paste: 'w % 4'"), ("B", 65536, "segmif_paste.h, paste: 'B outside 1..65535'"),
+    ("n_class", 256, "segmif_paste.h, paste: 'n_class outside 1..255'"),
+    ("label_out", 0x10000000 + 0x100000 * 19 + 8, _P16 + " (label_out + 8)")])  # table = NULL: 'NULL table with P > 0' (P = 3)
+
 ENTRIES = E
 
 _SIZE = "size query / no pointers"
@@ -539,7 +625,8 @@ EXEMPT = {
     "segmif_augment_record_bytes": _SIZE, "segmif_fusion_stats_workspace_bytes": _SIZE, "segmif_structural_stats_workspace_bytes": _SIZE,
     "segmif_fusion_objective_blocks": _SIZE, "segmif_seg_objective_workspace_bytes": _SIZE, "segmif_region_objective_workspace_bytes": _SIZE,
     "segmif_grad_guard_record_bytes": _SIZE, "segmif_grad_entry_stat_bytes": _SIZE, "segmif_grad_param_count_bytes": _SIZE,
-    "segmif_grad_norm_workspace_bytes": _SIZE, "segmif_strong_augment_blocks": _SIZE,
+    "segmif_grad_norm_workspace_bytes": _SIZE, "segmif_strong_augment_blocks": _SIZE, "segmif_distill_workspace_bytes": _SIZE,
+    "segmif_calibration_workspace_bytes": _SIZE, "segmif_object_workspace_bytes": _SIZE, "segmif_object_boxes_workspace_bytes": _SIZE,
     "segmif_igemm_workspace_floats": "size query / no pointers of its own: it resolves the descriptor with segmif_igemm_f32's checks and returns 0 for a refused one",
     "segmif_comm_available": "size query / no pointers (an optional version word); -38 without RCCL",
     "segmif_conv3x3_split16_pack": "rejections covered by tests/test_abi_and_host.py::test_round4_training_entry_points_size_rules_and_rejections_without_a_gpu",
@@ -561,6 +648,22 @@ EXEMPT = {
 }
 
 
+def find(name, arg, value):
+    """the index of the row that sends `value` for `arg` to the entry point `name`: how the host test of a header holds the table to
+    the cases its header lists.  A misaligned pointer stands for its misalignment, the fake base addresses being the table's own."""
+    for i, e, _, a, v, _ in all_rows():
+        if e.name == name and a == arg:
+            tag = dict(e.args + e.tail).get(a, {}) if isinstance(a, str) else {}
+            if tag.get("kind") == "ptr" and isinstance(v, int) and isinstance(value, int):
+                same = v % 16 == value % 16
+            else:
+                same = repr(v) == repr(value)  # (repr: NaN inside a tuple, 0 and 0.0 apart)
+            if same:
+                return i
+    raise KeyError(f"tests/_abi_contract_table.py has no row {name}: {arg} = {value!r}")
+
+
+@functools.lru_cache(maxsize=None)
 def all_rows():
     """[(index, entry, label, arg, value, reason)] in a fixed order: what the child sends and the tests are parametrized over"""
     out = []

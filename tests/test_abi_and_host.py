@@ -1,16 +1,16 @@
-"""CPU-only checks: the C-ABI library loads and exports every symbol include/segmif_hip.h
-declares, the ctypes struct matches the C layout, host-side module logic (state_dict keys, cache
+"""CPU-only checks: the C-ABI library loads and exports every symbol the headers under include/ declare, each bound from its
+table of _lib.HEADERS; every ctypes struct matches the C layout; host-side module logic (state_dict keys, cache
 invalidation, loud failure on CPU tensors).  No kernel is launched here."""
 import ctypes
 import json
 import os
-import re
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 import torch
+
+import _abi_headers as headers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -23,57 +23,73 @@ def lib():
     return _lib.load()
 
 
-def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "segmif_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(segmif_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_every_declared_symbol_is_exported_and_bound(lib):
     from segmif_amd import _lib
-    syms = declared_symbols()
+    syms = headers.declared("segmif_hip.h")
     assert len(syms) >= 18
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in segmif_hip.h but not exported"
         assert s in _lib.SIGNATURES, f"{s} has no ctypes signature"
     assert sorted(_lib.SIGNATURES) == syms
-    assert lib.segmif_abi_version() == 4
+    assert lib.segmif_abi_version() == 4  # counts the main header only
     assert lib.segmif_igemm_num_tiles() == 15
     assert lib.segmif_linattn_num_blocks(307200) == 300
 
 
-def test_struct_layout_matches_c(lib, tmp_path):
-    """Compile a tiny C program against the header and compare sizeof/offsetof with ctypes."""
-    from segmif_amd._lib import SegmifIgemm
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "segmif_hip.h"\nint main(){printf("%zu %zu %zu %zu %zu\\n",'
-                   'sizeof(SegmifIgemm),offsetof(SegmifIgemm,M),offsetof(SegmifIgemm,act),'
-                   'offsetof(SegmifIgemm,in_zstride),offsetof(SegmifIgemm,tile));return 0;}')
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    want = [ctypes.sizeof(SegmifIgemm), SegmifIgemm.M.offset, SegmifIgemm.act.offset,
-            SegmifIgemm.in_zstride.offset, SegmifIgemm.tile.offset]
-    assert got == want
+def test_every_header_has_its_table_and_every_table_its_header():
+    from segmif_amd import _lib
+    assert sorted(_lib.HEADERS) == headers.headers(), "include/*.h and the keys of segmif_amd/_lib.py's HEADERS differ"
 
 
-def test_struct_layout_of_the_f16x3_fields_matches_c(lib, tmp_path):
-    """The descriptors that grew f16x3 fields (planes_f16 / planes_amax): size and the new fields' offsets against gcc."""
-    from segmif_amd._lib import SegmifConvPlanes, SegmifCrossTail, SegmifGemmSplit, SegmifIgemm
-    src = tmp_path / "layout16.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "segmif_hip.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n",'
-                   'sizeof(SegmifIgemm),offsetof(SegmifIgemm,planes_f16),offsetof(SegmifIgemm,planes_amax),'
-                   'sizeof(SegmifCrossTail),offsetof(SegmifCrossTail,planes_f16),offsetof(SegmifCrossTail,planes_amax),'
-                   'offsetof(SegmifIgemm,planes_amax_images),offsetof(SegmifCrossTail,planes_amax_images),'
-                   'sizeof(SegmifConvPlanes),sizeof(SegmifGemmSplit));return 0;}')
-    exe = tmp_path / "layout16"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    want = [ctypes.sizeof(SegmifIgemm), SegmifIgemm.planes_f16.offset, SegmifIgemm.planes_amax.offset,
-            ctypes.sizeof(SegmifCrossTail), SegmifCrossTail.planes_f16.offset, SegmifCrossTail.planes_amax.offset,
-            SegmifIgemm.planes_amax_images.offset, SegmifCrossTail.planes_amax_images.offset,
-            ctypes.sizeof(SegmifConvPlanes), ctypes.sizeof(SegmifGemmSplit)]
-    assert got == want
+@pytest.mark.parametrize("header", headers.headers())
+def test_header_and_registry_agree(lib, header):
+    """What a header declares is what its table of _lib.HEADERS lists; every symbol is exported and bound with that signature, and is
+    declared in no other header and listed in no other table."""
+    from segmif_amd import _lib
+    assert header in _lib.HEADERS, f"include/{header} has no table in segmif_amd/_lib.py's HEADERS"
+    signatures, syms = _lib.HEADERS[header], headers.declared(header)
+    assert not set(syms) - set(signatures), f"declared in {header} without a ctypes signature: {sorted(set(syms) - set(signatures))}"
+    assert not set(signatures) - set(syms), f"in {header}'s table but not declared there: {sorted(set(signatures) - set(syms))}"
+    for s in syms:
+        assert hasattr(lib, s), f"{s} is declared in {header} but not exported"
+        res, args = signatures[s]
+        fn = getattr(lib, s)
+        assert fn.restype is res and list(fn.argtypes) == list(args), f"{s} is not bound with its signature of {header}'s table"
+        for other, table in _lib.HEADERS.items():
+            if other != header:
+                assert s not in headers.declared(other), f"{s} is declared in {header} and in {other}"
+                assert s not in table, f"{s} is in the tables of {header} and of {other}"
+
+
+def _structures():
+    """{name: class} of the ctypes.Structure subclasses segmif_amd/_lib.py defines"""
+    from segmif_amd import _lib
+    return {n: c for n, c in vars(_lib).items() if isinstance(c, type) and issubclass(c, ctypes.Structure) and c.__module__ == _lib.__name__}
+
+
+def test_every_ctypes_structure_is_a_struct_of_some_header():
+    typedefd = {n for h in headers.headers() for n in headers.structs(h)}
+    assert not set(_structures()) - typedefd, f"ctypes structures no header typedefs: {sorted(set(_structures()) - typedefd)}"
+
+
+@pytest.mark.parametrize("header", headers.headers())
+def test_struct_layouts_match_c(header, tmp_path):
+    """Every struct a header typedefs has a ctypes class in _lib.py with the same fields in the same order (a ctypes name with one
+    trailing underscore, in_, is the C field without it), and gcc's sizeof(struct) and offsetof / sizeof of every field are ctypes'."""
+    classes, exprs, want = _structures(), [], []
+    for name, c_fields in headers.structs(header).items():
+        assert name in classes, f"{header} typedefs {name}, which has no ctypes.Structure in segmif_amd/_lib.py"
+        S = classes[name]
+        fields = [f[:-1] if f.endswith("_") else f for f, _ in S._fields_]
+        assert fields == c_fields, f"{name}: ctypes lacks {[f for f in c_fields if f not in fields]}, C lacks {[f for f in fields if f not in c_fields]}, or the order differs"
+        exprs.append(f"sizeof({name})")
+        want.append((f"sizeof({name})", ctypes.sizeof(S)))
+        for (f, _), c in zip(S._fields_, c_fields):
+            exprs += [f"offsetof({name}, {c})", f"sizeof((({name}*)0)->{c})"]
+            want += [(f"offsetof({name}, {c})", getattr(S, f).offset), (f"sizeof({name}.{c})", getattr(S, f).size)]
+    if exprs:
+        bad = [f"{what}: gcc {c}, ctypes {py}" for (what, py), c in zip(want, headers.c_ints(header, exprs, tmp_path)) if c != py]
+        assert not bad, bad
 
 
 def test_f16x3_entry_points_size_rules_and_rejections_without_a_gpu(lib):
@@ -412,21 +428,6 @@ def test_compute_results_host_port_matches_reference(golden_dir):
         metrics.confusion_matrix(torch.zeros(4, dtype=torch.int32), torch.zeros(4, dtype=torch.int64))
     with pytest.raises(RuntimeError):
         metrics.quantize_fused(torch.zeros(1, 3, 4, 4))
-
-
-def test_struct_layout_of_the_round4_igemm_fields_matches_c(lib, tmp_path):
-    """SegmifIgemm's round-4 tail (relu_mask .. mask_zstride: the DRDB / CrossPath backward epilogues and the f16x3 training convs'
-    range slots): size and every new field's offset against gcc."""
-    from segmif_amd._lib import SegmifIgemm
-    names = ["relu_mask", "ld_mask", "split_f16", "split_in_amax", "split_in_amax_n", "split_out_amax", "split_out_amax_n",
-             "wgrad_dy_amax", "wgrad_dy_amax_n", "mask_zstride"]
-    src = tmp_path / "layout_r4.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "segmif_hip.h"\nint main(){printf("%zu' + " %zu" * len(names) + '\\n",sizeof(SegmifIgemm)'
-                   + "".join(f",offsetof(SegmifIgemm,{n})" for n in names) + ");return 0;}")
-    exe = tmp_path / "layout_r4"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert got == [ctypes.sizeof(SegmifIgemm)] + [getattr(SegmifIgemm, n).offset for n in names]
 
 
 def test_round4_training_entry_points_size_rules_and_rejections_without_a_gpu(lib):

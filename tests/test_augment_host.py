@@ -4,7 +4,6 @@ parameter sampling, the iterator's order and the refusals.  No kernel is launche
 import ctypes
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
@@ -117,8 +116,9 @@ def test_the_fixture_covers_what_it_should(golden):
     assert os.path.getsize(os.path.join(ROOT, "tests", "golden", "augment.npz")) < 2 ** 20
 
 
-def test_record_layout_matches_c(data, tmp_path):
-    """The word offsets segmif_amd.data packs records with are those of the C struct and of its ctypes mirror."""
+def test_record_layout_matches_c(data):
+    """The word offsets segmif_amd.data packs records with are those of the C struct's ctypes mirror (which
+    tests/test_abi_and_host.py::test_struct_layouts_match_c holds to the header, field by field)."""
     from segmif_amd._lib import SegmifAugmentRec as R
     fields = {"src": data._SRC, "h": data._H, "w": data._W, "nw": data._NW, "nh": data._NH, "flip": data._FLIP, "bright_on": data._BON,
               "beta": data._BETA, "contrast_on": data._CON, "alpha": data._ALPHA, "pad_h": data._PADH, "pad_w": data._PADW,
@@ -128,13 +128,6 @@ def test_record_layout_matches_c(data, tmp_path):
     assert ctypes.sizeof(R) == 4 * data.REC_WORDS
     for name, word in fields.items():
         assert getattr(R, name).offset == 4 * word, name
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "segmif_hip.h"\nint main(){printf("%zu", sizeof(SegmifAugmentRec));'
-                   + "".join(f'printf(" %zu", offsetof(SegmifAugmentRec, {n}));' for n in fields) + "return 0;}")
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert got == [4 * data.REC_WORDS] + [4 * v for v in fields.values()]
 
 
 def test_pack_records(data):

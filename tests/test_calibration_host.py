@@ -1,34 +1,25 @@
 """CPU-only checks of the calibration statistics (csrc/calibration_stats.hip behind utils/calibration.py, the Evaluator's
 calibration= and the --calibration / --st-temperature flags; ABI in include/segmif_calib.h).  No kernel is launched here.
 
-  - the header's guarantees: every declared symbol is exported and bound from _lib.CALIB_SIGNATURES and none of them is in
-    segmif_hip.h or SIGNATURES, the struct's layout is a compiled C probe's, and every single-argument mutation of a valid baseline
-    out of the documented domain returns SEGMIF_EINVAL - sent by tests/_calibration_child.py in a child process that sees no
-    device and has proved so; the baseline itself is never sent
+  - the header's part of what tests/test_abi_and_host.py and tests/test_abi_contract_host.py check for every header: the symbols it
+    is expected to declare, its constants, workspace_bytes, and that the contract table holds every case of its EINVAL list
   - calibration_scores on hand-made tables, uniform_edges, the parser errors, the loud failures of the Python layers
   - the restatement tests/_calibration_ref.py against F.interpolate + softmax in float64 and an ECE worked by hand, and the
     seeded cases of the GPU tests: the restatement alone leaves at most 1 % of the valid pixels of every case out"""
-import ctypes
-import json
 import math
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
-import _calibration_child as child
+import _abi_contract_table as table
+import _abi_headers as headers
 import _calibration_ref as ref
+from test_abi_contract_host import check_rejected, records  # noqa: F401 - the fixture: the contract child's records
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "segmif_calib.h")
-EINVAL = -22
-ROWS = child.rows()
-IDS = [r[1] for r in ROWS]
+NAME = "segmif_calibration_stats_f32"
 
 
 @pytest.fixture(scope="module")
@@ -39,51 +30,21 @@ def lib():
     return _lib.load()
 
 
-def declared(path):
-    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(segmif_[a-z0-9_]+)\s*\(", text)))
-
-
 # ---- the ABI ------------------------------------------------------------------------------------------------------------------------------
 
-def test_every_declared_symbol_is_exported_and_bound_and_not_in_the_main_header(lib):
-    from segmif_amd import _lib
-    syms = declared(HEADER)
-    assert syms == ["segmif_calibration_stats_f32", "segmif_calibration_workspace_bytes"]
-    assert sorted(_lib.CALIB_SIGNATURES) == syms
-    main = declared(os.path.join(ROOT, "include", "segmif_hip.h")) + declared(os.path.join(ROOT, "include", "segmif_distill.h"))
-    for s in syms:
-        fn = getattr(lib, s)  # exported
-        res, args = _lib.CALIB_SIGNATURES[s]
-        assert fn.restype is res and list(fn.argtypes) == list(args), s  # bound by _lib.load()
-        assert s not in main and s not in _lib.SIGNATURES and s not in _lib.DISTILL_SIGNATURES, s
-    assert lib.segmif_abi_version() == 4  # the main header's count is what it was
-
-
-def test_the_digest_reads_the_header():
-    import inspect
+def test_the_header_declares_these_symbols_and_its_source_is_built():
     from segmif_amd import build
-    assert "segmif_calib.h" in inspect.getsource(build._digest) and "calibration_stats.hip" in build.SOURCES
+    assert headers.declared("segmif_calib.h") == [NAME, "segmif_calibration_workspace_bytes"]
+    assert "calibration_stats.hip" in build.SOURCES
 
 
-def test_struct_layout_matches_c(tmp_path):
+def test_the_headers_constants_and_the_descriptors_fields(tmp_path):
     from segmif_amd import _lib
-    S = _lib.SegmifCalib
-    fields = ["n_temperatures", "n_edges", "n_thresholds", "reserved0", "temperatures", "edges", "thresholds", "reserved"]
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "segmif_calib.h"\nint main(){printf("%zu", sizeof(SegmifCalib));\n'
-                   + "".join(f'printf(" %zu %zu", offsetof(SegmifCalib, {f}), sizeof(((SegmifCalib*)0)->{f}));\n' for f in fields)
-                   + 'printf(" %d %d %d %d %d %d\\n", SEGMIF_CALIB_MAX_TEMPERATURES, SEGMIF_CALIB_MAX_EDGES, SEGMIF_CALIB_MAX_THRESHOLDS,'
-                     "SEGMIF_CALIB_BLOCK_COLUMNS, SEGMIF_CALIB_BLOCK_ROWS, SEGMIF_CALIB_MAX_GRID);return 0;}")
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    want = [ctypes.sizeof(S)]
-    for f in fields:
-        want += [getattr(S, f).offset, getattr(S, f).size]
-    assert got[:len(want)] == want
-    assert got[len(want):] == [_lib.CALIB_MAX_TEMPERATURES, _lib.CALIB_MAX_EDGES, _lib.CALIB_MAX_THRESHOLDS, 256, 4, 65535]
-    assert [f for f, _ in S._fields_] == fields
+    got = headers.c_ints("segmif_calib.h", ["SEGMIF_CALIB_MAX_TEMPERATURES", "SEGMIF_CALIB_MAX_EDGES", "SEGMIF_CALIB_MAX_THRESHOLDS",
+                                            "SEGMIF_CALIB_BLOCK_COLUMNS", "SEGMIF_CALIB_BLOCK_ROWS", "SEGMIF_CALIB_MAX_GRID"], tmp_path)
+    assert got == [_lib.CALIB_MAX_TEMPERATURES, _lib.CALIB_MAX_EDGES, _lib.CALIB_MAX_THRESHOLDS, 256, 4, 65535]
+    assert [f for f, _ in _lib.SegmifCalib._fields_] == ["n_temperatures", "n_edges", "n_thresholds", "reserved0", "temperatures", "edges",
+                                                         "thresholds", "reserved"]
 
 
 def test_workspace_bytes_is_positive_for_legal_sizes_and_zero_for_refused_ones(lib):
@@ -97,42 +58,31 @@ def test_workspace_bytes_is_positive_for_legal_sizes_and_zero_for_refused_ones(l
         assert size(B, OH, OW, NT) == 0, (B, OH, OW, NT)
 
 
-# ---- rejections, in a child that sees no device -------------------------------------------------------------------------------------------
+# ---- rejections: the cases of the header's EINVAL list, each a row of tests/_abi_contract_table.py that the contract child sent -------
 
-@pytest.fixture(scope="module")
-def records(tmp_path_factory, lib):
-    rec_path = str(tmp_path_factory.mktemp("calibration_contract") / "records.jsonl")
-    env = dict(os.environ)
-    env.update({"HIP_VISIBLE_DEVICES": "-1", "CUDA_VISIBLE_DEVICES": "-1"})
-    cmd = ["timeout", "-k", "10", "120", sys.executable, os.path.join(ROOT, "tests", "_calibration_child.py"), rec_path]
-    r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=150)
-    out = {"status": r.returncode, "tail": r.stdout[-1500:] + "\n" + r.stderr[-2500:]}
-    for line in (json.loads(l) for l in open(rec_path)) if os.path.exists(rec_path) else ():
-        if "refused" in line:
-            out["error"] = "the child refused to call anything: " + line["refused"]
-        elif "proof" in line:
-            out["proof"] = line["proof"]
-        elif "i" in line:
-            out[line["i"]] = line["rc"]
-    return out
+MUTATIONS = [("desc", None), ("x", None), ("label", None), ("counts", None), ("totals", None), ("sums", None), ("workspace", None),
+             ("above", None),  # NK = 2 > 0
+             ("C", 0), ("C", -1), ("C", 33), ("ldx", 8),
+             ("NT", 0), ("NT", -1), ("NT", 17), ("NE", -1), ("NE", 32), ("NK", -1), ("NK", 9),
+             ("temperatures", (1.0, 0.0)), ("temperatures", (-1.0, 2.0)), ("temperatures", (math.inf, 2.0)), ("temperatures", (1.0, math.nan)),
+             ("edges", (0.25, 0.25, 0.75)), ("edges", (0.5, 0.25, 0.75)), ("edges", (0.0, 0.5, 0.75)), ("edges", (0.25, 0.5, 1.0)),
+             ("edges", (-0.5, 0.5, 0.75)), ("edges", (0.25, math.nan, 0.75)),
+             ("thresholds", (0.9, 1.5)), ("thresholds", (-0.1, 0.968)), ("thresholds", (math.nan, 0.968)),
+             ("B", 0), ("B", -2), ("IH", 0), ("IW", 0), ("OH", 0), ("OW", 0), ("OW", -19),
+             ("B", 65536), ("OH", 65536)]
+FIELD = {"NT": "n_temperatures", "NE": "n_edges", "NK": "n_thresholds"}  # the header's names for the descriptor's counts
 
 
-def test_the_child_saw_no_device_and_ran_every_row(records):
-    assert "error" not in records, records["error"]
-    assert records["status"] == 0 and "proof" in records, records["tail"]
-    assert not [IDS[i] for i in range(len(ROWS)) if i not in records]
-    args = {a for a, _ in child.MUTATIONS}  # every case of the header's EINVAL list is a row
+def test_the_cases_cover_the_headers_einval_list():
+    args = {a for a, _ in MUTATIONS}
     assert {"desc", "x", "label", "counts", "totals", "sums", "workspace", "above", "C", "ldx", "NT", "NE", "NK", "temperatures", "edges",
             "thresholds", "B", "IH", "IW", "OH", "OW"} <= args
-    assert ("B", 65536) in child.MUTATIONS and ("OH", 65536) in child.MUTATIONS  # the grid limits
+    assert ("B", 65536) in MUTATIONS and ("OH", 65536) in MUTATIONS  # the grid limits
 
 
-@pytest.mark.parametrize("row", ROWS, ids=IDS)
-def test_rejected(records, row):
-    i = row[0]
-    assert "error" not in records, records["error"]
-    assert i in records, f"{IDS[i]}: the child wrote no record\n{records['tail']}"
-    assert records[i] == EINVAL, f"{IDS[i]} returned {records[i]}, not SEGMIF_EINVAL"
+@pytest.mark.parametrize("case", MUTATIONS, ids=[f"{NAME}:{arg}={value}" for arg, value in MUTATIONS])
+def test_rejected(records, case):
+    check_rejected(records, table.find(NAME, FIELD.get(case[0], case[0]), case[1]))
 
 
 # ---- scores on hand-made tables ---------------------------------------------------------------------------------------------------------------

@@ -2,32 +2,23 @@
 data.CopyPaste, the --copy-paste flags; ABI in include/segmif_paste.h).  No kernel is launched here.
 
   - the restatement tests/_copy_paste_ref.py: its cases worked by hand, and its boxes against scipy.ndimage.find_objects per class
-  - the header's guarantees: every declared symbol is exported and bound from _lib.PASTE_SIGNATURES and is in no other header or
-    table, the digest reads the header, segmif_abi_version() is what it was, workspace_bytes, and every host-checkable rejection
-    sent by tests/_copy_paste_child.py in a child process that sees no device and has proved so
+  - the header's part of what tests/test_abi_and_host.py and tests/test_abi_contract_host.py check for every header: the symbols it
+    is expected to declare, its constants against _lib and ops, workspace_bytes, and cases of its EINVAL list in the contract table
   - CopyPaste.draw: a fixed number of draws per sample, centres inside the crop, steps and sizes within the kernel's domain for boxes of
     1 and of 4096, reproducible from the seed and different per rank; ops.check_paste_table
   - the parser's errors and the unchanged default plan"""
-import json
 import os
 import random
-import re
-import subprocess
-import sys
 import types
 
 import numpy as np
 import pytest
 
-import _copy_paste_child as child
+import _abi_contract_table as table
+import _abi_headers as headers
 import _copy_paste_ref as ref
 import _objects_ref as objects_ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "segmif_paste.h")
-EINVAL = -22
-ROWS = child.rows()
-IDS = [r[1] for r in ROWS]
+from test_abi_contract_host import check_rejected, records  # noqa: F401 - the fixture: the contract child's records
 
 
 @pytest.fixture(scope="module")
@@ -36,11 +27,6 @@ def lib():
     if not os.path.exists(_lib.LIB_PATH):
         build.build()
     return _lib.load()
-
-
-def declared(path):
-    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(segmif_[a-z0-9_]+)\s*\(", text)))
 
 
 # ---- the restatement ----------------------------------------------------------------------------------------------------------------------
@@ -100,33 +86,22 @@ def test_the_patch_store_holds_the_object_alone():
 
 # ---- the ABI ------------------------------------------------------------------------------------------------------------------------------
 
-def test_every_declared_symbol_is_exported_and_bound_and_in_no_other_header(lib):
-    from segmif_amd import _lib
-    syms = declared(HEADER)
-    assert syms == ["segmif_copy_paste_f32", "segmif_object_boxes_i32", "segmif_object_boxes_workspace_bytes", "segmif_object_pack_u8"]
-    assert sorted(_lib.PASTE_SIGNATURES) == syms
-    others = sum((declared(os.path.join(ROOT, "include", h)) for h in ("segmif_hip.h", "segmif_distill.h", "segmif_calib.h", "segmif_objects.h")), [])
-    for s in syms:
-        fn = getattr(lib, s)  # exported
-        res, args = _lib.PASTE_SIGNATURES[s]
-        assert fn.restype is res and list(fn.argtypes) == list(args), s  # bound by _lib.load()
-        assert s not in others, s
-        for table in (_lib.SIGNATURES, _lib.DISTILL_SIGNATURES, _lib.CALIB_SIGNATURES, _lib.OBJECT_SIGNATURES):
-            assert s not in table, s
-    assert lib.segmif_abi_version() == 4  # the main header's count is what it was
+def test_the_header_declares_these_symbols_and_its_source_is_built():
+    from segmif_amd import build
+    assert headers.declared("segmif_paste.h") == ["segmif_copy_paste_f32", "segmif_object_boxes_i32", "segmif_object_boxes_workspace_bytes",
+                                                  "segmif_object_pack_u8"]
+    assert "copy_paste.hip" in build.SOURCES
 
 
-def test_the_digest_reads_the_header_and_the_constants_are_the_headers():
-    import inspect
-    from segmif_amd import _lib, build, ops
-    assert "segmif_paste.h" in inspect.getsource(build._digest) and "copy_paste.hip" in build.SOURCES
-    text = open(HEADER).read()
-    defs = {k: v for k, v in re.findall(r"#define (SEGMIF_PASTE_[A-Z_]+) +\(?([0-9 <]+)\)?", text)}
-    assert eval(defs["SEGMIF_PASTE_RECORD_WORDS"]) == _lib.PASTE_RECORD_WORDS == ops.PASTE_WORDS == ref.WORDS == 8
-    assert eval(defs["SEGMIF_PASTE_MAX_SLOTS"]) == _lib.PASTE_MAX_SLOTS == ops.PASTE_MAX_SLOTS == ref.MAX_SLOTS
-    assert eval(defs["SEGMIF_PASTE_MAX_SIZE"]) == _lib.PASTE_MAX_SIZE == ops.PASTE_MAX_SIZE == ref.MAX_SIZE == 4096
-    assert eval(defs["SEGMIF_PASTE_MAX_STEP"]) == _lib.PASTE_MAX_STEP == ops.PASTE_MAX_STEP == ref.MAX_STEP == 2 ** 24
-    assert eval(defs["SEGMIF_PASTE_MAX_FRAMES"]) == _lib.PASTE_MAX_FRAMES and eval(defs["SEGMIF_PASTE_WORKSPACE_PER_PIXEL"]) == _lib.PASTE_WORKSPACE_PER_PIXEL
+def test_the_constants_are_the_headers(tmp_path):
+    from segmif_amd import _lib, ops
+    names = ["RECORD_WORDS", "MAX_SLOTS", "MAX_SIZE", "MAX_STEP", "MAX_FRAMES", "WORKSPACE_PER_PIXEL"]
+    defs = dict(zip(names, headers.c_ints("segmif_paste.h", ["SEGMIF_PASTE_" + n for n in names], tmp_path)))
+    assert defs["RECORD_WORDS"] == _lib.PASTE_RECORD_WORDS == ops.PASTE_WORDS == ref.WORDS == 8
+    assert defs["MAX_SLOTS"] == _lib.PASTE_MAX_SLOTS == ops.PASTE_MAX_SLOTS == ref.MAX_SLOTS
+    assert defs["MAX_SIZE"] == _lib.PASTE_MAX_SIZE == ops.PASTE_MAX_SIZE == ref.MAX_SIZE == 4096
+    assert defs["MAX_STEP"] == _lib.PASTE_MAX_STEP == ops.PASTE_MAX_STEP == ref.MAX_STEP == 2 ** 24
+    assert defs["MAX_FRAMES"] == _lib.PASTE_MAX_FRAMES and defs["WORKSPACE_PER_PIXEL"] == _lib.PASTE_WORKSPACE_PER_PIXEL
 
 
 def test_workspace_bytes_is_positive_for_legal_sizes_and_zero_for_refused_ones(lib):
@@ -137,41 +112,35 @@ def test_workspace_bytes_is_positive_for_legal_sizes_and_zero_for_refused_ones(l
         assert size(n, H, W) == 0, (n, H, W)
 
 
-# ---- rejections, in a child that sees no device -------------------------------------------------------------------------------------------
+# ---- rejections: the cases of the header's EINVAL list, each a row of tests/_abi_contract_table.py that the contract child sent -------
 
-@pytest.fixture(scope="module")
-def records(tmp_path_factory, lib):
-    rec_path = str(tmp_path_factory.mktemp("copy_paste_contract") / "records.jsonl")
-    env = dict(os.environ)
-    env.update({"HIP_VISIBLE_DEVICES": "-1", "CUDA_VISIBLE_DEVICES": "-1"})
-    cmd = ["timeout", "-k", "10", "120", sys.executable, os.path.join(ROOT, "tests", "_copy_paste_child.py"), rec_path]
-    r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=150)
-    out = {"status": r.returncode, "tail": r.stdout[-1500:] + "\n" + r.stderr[-2500:]}
-    for line in (json.loads(l) for l in open(rec_path)) if os.path.exists(rec_path) else ():
-        if "refused" in line:
-            out["error"] = "the child refused to call anything: " + line["refused"]
-        elif "proof" in line:
-            out["proof"] = line["proof"]
-        elif "i" in line:
-            out[line["i"]] = line["rc"]
-    return out
+MUTATIONS = {
+    "segmif_object_boxes_i32": [("root", None), ("label", None), ("counter", None), ("workspace", None), ("records", None),
+                                ("K", 0), ("K", -1), ("K", 33), ("min_area", 0), ("min_area", -3), ("max_box", 0), ("capacity", -1),
+                                ("frame0", -1), ("frame0", 2 ** 31 - 2), ("n", 0), ("n", -2), ("n", 32768), ("H", 0), ("W", 0), ("W", -53),
+                                ("HW", (65536, 32768)), ("HW", (46341, 46341))],
+    "segmif_object_pack_u8": [("records", None), ("offsets", None), ("root", None), ("ir", None), ("vis", None), ("mask", None),
+                              ("patches", None), ("M", 0), ("M", -1), ("store_pixels", -1), ("frame0", -1), ("n", 0), ("n", 32768),
+                              ("H", 0), ("W", 0), ("HW", (65536, 32768))],
+    "segmif_copy_paste_f32": [("ir3", None), ("vis3", None), ("mask3", None), ("label", None), ("records", None), ("offsets", None),
+                              ("patches", None), ("table", None), ("ir3_out", None), ("vis3_out", None), ("mask3_out", None),
+                              ("label_out", None), ("pasted", None), ("P", 9), ("P", -1), ("w", 10), ("w", 13), ("w", 0), ("h", 0), ("B", 0),
+                              ("B", 65536), ("n_class", 0), ("n_class", 256), ("M", 0), ("store_pixels", 0),
+                              ("ir3", 0x100004), ("label_out", 0xc00008)],  # a tensor 4 bytes, and 8 bytes, off its 16-byte alignment
+}
+CASES = [(entry, arg, value) for entry, muts in MUTATIONS.items() for arg, value in muts]
 
 
-def test_the_child_saw_no_device_and_ran_every_row(records):
-    assert "error" not in records, records["error"]
-    assert records["status"] == 0 and "proof" in records, records["tail"]
-    assert not [IDS[i] for i in range(len(ROWS)) if i not in records]
-    boxes, paste = (set(child.MUTATIONS[k]) for k in ("segmif_object_boxes_i32", "segmif_copy_paste_f32"))
+def test_the_cases_cover_the_headers_einval_list():
+    boxes, paste = (set(MUTATIONS[k]) for k in ("segmif_object_boxes_i32", "segmif_copy_paste_f32"))
     assert {("K", 0), ("K", 33), ("capacity", -1), ("root", None), ("records", None)} <= boxes   # K outside 1..32, a negative capacity
     assert {("P", 9), ("w", 10), ("table", None), ("pasted", None)} <= paste                       # P > 8, w % 4
 
 
-@pytest.mark.parametrize("row", ROWS, ids=IDS)
-def test_rejected(records, row):
-    i = row[0]
-    assert "error" not in records, records["error"]
-    assert i in records, f"{IDS[i]}: the child wrote no record\n{records['tail']}"
-    assert records[i] == EINVAL, f"{IDS[i]} returned {records[i]}, not SEGMIF_EINVAL"
+@pytest.mark.parametrize("case", CASES, ids=[f"{entry}:{arg}={value}" for entry, arg, value in CASES])
+def test_rejected(records, case):
+    entry, arg, value = case
+    check_rejected(records, table.find(entry, ("H", "W") if arg == "HW" else arg, value))
 
 
 # ---- the policy ---------------------------------------------------------------------------------------------------------------------------

@@ -1,34 +1,25 @@
 """CPU-only checks of the distillation objectives (csrc/distill_objective.hip behind losses.DistillObjective, segmif_amd.distill and
 the train command's --distill-* flags; ABI in include/segmif_distill.h).  No kernel is launched here.
 
-  - the header's two guarantees, which tests/test_abi_and_host.py and tests/test_abi_contract_host.py give segmif_hip.h: every
-    declared symbol is exported and bound (from _lib.DISTILL_SIGNATURES, none of them in segmif_hip.h or SIGNATURES), the struct's
-    layout is a compiled C probe's, and every single-argument mutation of a valid baseline out of the documented domain returns
-    SEGMIF_EINVAL - sent by tests/_distill_child.py in a child process that sees no device and has proved so, started with
-    subprocess.run under `timeout -k 10 120`; the baseline itself is never sent
+  - the header's part of what tests/test_abi_and_host.py and tests/test_abi_contract_host.py check for every header (symbols exported
+    and bound, struct layouts, every row of the contract table rejected): the symbols it is expected to declare, its constants, and
+    that the contract table holds every case of its EINVAL list
   - the float64 restatement tests/_distill_ref.py against F.kl_div, its zero cases, its gradient against autograd
   - parser, checks and plan of the --distill-* flags
   - the loud failures of losses.DistillObjective"""
-import ctypes
-import json
 import math
 import os
-import re
-import subprocess
-import sys
 
 import pytest
 import torch
 import torch.nn.functional as F
 
-import _distill_child as child
+import _abi_contract_table as table
+import _abi_headers as headers
 import _distill_ref as ref
+from test_abi_contract_host import check_rejected, records  # noqa: F401 - the fixture: the contract child's records
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "segmif_distill.h")
-EINVAL = -22
-ROWS = child.rows()
-IDS = [r[2] for r in ROWS]
+FWD, BWD = "segmif_distill_objective_f32", "segmif_distill_objective_bwd_f32"
 
 
 @pytest.fixture(scope="module")
@@ -39,46 +30,19 @@ def lib():
     return _lib.load()
 
 
-def declared(path):
-    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(segmif_[a-z0-9_]+)\s*\(", text)))
-
-
 # ---- the ABI ------------------------------------------------------------------------------------------------------------------------------
 
-def test_every_declared_symbol_is_exported_and_bound_and_not_in_the_main_header(lib):
-    from segmif_amd import _lib
-    syms = declared(HEADER)
-    assert syms == ["segmif_distill_objective_bwd_f32", "segmif_distill_objective_f32", "segmif_distill_workspace_bytes"]
-    assert sorted(_lib.DISTILL_SIGNATURES) == syms
-    main = declared(os.path.join(ROOT, "include", "segmif_hip.h"))
-    for s in syms:
-        fn = getattr(lib, s)  # exported
-        res, args = _lib.DISTILL_SIGNATURES[s]
-        assert fn.restype is res and list(fn.argtypes) == list(args), s  # bound by _lib.load()
-        assert s not in main and s not in _lib.SIGNATURES, s
-    assert lib.segmif_abi_version() == 4  # the main header's count is what it was
-
-
-def test_the_digest_reads_the_header():
-    import inspect
+def test_the_header_declares_these_symbols_and_its_source_is_built():
     from segmif_amd import build
-    assert "segmif_distill.h" in inspect.getsource(build._digest) and "distill_objective.hip" in build.SOURCES
+    assert headers.declared("segmif_distill.h") == [BWD, FWD, "segmif_distill_workspace_bytes"]
+    assert "distill_objective.hip" in build.SOURCES
 
 
-def test_struct_layout_matches_c(tmp_path):
-    from segmif_amd._lib import DISTILL_CHANNEL, DISTILL_PIXEL, SegmifDistill
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "segmif_distill.h"\nint main(){printf("%zu %zu %zu %zu %d %d %d %d %d\\n",'
-                   "sizeof(SegmifDistill),offsetof(SegmifDistill,temperature),offsetof(SegmifDistill,mode),offsetof(SegmifDistill,reserved),"
-                   "SEGMIF_DISTILL_PIXEL,SEGMIF_DISTILL_CHANNEL,SEGMIF_DISTILL_BLOCK_ROWS,SEGMIF_DISTILL_MAX_BLOCKS_PER_SAMPLE,"
-                   "SEGMIF_DISTILL_MAX_BATCH);return 0;}")
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert got[:4] == [ctypes.sizeof(SegmifDistill), SegmifDistill.temperature.offset, SegmifDistill.mode.offset,
-                       SegmifDistill.reserved.offset]
-    assert got[4:6] == [DISTILL_PIXEL, DISTILL_CHANNEL] and got[6:] == [256, 64, 65535]
+def test_the_headers_constants(tmp_path):
+    from segmif_amd._lib import DISTILL_CHANNEL, DISTILL_PIXEL
+    got = headers.c_ints("segmif_distill.h", ["SEGMIF_DISTILL_PIXEL", "SEGMIF_DISTILL_CHANNEL", "SEGMIF_DISTILL_BLOCK_ROWS",
+                                              "SEGMIF_DISTILL_MAX_BLOCKS_PER_SAMPLE", "SEGMIF_DISTILL_MAX_BATCH"], tmp_path)
+    assert got[:2] == [DISTILL_PIXEL, DISTILL_CHANNEL] and got[2:] == [256, 64, 65535]
 
 
 def test_workspace_bytes_is_positive_for_legal_sizes_and_zero_for_refused_ones(lib):
@@ -98,42 +62,27 @@ def test_workspace_bytes_is_positive_for_legal_sizes_and_zero_for_refused_ones(l
     assert size(16641, 16641, 9, 1) == table + 64 * (8 + stat)        # 66 tiles: the cap
 
 
-# ---- rejections, in a child that sees no device -------------------------------------------------------------------------------------------
+# ---- rejections: the cases of the header's EINVAL list, each a row of tests/_abi_contract_table.py that the contract child sent -------
 
-@pytest.fixture(scope="module")
-def records(tmp_path_factory, lib):
-    rec_path = str(tmp_path_factory.mktemp("distill_contract") / "records.jsonl")
-    env = dict(os.environ)
-    env.update({"HIP_VISIBLE_DEVICES": "-1", "CUDA_VISIBLE_DEVICES": "-1"})
-    cmd = ["timeout", "-k", "10", "120", sys.executable, os.path.join(ROOT, "tests", "_distill_child.py"), rec_path]
-    r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=150)
-    out = {"status": r.returncode, "tail": r.stdout[-1500:] + "\n" + r.stderr[-2500:]}
-    for line in (json.loads(l) for l in open(rec_path)) if os.path.exists(rec_path) else ():
-        if "refused" in line:
-            out["error"] = "the child refused to call anything: " + line["refused"]
-        elif "proof" in line:
-            out["proof"] = line["proof"]
-        elif "i" in line:
-            out[line["i"]] = line["rc"]
-    return out
+COMMON = [("desc", None), ("student", None), ("teacher", None), ("workspace", None), ("record4", None), ("C", 0), ("C", -1), ("C", 33),
+          ("lds", 8), ("ldt", 8), ("temperature", 0.0), ("temperature", -1.0), ("temperature", math.inf), ("temperature", math.nan),
+          ("mode", 2), ("mode", -1), ("rows", 0), ("rows", -512), ("rows_per_sample", 0), ("rows_per_sample", -256),
+          ("rows_per_sample", 255),  # rows % rows_per_sample != 0
+          ("rows", 65536 * 256)]     # B = 65536: beyond SEGMIF_DISTILL_MAX_BATCH, the grid's second dimension
+MUTATIONS = {FWD: COMMON, BWD: COMMON + [("upstream", None), ("dstudent", None), ("ldd", 8)]}
+CASES = [(name, arg, value) for name in (FWD, BWD) for arg, value in MUTATIONS[name]]
 
 
-def test_the_child_saw_no_device_and_ran_every_row(records):
-    assert "error" not in records, records["error"]
-    assert records["status"] == 0 and "proof" in records, records["tail"]
-    assert not [IDS[i] for i in range(len(ROWS)) if i not in records]
-    for name in (child.FWD, child.BWD):  # every case of the header's EINVAL list is a row of each entry point
-        args = {a for a, _ in child.MUTATIONS[name]}
+def test_the_cases_cover_the_headers_einval_list():
+    for name in (FWD, BWD):  # every case of the header's EINVAL list is a row of each entry point
+        args = {a for a, _ in MUTATIONS[name]}
         assert {"desc", "student", "teacher", "workspace", "record4", "C", "lds", "ldt", "temperature", "mode", "rows", "rows_per_sample"} <= args
-    assert {"upstream", "dstudent", "ldd"} <= {a for a, _ in child.MUTATIONS[child.BWD]}
+    assert {"upstream", "dstudent", "ldd"} <= {a for a, _ in MUTATIONS[BWD]}
 
 
-@pytest.mark.parametrize("row", ROWS, ids=IDS)
-def test_rejected(records, row):
-    i = row[0]
-    assert "error" not in records, records["error"]
-    assert i in records, f"{IDS[i]}: the child wrote no record\n{records['tail']}"
-    assert records[i] == EINVAL, f"{IDS[i]} returned {records[i]}, not SEGMIF_EINVAL"
+@pytest.mark.parametrize("case", CASES, ids=[f"{name}:{arg}={value}" for name, arg, value in CASES])
+def test_rejected(records, case):
+    check_rejected(records, table.find(*case))
 
 
 # ---- the restatement, on the CPU ------------------------------------------------------------------------------------------------------------

@@ -10,13 +10,12 @@ No kernel is launched here."""
 import ctypes
 import inspect
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _abi_headers as headers
 VALUE_TOL, GRAD_TOL = 1e-5, 1e-4
 THREE_ARG = ("Fusionloss", "Fusionloss_add")
 FOUR_ARG = ("Fusionloss2", "Fusionloss4", "Fusionloss6", "Fusionloss_grad", "Fusionloss_grad2")
@@ -119,17 +118,9 @@ def test_table_validation_on_the_host():
 
 
 def test_objective_structs_match_c(lib, tmp_path):
-    from segmif_amd._lib import SegmifFusionObjective, SegmifObjTerm
-    fields = [n for n, _ in SegmifObjTerm._fields_]
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "segmif_hip.h"\nint main(){printf("%zu %zu %zu %d' + " %zu" * len(fields)
-                   + '\\n",sizeof(SegmifObjTerm),sizeof(SegmifFusionObjective),offsetof(SegmifFusionObjective,term),SEGMIF_OBJ_MAX_TERMS'
-                   + "".join(f",offsetof(SegmifObjTerm,{n})" for n in fields) + ");return 0;}")
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
-    assert got == [ctypes.sizeof(SegmifObjTerm), ctypes.sizeof(SegmifFusionObjective), SegmifFusionObjective.term.offset, 8] \
-        + [getattr(SegmifObjTerm, n).offset for n in fields]
+    """(the two structs' layout: tests/test_abi_and_host.py::test_struct_layouts_match_c)"""
+    from segmif_amd._lib import SegmifFusionObjective
+    assert headers.c_ints("segmif_hip.h", ["SEGMIF_OBJ_MAX_TERMS"], tmp_path) == [len(SegmifFusionObjective().term)] == [8]
 
 
 def test_bad_descriptors_are_refused_without_a_gpu(lib):

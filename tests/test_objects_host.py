@@ -4,29 +4,21 @@
   - the restatement tests/_objects_ref.py (min-propagation to a fixed point) against scipy.ndimage.label per class, components
     canonicalised to their minimum index, on every case of CASES under both connectivities; and against three cases worked by hand
   - object_scores on a table written by hand: an empty class, P + R = 0, the means, a bad coverage, a set status word
-  - the header's guarantees: every declared symbol is exported and bound from _lib.OBJECT_SIGNATURES and none of them is in
-    segmif_hip.h or SIGNATURES, the digest reads the header, the struct's layout is a compiled C probe's, workspace_bytes, and every
-    rejection of the header's list sent by tests/_objects_child.py in a child process that sees no device and has proved so
+  - the header's part of what tests/test_abi_and_host.py and tests/test_abi_contract_host.py check for every header: the symbols it
+    is expected to declare, its constants, workspace_bytes, and that the contract table holds every case of its EINVAL list
   - the evaluate parser's new errors; Evaluator(objects=) refuses unknown keys"""
-import ctypes
-import json
 import math
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-import _objects_child as child
+import _abi_contract_table as table
+import _abi_headers as headers
 import _objects_ref as ref
+from test_abi_contract_host import check_rejected, records  # noqa: F401 - the fixture: the contract child's records
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "segmif_objects.h")
-EINVAL = -22
-ROWS = child.rows()
-IDS = [r[1] for r in ROWS]
+NAME = "segmif_object_stats_i32"
 
 
 @pytest.fixture(scope="module")
@@ -35,11 +27,6 @@ def lib():
     if not os.path.exists(_lib.LIB_PATH):
         build.build()
     return _lib.load()
-
-
-def declared(path):
-    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(segmif_[a-z0-9_]+)\s*\(", text)))
 
 
 # ---- the restatement ----------------------------------------------------------------------------------------------------------------------
@@ -207,44 +194,18 @@ def test_settings_fail_loudly():
 
 # ---- the ABI ------------------------------------------------------------------------------------------------------------------------------
 
-def test_every_declared_symbol_is_exported_and_bound_and_not_in_the_main_header(lib):
-    from segmif_amd import _lib
-    syms = declared(HEADER)
-    assert syms == ["segmif_object_stats_i32", "segmif_object_workspace_bytes"]
-    assert sorted(_lib.OBJECT_SIGNATURES) == syms
-    others = sum((declared(os.path.join(ROOT, "include", h)) for h in ("segmif_hip.h", "segmif_distill.h", "segmif_calib.h")), [])
-    for s in syms:
-        fn = getattr(lib, s)  # exported
-        res, args = _lib.OBJECT_SIGNATURES[s]
-        assert fn.restype is res and list(fn.argtypes) == list(args), s  # bound by _lib.load()
-        assert s not in others and s not in _lib.SIGNATURES and s not in _lib.DISTILL_SIGNATURES and s not in _lib.CALIB_SIGNATURES, s
-    assert lib.segmif_abi_version() == 4  # the main header's count is what it was
-
-
-def test_the_digest_reads_the_header():
-    import inspect
+def test_the_header_declares_these_symbols_and_its_source_is_built():
     from segmif_amd import build
-    assert "segmif_objects.h" in inspect.getsource(build._digest) and "objects.hip" in build.SOURCES
+    assert headers.declared("segmif_objects.h") == [NAME, "segmif_object_workspace_bytes"]
+    assert "objects.hip" in build.SOURCES
 
 
-def test_struct_layout_matches_c(tmp_path):
+def test_the_headers_constants_and_the_descriptors_fields(tmp_path):
     from segmif_amd import _lib
-    S = _lib.SegmifObjects
-    fields = ["connectivity", "n_edges", "edges", "reserved"]
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "segmif_objects.h"\nint main(){printf("%zu", sizeof(SegmifObjects));\n'
-                   + "".join(f'printf(" %zu %zu", offsetof(SegmifObjects, {f}), sizeof(((SegmifObjects*)0)->{f}));\n' for f in fields)
-                   + 'printf(" %d %d %d %d %d %d\\n", SEGMIF_OBJECTS_TILE, SEGMIF_OBJECTS_RUN, SEGMIF_OBJECTS_MAX_EDGES, SEGMIF_OBJECTS_DECILES,'
-                     "SEGMIF_OBJECTS_MAX_FRAMES, SEGMIF_OBJECTS_WORKSPACE_PER_PIXEL);return 0;}")
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    want = [ctypes.sizeof(S)]
-    for f in fields:
-        want += [getattr(S, f).offset, getattr(S, f).size]
-    assert got[:len(want)] == want
-    assert got[len(want):] == [64, 8, _lib.OBJECTS_MAX_EDGES, _lib.OBJECTS_DECILES, _lib.OBJECTS_MAX_FRAMES, _lib.OBJECTS_WORKSPACE_PER_PIXEL]
-    assert [f for f, _ in S._fields_] == fields
+    got = headers.c_ints("segmif_objects.h", ["SEGMIF_OBJECTS_TILE", "SEGMIF_OBJECTS_RUN", "SEGMIF_OBJECTS_MAX_EDGES", "SEGMIF_OBJECTS_DECILES",
+                                              "SEGMIF_OBJECTS_MAX_FRAMES", "SEGMIF_OBJECTS_WORKSPACE_PER_PIXEL"], tmp_path)
+    assert got == [64, 8, _lib.OBJECTS_MAX_EDGES, _lib.OBJECTS_DECILES, _lib.OBJECTS_MAX_FRAMES, _lib.OBJECTS_WORKSPACE_PER_PIXEL]
+    assert [f for f, _ in _lib.SegmifObjects._fields_] == ["connectivity", "n_edges", "edges", "reserved"]
 
 
 def test_workspace_bytes_is_positive_for_legal_sizes_and_zero_for_refused_ones(lib):
@@ -257,41 +218,27 @@ def test_workspace_bytes_is_positive_for_legal_sizes_and_zero_for_refused_ones(l
         assert size(B, H, W) == 0, (B, H, W)
 
 
-# ---- rejections, in a child that sees no device -------------------------------------------------------------------------------------------
+# ---- rejections: the cases of the header's EINVAL list, each a row of tests/_abi_contract_table.py that the contract child sent -------
 
-@pytest.fixture(scope="module")
-def records(tmp_path_factory, lib):
-    rec_path = str(tmp_path_factory.mktemp("objects_contract") / "records.jsonl")
-    env = dict(os.environ)
-    env.update({"HIP_VISIBLE_DEVICES": "-1", "CUDA_VISIBLE_DEVICES": "-1"})
-    cmd = ["timeout", "-k", "10", "120", sys.executable, os.path.join(ROOT, "tests", "_objects_child.py"), rec_path]
-    r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=150)
-    out = {"status": r.returncode, "tail": r.stdout[-1500:] + "\n" + r.stderr[-2500:]}
-    for line in (json.loads(l) for l in open(rec_path)) if os.path.exists(rec_path) else ():
-        if "refused" in line:
-            out["error"] = "the child refused to call anything: " + line["refused"]
-        elif "proof" in line:
-            out["proof"] = line["proof"]
-        elif "i" in line:
-            out[line["i"]] = line["rc"]
-    return out
+MUTATIONS = [("desc", None), ("pred", None), ("label", None), ("obj", None), ("mass", None), ("status", None), ("workspace", None),
+             ("K", 0), ("K", -1), ("K", 33),
+             ("connectivity", 0), ("connectivity", 6), ("connectivity", -8), ("connectivity", 16),
+             ("n_edges", -1), ("n_edges", 4),
+             ("edges", (1024, 1024)), ("edges", (9216, 1024)), ("edges", (0, 9216)), ("edges", (-5, 9216)),
+             ("B", 0), ("B", -2), ("H", 0), ("H", -37), ("W", 0), ("W", -53),
+             ("HW", (65536, 32768)), ("HW", (46341, 46341)), ("HW", (2, 2 ** 30)),  # H * W >= 2^31
+             ("B", 32768)]  # the grid's z holds 2 B
 
 
-def test_the_child_saw_no_device_and_ran_every_row(records):
-    assert "error" not in records, records["error"]
-    assert records["status"] == 0 and "proof" in records, records["tail"]
-    assert not [IDS[i] for i in range(len(ROWS)) if i not in records]
-    args = {a for a, _ in child.MUTATIONS}  # every case of the header's EINVAL list is a row
+def test_the_cases_cover_the_headers_einval_list():
+    args = {a for a, _ in MUTATIONS}
     assert {"desc", "pred", "label", "obj", "mass", "status", "workspace", "K", "connectivity", "n_edges", "edges", "B", "H", "W", "HW"} <= args
-    assert ("B", 32768) in child.MUTATIONS  # the grid limit
+    assert ("B", 32768) in MUTATIONS  # the grid limit
 
 
-@pytest.mark.parametrize("row", ROWS, ids=IDS)
-def test_rejected(records, row):
-    i = row[0]
-    assert "error" not in records, records["error"]
-    assert i in records, f"{IDS[i]}: the child wrote no record\n{records['tail']}"
-    assert records[i] == EINVAL, f"{IDS[i]} returned {records[i]}, not SEGMIF_EINVAL"
+@pytest.mark.parametrize("case", MUTATIONS, ids=[f"{NAME}:{arg}={value}" for arg, value in MUTATIONS])
+def test_rejected(records, case):
+    check_rejected(records, table.find(NAME, ("H", "W") if case[0] == "HW" else case[0], case[1]))
 
 
 # ---- the parser and the Evaluator -----------------------------------------------------------------------------------------------------------

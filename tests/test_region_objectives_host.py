@@ -8,14 +8,13 @@
 No kernel is launched here."""
 import ctypes
 import os
-import subprocess
 
 import pytest
 import torch
 
+import _abi_headers as headers
 import _region_objective_ref as ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL = -22
 
 
@@ -164,17 +163,10 @@ def test_command_line_help_names_the_flags(capsys):
 
 # ---- the C entry points ------------------------------------------------------------------------------------------------------------------
 def test_struct_layout_matches_c(lib, tmp_path):
-    from segmif_amd._lib import SegmifRegionObjective
+    """the header's enum values against autograd's (the struct's layout: tests/test_abi_and_host.py::test_struct_layouts_match_c)"""
     from segmif_amd import autograd as ag
-    fields = [n for n, _ in SegmifRegionObjective._fields_]
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "segmif_hip.h"\nint main(){printf("%zu %d %d %d %d' + " %zu" * len(fields)
-                   + '\\n",sizeof(SegmifRegionObjective),SEGMIF_REGION_LOVASZ,SEGMIF_REGION_DICE,SEGMIF_REGION_PRESENT,SEGMIF_REGION_ALL'
-                   + "".join(f",offsetof(SegmifRegionObjective,{n})" for n in fields) + ");return 0;}")
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
-    assert got == [ctypes.sizeof(SegmifRegionObjective), 0, 1, 0, 1] + [getattr(SegmifRegionObjective, n).offset for n in fields]
+    got = headers.c_ints("segmif_hip.h", ["SEGMIF_REGION_LOVASZ", "SEGMIF_REGION_DICE", "SEGMIF_REGION_PRESENT", "SEGMIF_REGION_ALL"], tmp_path)
+    assert got == [0, 1, 0, 1]
     assert ag._REGION_KINDS == {"lovasz": 0, "dice": 1} and ag._REGION_CLASSES == {"present": 0, "all": 1}
 
 

@@ -12,16 +12,15 @@ import ctypes
 import inspect
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+import _abi_headers as headers
 import _seg_objective_ref as ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GATE = 1e-6
 CASES = {"normal": dict(reduction="mean_all"), "focal_g2": dict(gamma=2.0), "focal_g05": dict(gamma=0.5)}
 OHEM_CASES = ("ohem_thresh", "ohem_thresh_low", "ohem_topk_valid", "ohem_topk_ignored")
@@ -102,16 +101,8 @@ def test_restatement_ohem_formula_without_the_sort(golden):
 
 
 def test_struct_layout_matches_c(lib, tmp_path):
-    from segmif_amd._lib import SegmifSegObjective
-    fields = [n for n, _ in SegmifSegObjective._fields_]
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "segmif_hip.h"\nint main(){printf("%zu %d %d %d' + " %zu" * len(fields)
-                   + '\\n",sizeof(SegmifSegObjective),SEGMIF_SEG_MEAN_VALID,SEGMIF_SEG_MEAN_ALL,SEGMIF_SEG_OHEM'
-                   + "".join(f",offsetof(SegmifSegObjective,{n})" for n in fields) + ");return 0;}")
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
-    assert got == [ctypes.sizeof(SegmifSegObjective), 0, 1, 2] + [getattr(SegmifSegObjective, n).offset for n in fields]
+    """the header's enum values against autograd's (the struct's layout: tests/test_abi_and_host.py::test_struct_layouts_match_c)"""
+    assert headers.c_ints("segmif_hip.h", ["SEGMIF_SEG_MEAN_VALID", "SEGMIF_SEG_MEAN_ALL", "SEGMIF_SEG_OHEM"], tmp_path) == [0, 1, 2]
     from segmif_amd import autograd as ag
     assert ag._SEG_REDUCTIONS == {"mean": 0, "mean_all": 1, "ohem": 2}
 

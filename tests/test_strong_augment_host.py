@@ -5,14 +5,12 @@ import colorsys
 import ctypes
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
+import _abi_headers as headers
 import _strong_aug_ref as sr
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F64 = np.float64
 
 
@@ -189,20 +187,15 @@ def lib():
 
 
 def test_record_layout_matches_c(lib, tmp_path):
+    """ops' numpy record against the C struct's ctypes mirror (which tests/test_abi_and_host.py::test_struct_layouts_match_c holds to
+    the header, field by field), and the tile constants against the header"""
     from segmif_amd import _lib, ops
     names = ("jitter_on", "fb", "fc", "fs", "fh", "radius", "taps", "reserved")
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "segmif_hip.h"\nint main(){printf("%zu' + " %zu" * len(names)
-                   + '\\n",sizeof(SegmifStrongAugRec)' + "".join(f",offsetof(SegmifStrongAugRec,{n})" for n in names) + ");return 0;}")
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
     rec, dt = _lib.SegmifStrongAugRec, ops.strong_rec_dtype()
-    assert got == [ctypes.sizeof(rec)] + [getattr(rec, n).offset for n in names]
-    assert got == [dt.itemsize] + [dt.fields[n][1] for n in names]
-    assert got[0] == 64 == 4 * ops.STRONG_REC_WORDS
-    text = open(os.path.join(ROOT, "include", "segmif_hip.h")).read()
-    assert f"#define SEGMIF_STRONG_TILE_H {ops.STRONG_TILE[0]}\n" in text and f"#define SEGMIF_STRONG_TILE_W {ops.STRONG_TILE[1]}\n" in text
+    assert [f for f, _ in rec._fields_] == list(names)
+    assert [ctypes.sizeof(rec)] + [getattr(rec, n).offset for n in names] == [dt.itemsize] + [dt.fields[n][1] for n in names]
+    assert ctypes.sizeof(rec) == 64 == 4 * ops.STRONG_REC_WORDS
+    assert headers.c_ints("segmif_hip.h", ["SEGMIF_STRONG_TILE_H", "SEGMIF_STRONG_TILE_W"], tmp_path) == list(ops.STRONG_TILE)
 
 
 def _aligned(nbytes):
